@@ -17,10 +17,13 @@ Weights are random-init (no network), inputs synthetic and resident in HBM befor
 
 Everything of a step is enqueued on ONE stream (--msda-stream 1 puts the det-head MSDA calls on a side stream: valid only
 as cross-batch pipelining).
-Prints ONE JSON line (rank 0): metric/value/unit + "roofline" (the kernel with the largest measured share of a step) +
-"rooflines" (every hot kernel, each timed alone with HIP events on the stream the C ABI launches on) + "phases_ms"
-(ViT+projector / token all-gather / MSDA, max over ranks) + "cpu_baseline" (reference CPU path on the host cores: 1 warm-up
-+ 3 repetitions, median, bounded sample; N=1 only).
+Prints ONE JSON line (rank 0): metric/value/unit/ms_per_step + "config".  A plain run does nothing else: set-up, W warm-up
+steps, EXACTLY K timed steps, the outputs of the last timed step if --dump-outputs DIR is given, the line.
+--full adds everything that takes runs of its own: the InternViT-6B workload under "internvit6b" (N=1), "roofline" (the
+kernel with the largest measured share of a step) + "rooflines" (every hot kernel, each timed alone with HIP events on the
+stream the C ABI launches on) + "phases_ms" (ViT+projector / token all-gather / MSDA, max over ranks) + "clocks" + the other
+all-gather schedule (N>1) + "cpu_baseline" (reference CPU path on the host cores: 1 warm-up + 3 repetitions, median, bounded
+sample; N=1 only), and writes the full record to a detail file.
 """
 import argparse
 import json
@@ -152,6 +155,25 @@ def event_time(fn, iters, stream=None, rounds=3):
         torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1) * 1e-3 / iters)
     return float(np.median(ts))
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: all files together, float32
+
+
+def dump_outputs(path, named):
+    """named: [(name, tensor)] -> <path>/<name>.npy, float32.  A tensor that fits its share of DUMP_BUDGET_BYTES is written
+    whole, in its own shape; a larger one as a 1-D sample of its flattened elements at sorted positions drawn by a generator
+    seeded with its name and size, so the same run arguments write the same positions every time."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // len(named)
+    for name, t in named:
+        t = t.detach()
+        if t.numel() > cap:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), t.numel()])
+            idx = torch.from_numpy(np.sort(rng.choice(t.numel(), cap, replace=False))).to(t.device)
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 class ClockSampler:
@@ -675,9 +697,10 @@ def read_in_step_profile(lib, n_steps):
     return out
 
 
-def run_workload(args, workload, dev, rank, world, dist, dry):
+def run_workload(args, workload, dev, rank, world, dist, dry, dump=None):
     """One workload end to end: build, warm up, time EXACTLY args.steps steps (barrier + synchronize on both sides, max over
-    ranks), phases, in-step kernel times, rooflines.  Returns the record (rank 0) or None."""
+    ranks), write the last timed step's outputs to `dump` (rank 0) if given; with args.full also phases, in-step kernel
+    times, rooflines.  Returns the record (rank 0) or None."""
     from visionllm_amd.dist import all_gather_visual_tokens
     from visionllm_amd.dist import shard_images
     ivit = workload == "internvit6b"
@@ -720,7 +743,7 @@ def run_workload(args, workload, dev, rank, world, dist, dry):
         for t in msda_in.values():
             A.remember_geometry(t["shapes"])     # one read-back now (a det head's own shape check does it), one launch per call
         layer = None
-        if rank == 0 and not ivit:
+        if args.full and rank == 0 and not ivit:
             try:
                 layer = build_msda_layer(dev, IMAGES_PER_RANK)
                 layer[0](); torch.cuda.synchronize()
@@ -823,34 +846,46 @@ def run_workload(args, workload, dev, rank, world, dist, dry):
 
     def drain():
         if pending[0] is not None:
-            check_gathered(pending[0][0].wait()[0], pending[0][1])
+            gathered = pending[0][0].wait()[0]
+            check_gathered(gathered, pending[0][1])
             pending[0] = None
+            return gathered
+        return None
+
+    last = [None]
 
     def timed(n_steps, lag_steps):
-        """EXACTLY n_steps steps between (barrier + synchronize) pairs; the last lagged collective is drained inside."""
+        """EXACTLY n_steps steps between (barrier + synchronize) pairs; the last lagged collective is drained inside.  The
+        last step's outputs are kept in `last` (only the last: an earlier step's are freed as they would be by a caller)."""
         lag[0] = lag_steps
         sync()
         if world > 1:
             dist.barrier()
         sync()
         t0 = time.perf_counter()
-        for _ in range(n_steps):
-            step()
-        drain()                      # (the last step's collective belongs to the timed region)
+        for i in range(n_steps):
+            if i == n_steps - 1:
+                last[0] = step()
+            else:
+                step()
+        gathered = drain()           # (the last step's collective belongs to the timed region)
         sync()
         if world > 1:
             dist.barrier()
         sync()
-        return time.perf_counter() - t0
+        dt = time.perf_counter() - t0
+        if gathered is not None and last[0] is not None:
+            last[0][-1] = gathered   # (lag 1: the last step's tokens arrive with the drain)
+        return dt
 
     with torch.no_grad():
         for _ in range(args.warmup):
             step()
         drain()
-        # headline: the collective of a step is waited for INSIDE the step (lag 0: its cost is fully visible); for N > 1 the
-        # pipelined schedule (lag 1: waited for one step later, overlapping the next encoder) is timed as well, same steps
+        # headline: the collective of a step is waited for INSIDE the step (lag 0: its cost is fully visible); for N > 1 and
+        # --full the pipelined schedule (lag 1: waited for one step later, overlapping the next encoder) is timed as well, same steps
         headline_lag = args.allgather_lag if world > 1 else 0
-        sampler = ClockSampler(dev) if (not dry and rank == 0) else None
+        sampler = ClockSampler(dev) if (args.full and not dry and rank == 0) else None
         sysfs = sampler is not None and sampler.has_sysfs()
         if sysfs:
             sampler.start(True)
@@ -867,31 +902,40 @@ def run_workload(args, workload, dev, rank, world, dist, dry):
             clocks = sampler.stop()
             if clocks is not None:
                 clocks["note"] = "sampled over an untimed repetition of the same steps right after the timed region"
-        dt_alt = timed(args.steps, 1 - headline_lag) if world > 1 else None
-        # per-phase times (outside the timed region): 3 instrumented steps, median per rank, max over ranks
-        ph = []
-        for _ in range(3):
-            marks = []
-            step(marks)
-            sync()
-            ph.append([marks[i].ms_to(marks[i + 1]) for i in range(3)])
-        ph = np.median(np.array(ph), axis=0)
-        # in-step kernel times: 3 more steps with the library's recorder on (an event in front of every operator)
+        if dump is not None and rank == 0:
+            # what a caller of the step receives, in step order: the 12 MSDA outputs, then the (gathered) visual tokens
+            names = [] if dry else [f"msda_{tag}_{i}" for tag, n in (("enc", MSDA["enc_layers"]), ("dec", MSDA["dec_layers"]))
+                                    for i in range(n)]
+            dump_outputs(dump, list(zip(names + ["visual_tokens"], last[0], strict=True)))
+        last[0] = None               # (freed before any further step, as in the timed region)
+        dt_alt = timed(args.steps, 1 - headline_lag) if (args.full and world > 1) else None
+        last[0] = None
+        ph = [0.0, 0.0, 0.0]
         in_step = {}
-        if not dry and rank == 0:
-            from visionllm_amd import _lib
-            L = _lib.lib()
-            L.vllm_prof_enable(1)
+        if args.full:
+            # per-phase times (outside the timed region): 3 instrumented steps, median per rank, max over ranks
+            ph = []
             for _ in range(3):
-                step()
-                if layer is not None:
-                    layer[0]()     # (behind the step, inside the recorder's window: the `msda_layer` tag)
-            in_step = read_in_step_profile(L, 3)
-            L.vllm_prof_enable(0)
-        elif not dry:
-            for _ in range(3):
-                step()       # (all ranks run the same number of collectives)
-        drain()
+                marks = []
+                step(marks)
+                sync()
+                ph.append([marks[i].ms_to(marks[i + 1]) for i in range(3)])
+            ph = np.median(np.array(ph), axis=0)
+            # in-step kernel times: 3 more steps with the library's recorder on (an event in front of every operator)
+            if not dry and rank == 0:
+                from visionllm_amd import _lib
+                L = _lib.lib()
+                L.vllm_prof_enable(1)
+                for _ in range(3):
+                    step()
+                    if layer is not None:
+                        layer[0]()     # (behind the step, inside the recorder's window: the `msda_layer` tag)
+                in_step = read_in_step_profile(L, 3)
+                L.vllm_prof_enable(0)
+            elif not dry:
+                for _ in range(3):
+                    step()       # (all ranks run the same number of collectives)
+            drain()
     red = torch.tensor([dt, ph[0], ph[1], ph[2], dt_alt if dt_alt is not None else 0.0], device=None if dry else dev, dtype=torch.float64)
     per_rank = [red.clone()]
     if world > 1:
@@ -917,22 +961,24 @@ def run_workload(args, workload, dev, rank, world, dist, dry):
                    "tiles_per_rank": counts, "ragged_tiles": bool(args.ragged_tiles),
                    "streams": ("vit+projector | msda (side stream; cross-batch pipelining)" if args.msda_stream else "single") +
                               ("" if args.encoder_chunks <= 1 else f"; vit tiles as {args.encoder_chunks} chunks on separate streams")},
-        "phases_ms": {"vit_projector": float(red[1].item()), "token_allgather": float(red[2].item()), "msda_12_calls": float(red[3].item()),
-                      "note": "3 instrumented steps after the timed region (collective waited for before the MSDA calls), median per rank, max over ranks"},
-        "per_rank": [{"rank": r, "timed_s": float(v[0].item()), "vit_projector_ms": float(v[1].item()), "token_allgather_ms": float(v[2].item()),
-                      "msda_12_calls_ms": float(v[3].item()), "tiles": counts[r]} for r, v in enumerate(per_rank)],
+        "per_rank": [{"rank": r, "timed_s": float(v[0].item()), "tiles": counts[r]} for r, v in enumerate(per_rank)],
     }
     if dry:
         rec["dry_run_collectives_checked"] = checked[0]
-    if not dry:
+    if args.full:
+        rec["phases_ms"] = {"vit_projector": float(red[1].item()), "token_allgather": float(red[2].item()), "msda_12_calls": float(red[3].item()),
+                            "note": "3 instrumented steps after the timed region (collective waited for before the MSDA calls), median per rank, max over ranks"}
+        for pr, v in zip(rec["per_rank"], per_rank):
+            pr.update(vit_projector_ms=float(v[1].item()), token_allgather_ms=float(v[2].item()), msda_12_calls_ms=float(v[3].item()))
+    if args.full and not dry:
         rec["clocks"] = clocks
-    if world > 1:
+    if args.full and world > 1:
         alt = float(red[4].item())
         rec["allgather_lag_alt"] = {"allgather_lag_steps": 1 - headline_lag, "value": world * IMAGES_PER_RANK * args.steps / alt,
                                     "ms_per_step": alt / args.steps * 1e3,
                                     "note": "the same steps with the other collective schedule (lag 1 = a step's tokens are waited for one step "
                                             "later and overlap the next encoder; lag 0 = inside the step)"}
-    if not dry:
+    if args.full and not dry:
         bdims = ([(n_tiles * T // 4, LLM_HIDDEN, 4 * cfg["hidden_size"]), (n_tiles * T // 4, LLM_HIDDEN, LLM_HIDDEN)] if ivit else
                  [(n_tiles * T, LLM_HIDDEN, cfg["hidden_size"]), (n_tiles * T, LLM_HIDDEN, LLM_HIDDEN)])
         rl = kernel_rooflines(dev, msda_in, n_tiles, cfg, bdims, workload=workload, in_step=in_step, layer=layer)
@@ -1060,11 +1106,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the InternViT-6B workload (N=1, unless --workload says otherwise), rooflines, in-step "
+                         "kernel times, phases, clocks, the other all-gather schedule (N>1), the CPU baseline (N=1) and the detail "
+                         "file.  Off: set-up, warm-up, the timed steps and the line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the 12 MSDA outputs and the visual tokens) as "
+                         "DIR/<name>.npy, float32; an output larger than its share of %d MB as a fixed, seeded sample of its elements"
+                         % (DUMP_BUDGET_BYTES >> 20))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--workload", default="auto", choices=["auto", "vitl", "internvit6b", "both"],
                     help="vitl: the metric's ViT-L config; internvit6b: BASELINE configs[2] (5 tiles of 448^2 per image through "
                          "InternViT-6B + pixel-shuffle + internvl_mlp projector); both: the vitl line with the InternViT-6B record under "
-                         "the key \"internvit6b\"; auto (default): both on one GPU, vitl on several")
+                         "the key \"internvit6b\"; auto (default): both with --full on one GPU, vitl otherwise")
     ap.add_argument("--msda-stream", type=int, default=0, choices=[0, 1],
                     help="0 (default): one stream; 1: the MSDA calls on a side stream next to the ViT (cross-batch pipelining: in "
                          "the reference the det head of a batch depends on that batch's LLM output)")
@@ -1083,6 +1137,8 @@ def main():
                     help="CPU plumbing check (no GPU, gloo): launcher respawn, rank mapping, process group, lagged collective + drain, "
                          "phases, JSON -- with the kernels stubbed out in the bench only; the line says so and is NOT a measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         _respawn_under_launcher(args.gpus)
@@ -1107,9 +1163,9 @@ def main():
 
     workload = args.workload
     if workload == "auto":
-        workload = "both" if (world == 1 and not args.dry_run) else "vitl"
+        workload = "both" if (args.full and world == 1 and not args.dry_run) else "vitl"
     first = "internvit6b" if workload == "internvit6b" else "vitl"
-    rec = run_workload(args, first, dev, rank, world, dist, args.dry_run)
+    rec = run_workload(args, first, dev, rank, world, dist, args.dry_run, dump=args.dump_outputs)
     extra = run_workload(args, "internvit6b", dev, rank, world, dist, args.dry_run) if workload == "both" else None
     if rank == 0:
         head = {
@@ -1131,7 +1187,14 @@ def main():
         if extra is not None:
             full["internvit6b"] = dict(extra, metric="images/sec (InternViT-6B+pixel-shuffle+internvl_mlp+MSDeformAttn fwd, 1336px; BASELINE configs[2])",
                                        unit="images/sec", n_gpus=world, steps=args.steps, warmup=args.warmup)
-        emit(full, head, rec, extra)
+        if args.full:
+            emit(full, head, rec, extra)
+        else:
+            line = dict(head, **{k: v for k, v in compact_record(rec).items() if k not in ("value", "ms_per_step")})
+            if extra is not None:
+                line["internvit6b"] = {k: v for k, v in compact_record(extra).items() if k in ("value", "ms_per_step", "config")}
+            sys.stdout.write(json.dumps(_sig(line), allow_nan=False, separators=(",", ":")) + "\n")
+            sys.stdout.flush()
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -10,11 +10,12 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*extra):
+def _run(*extra, full=True):
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "2", "--warmup", "1", *extra],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run", "--steps", "2", "--warmup", "1",
+                        *(["--full"] if full else []), *extra],
                        capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     # the driver's contract: stdout holds ONE line, it is the last one, it fits well inside the driver's 8 KB stdout tail (the
@@ -103,3 +104,45 @@ def test_bench_dry_run_world_4_and_8_ragged_shards_both_algorithms_both_lags():
         # warm-up 1 + 2 timed steps x 2 schedules + 3 phase steps = 8 collectives, every one checked on rank 0
         assert rec["dry_run_collectives_checked"] == 8, rec["dry_run_collectives_checked"]
         assert rec["allgather_lag_alt"]["allgather_lag_steps"] == 1 - lag
+
+
+def test_plain_run_times_the_steps_only_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full the line carries the headline only (no phases, no second schedule); --dump-outputs writes what the last
+    timed step returned, float32, and the same arguments write the same files."""
+    import numpy as np
+    for world in (1, 2):
+        dumps = []
+        for rep in range(2):
+            d = tmp_path / f"w{world}_{rep}"
+            rec = _run("--gpus", str(world), "--allgather-lag", "1" if world > 1 else "0", "--dump-outputs", str(d), full=False)
+            assert rec["n_gpus"] == world and rec["steps"] == 2 and rec["ms_per_step"] > 0 and rec["value"] > 0
+            assert {"metric", "unit", "higher_is_better", "dtype"} <= set(rec)
+            assert not {"phases_ms", "allgather_lag_alt", "clocks", "rooflines", "cpu_baseline", "internvit6b", "detail"} & set(rec)
+            # warm-up 1 + 2 timed steps: nothing else runs a collective
+            assert rec["dry_run_collectives_checked"] == 3, rec["dry_run_collectives_checked"]
+            assert sorted(os.listdir(d)) == ["visual_tokens.npy"]
+            dumps.append(np.load(d / "visual_tokens.npy"))
+        tok = dumps[0]
+        assert tok.dtype == np.float32 and tok.shape == (world * 40, 8, 64)
+        # dry-run tokens carry (rank, step): the dump holds the LAST timed step of every rank (warm-up 1 + 2 steps -> step 2)
+        for r in range(world):
+            assert (tok[r * 40:(r + 1) * 40] == r + 2).all()
+        assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_dump_outputs_samples_large_outputs_at_fixed_positions(tmp_path):
+    """An output larger than its share of the budget is written as a seeded sample: the same positions every time, within budget."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(bench.DUMP_BUDGET_BYTES // 4 + 1, dtype=torch.float32)     # (< 2^24: every index exact in float32)
+    small = torch.arange(12, dtype=torch.bfloat16).reshape(3, 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [("big", big), ("small", small)])
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.ndim == 1 and a.size == bench.DUMP_BUDGET_BYTES // 4 // 2
+    assert np.array_equal(a, b) and (np.diff(a) > 0).all()          # sorted, distinct positions of arange: the values are the indices
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.float().numpy())
+    assert sum(f.stat().st_size for f in (tmp_path / "a").glob("*.npy")) <= 64 * 1000 * 1000
