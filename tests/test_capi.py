@@ -289,6 +289,23 @@ def test_attention_lane_swaps_read_both_results(tmp_path):
         assert swaps > 0, name
 
 
+
+def test_retired_msda_tiled_values_are_rejected():
+    """msda_tiled 3 (generation 2) and 18 / 19 (generation 8) left the library: vllm_set_option refuses them, as it refuses 4, 6, 7,
+    15, 16 and out-of-range values, and leaves the option as it was."""
+    L = _lib.lib()
+    old = _lib.set_option("msda_tiled", 9)
+    try:
+        for v in (-1, 3, 4, 6, 7, 15, 16, 18, 19, 22):
+            assert _lib.set_option("msda_tiled", v) == -1, v                 # VLLM_EINVAL
+            assert "msda_tiled must be one of" in L.vllm_last_error().decode()
+            assert _lib.set_option("msda_tiled", 9) == 9, v                  # unchanged
+        for v in (0, 1, 2, 5, 8, 9, 10, 11, 12, 13, 14, 17, 20, 21):
+            _lib.set_option("msda_tiled", v)
+            assert _lib.set_option("msda_tiled", 9) == v
+    finally:
+        _lib.set_option("msda_tiled", old)
+
 def test_every_runtime_option_is_documented_in_the_header():
     """vllm_set_option's names (csrc/runtime.cpp) are part of the boundary: each must be described in include/vllm_hip.h."""
     import re

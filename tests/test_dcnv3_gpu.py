@@ -97,6 +97,31 @@ def test_tiled_kernel_vs_oracle_and_gather_kernel(N, H, W, G, C, k, s, p, d, sca
         torch.testing.assert_close(out, plain, rtol=1e-5, atol=1e-5)
 
 
+
+def test_every_accepted_dcnv3_tiled_value_matches_the_oracle():
+    """Every value vllm_set_option("dcnv3_tiled") accepts (0 gather, 1 pipelined, 3 two blocks per CU; 2 / 4 = 1 / 3 with the phase
+    clock, whose results were compared with nothing before) at a 3 x 3, group-channels-32 shape every kernel serves: oracle
+    tolerance of test_tiled_kernel_vs_oracle_and_gather_kernel, two runs bit-identical."""
+    from visionllm_amd import _lib
+    N, H, W, G, C, k = 2, 42, 42, 5, 32, 3
+    rng = np.random.default_rng(11)
+    inp = rng.standard_normal((N, H, W, G * C)).astype(np.float32)
+    off = rng.standard_normal((N, H, W, G * k * k * 2)).astype(np.float32)
+    msk = rng.random((N, H, W, G * k * k)).astype(np.float32)
+    a = (torch.from_numpy(inp).to(DEV), torch.from_numpy(off).to(DEV), torch.from_numpy(msk).to(DEV), k, k, 1, 1, 1, 1, 1, 1, G, C,
+         1.0)
+    ref = O.forward(inp, off, msk, k, k, 1, 1, 1, 1, 1, 1, G, C, 1.0)
+    old = _lib.set_option("dcnv3_tiled", 1)
+    try:
+        for mode in range(5):
+            _lib.set_option("dcnv3_tiled", mode)
+            assert _lib.set_option("dcnv3_tiled", mode) == mode      # (accepted: the previous value reads back)
+            out, again = A.dcnv3_forward(*a), A.dcnv3_forward(*a)
+            assert torch.equal(out, again), f"dcnv3_tiled = {mode}: two runs differ"
+            np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=2e-5, atol=2e-5, err_msg=f"dcnv3_tiled = {mode}")
+    finally:
+        _lib.set_option("dcnv3_tiled", old)
+
 def test_nonfinite_data_and_locations_do_not_leak():
     N, H, W, G, C, k = 1, 6, 6, 2, 4, 3
     inp = torch.randn(N, H, W, G * C)

@@ -140,6 +140,29 @@ def test_tiled_kernel_matches_gather_kernel(mode):
         _lib.set_option("msda_tiled", old)
 
 
+
+MSDA_TILED_ACCEPTED = (0, 1, 2, 5, 8, 9, 10, 11, 12, 13, 14, 17, 20, 21)
+
+
+def test_every_accepted_msda_tiled_value_matches_the_oracle():
+    """Every value vllm_set_option("msda_tiled") accepts, at the cfg-4 encoder shape (nested 2x pyramid, Lq == S, D = 32, P = 4,
+    L = 4: every generation applies): 0 gather; 1 / 20 generation 9 (21 + phase clock); 2 / 8 / 9 generation 4 (5 + phase clock);
+    10-14 / 17 generation 6 (10 / 14 + phase clock).  The phase-clock builds produce the profiles' numbers: their results must be the
+    oracle's too.  Each value: oracle tolerance of test_tiled_kernel_matches_gather_kernel, two runs bit-identical."""
+    from visionllm_amd import _lib
+    g = make_inputs(2, 8, 32, CFG4_SHAPES, 4, mode="encoder_like", seed=1)
+    ref = O.forward(g["value"], g["shapes"], g["lsi"], g["loc"], g["attw"])
+    old = _lib.set_option("msda_tiled", 1)
+    try:
+        for variant in MSDA_TILED_ACCEPTED:
+            assert _lib.set_option("msda_tiled", variant) >= 0, variant
+            out = _run(g)
+            again = _run(g)
+            assert torch.equal(out, again), f"msda_tiled = {variant}: two runs differ"
+            np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=4e-6, atol=4e-6, err_msg=f"msda_tiled = {variant}")
+    finally:
+        _lib.set_option("msda_tiled", old)
+
 PYRAMIDS = {
     "L4_partial_tiles": [(72, 104), (36, 52), (18, 26), (9, 13)],     # 104 / 16 = 6.5 tiles per row
     "L3": [(64, 80), (32, 40), (16, 20)],

@@ -336,7 +336,7 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dcnv3_fwd_pipe_kernel(const flo
     asm volatile("ds_read_b128 %0, %8\n\tds_read_b128 %1, %9\n\tds_read_b128 %2, %10\n\tds_read_b128 %3, %11\n\t"             \
                  "ds_read_b128 %4, %12\n\tds_read_b128 %5, %13\n\tds_read_b128 %6, %14\n\tds_read_b128 %7, %15"                \
                  : "=&v"(SET.a0), "=&v"(SET.a1), "=&v"(SET.a2), "=&v"(SET.a3), "=&v"(SET.c0), "=&v"(SET.c1), "=&v"(SET.c2), "=&v"(SET.c3) \
-                 : "v"(T0), "v"(T0 ^ 32), "v"(T0 ^ 64), "v"(T0 ^ 96), "v"(B0), "v"(B0 ^ 32), "v"(B0 ^ 64), "v"(B0 ^ 96));
+                 : "v"(T0), "v"(T0 ^ 32), "v"(T0 ^ 64), "v"(T0 ^ 96), "v"(B0), "v"(B0 ^ 32), "v"(B0 ^ 64), "v"(B0 ^ 96) : "memory");
 #define DP_RDP(SET, R_, LQ)                                                                                                   \
     {                                                                                                                         \
         const int t0_ = dp_qbi<LQ>(pc.top[R_]) + lbase, b0_ = dp_qbi<LQ>(pc.bot[R_]) + lbase;                                 \
@@ -350,8 +350,8 @@ __global__ __launch_bounds__(DP_THREADS, 2) void dcnv3_fwd_pipe_kernel(const flo
         float eT = pr_s ? x2 : x1, eB = pr_s ? x4 : x3;                                                                       \
         asm volatile("" : "+v"(t0_), "+v"(b0_), "+v"(eT), "+v"(eB));                                                          \
         dma_round();                                                                                                          \
-        if (CNT) asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(SET.a0), "+v"(SET.a1), "+v"(SET.a2), "+v"(SET.a3), "+v"(SET.c0), "+v"(SET.c1), "+v"(SET.c2), "+v"(SET.c3)); \
-        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(SET.a0), "+v"(SET.a1), "+v"(SET.a2), "+v"(SET.a3), "+v"(SET.c0), "+v"(SET.c1), "+v"(SET.c2), "+v"(SET.c3)); \
+        if (CNT) asm volatile("s_waitcnt lgkmcnt(8)" : "+v"(SET.a0), "+v"(SET.a1), "+v"(SET.a2), "+v"(SET.a3), "+v"(SET.c0), "+v"(SET.c1), "+v"(SET.c2), "+v"(SET.c3) : : "memory"); \
+        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(SET.a0), "+v"(SET.a1), "+v"(SET.a2), "+v"(SET.a3), "+v"(SET.c0), "+v"(SET.c1), "+v"(SET.c2), "+v"(SET.c3) : : "memory"); \
         _Pragma("unroll") for (int c = 0; c < 4; c += 2) {                                                                    \
             float2_t u0 = {acc[0][c], acc[0][c + 1]}, u1 = {acc[1][c], acc[1][c + 1]};                                        \
             float2_t u2 = {acc[2][c], acc[2][c + 1]}, u3 = {acc[3][c], acc[3][c + 1]};                                        \

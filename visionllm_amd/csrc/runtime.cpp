@@ -85,8 +85,10 @@ extern "C" int vllm_set_option(const char *name, int value)
     if (!name) return VLLM_EINVAL;
     if (!strcmp(name, "msda_tiled")) {
         const int old = vllm::msda_tiled_enabled();
-        if (value < 0 || value > 21 || value == 4 || value == 6 || value == 7 || value == 15 || value == 16) {
-            vllm::set_error("msda_tiled must be one of 0, 1, 2, 3, 5, 8, 9, 10..14, 17 .. 21");
+        // 3 (generation 2) and 18 / 19 (generation 8) left the library in round 5: rejected here, as 15 / 16 are
+        if (value < 0 || value > 21 || value == 3 || value == 4 || value == 6 || value == 7 || value == 15 || value == 16 || value == 18 ||
+            value == 19) {
+            vllm::set_error("msda_tiled must be one of 0, 1, 2, 5, 8, 9, 10..14, 17, 20, 21");
             return VLLM_EINVAL;
         }
         vllm::g_msda_tiled = value;
