@@ -13,6 +13,12 @@
  * (AT_ASSERTM in visionllmv2/model/unipose/ops/src/cuda/ms_deform_attn_cuda.cu:28-52).
  *
  * Reference paths are relative to /root/reference/VisionLLMv2/.
+ *
+ * Alignment: any pointer need only be aligned to its element type unless the declaration says more ("Alignment: ..." below);
+ * faster kernels behind an entry point are picked by the pointers' alignment and agree with the others to fp32 rounding.  One with a
+ * stated requirement returns VLLM_EINVAL (and writes nothing) for a pointer that misses it, and vllm_last_error() names it.
+ * Callers passing views at a storage offset (x[1:], a chunk of one flat buffer) copy such an operand into an aligned tensor first,
+ * as the Python mirror does.
  */
 #ifndef VLLM_HIP_H
 #define VLLM_HIP_H
@@ -144,6 +150,7 @@ int vllm_msda_forward_f32_geo(const float *value, const int64_t *shapes, const i
                               float *out, vllm_stream_t stream);
 /* bf16 value/out, fp32 loc/attw, fp32 accumulation (extension: the reference upcasts bf16 to fp32 first,
  * modeling_ov_grounding_dino_mask_dn.py:764-766; this variant halves the gathered bytes). */
+/* Alignment: value and out 16 bytes, loc 8 bytes. */
 int vllm_msda_forward_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi,
                            const float *loc, const float *attw,
                            int B, int S, int M, int D, int L, int Lq, int P,
@@ -201,6 +208,8 @@ long vllm_msda_layer_workspace_bytes(const VllmMsdaLayerDesc *desc, int B, int L
 /* query [B, Lq, C] bf16 (position embedding already added by the caller), reference_points [B, Lq, L, ref_dim] fp32,
  * input_flatten [B, S, C] bf16, padding_mask [B, S] uint8 (non-zero = padded) or NULL, spatial_shapes [L, 2] /
  * level_start_index [L] device int64 (H, W), out [B, Lq, C] bf16.  d_model % 64 == 0, d_model / n_heads % 4 == 0. */
+/* Alignment: query, input_flatten and every weight / bias of the descriptor 16 bytes (GEMM operands); reference_points 8 bytes (16
+ * with ref_dim 4); workspace 16 bytes. */
 int vllm_msda_layer_forward(const VllmMsdaLayerDesc *desc, const uint16_t *query, const float *reference_points,
                             const uint16_t *input_flatten, const uint8_t *padding_mask, const int64_t *spatial_shapes,
                             const int64_t *level_start_index, int B, int Lq, int S, uint16_t *out, void *workspace,
@@ -211,6 +220,7 @@ int vllm_msda_layer_forward(const VllmMsdaLayerDesc *desc, const uint16_t *query
 int vllm_msda_prep_f32(float *offsets_to_locations, float *logits_to_weights, const float *reference_points,
                        const int64_t *spatial_shapes, long R, int M, int L, int P, int ref_dim, int use_4d_normalizer,
                        vllm_stream_t stream);
+/* Alignment (vllm_f32_to_bf16): src 16 bytes, dst 8 bytes. */
 int vllm_f32_to_bf16(const float *src, uint16_t *dst, long n, vllm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
@@ -248,6 +258,7 @@ int vllm_dcnv3_backward_f64(const double *input, const double *offset, const dou
 /* Half-precision backward (round 5; dcnv3_cuda.cu:147 dispatches AND_HALF too): operands and gradients are binary16, the arithmetic
  * is the fp32 backward on widened copies in the CALLER's workspace (vllm_dcnv3_backward_f16_workspace bytes, 16-byte aligned; -1 for
  * an invalid geometry), every gradient rounded once.  grad_input need not be zero-filled here (the fp32 accumulator is). */
+/* Alignment (vllm_dcnv3_backward_f16): all seven tensors and the workspace 16 bytes. */
 long vllm_dcnv3_backward_f16_workspace(int N, int H, int W, int G, int C, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw);
 int vllm_dcnv3_backward_f16(const uint16_t *input, const uint16_t *offset, const uint16_t *mask, const uint16_t *grad_output, int N, int H,
                             int W, int G, int C, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, float offset_scale,
@@ -261,6 +272,7 @@ int vllm_dcnv3_backward_f16(const uint16_t *input, const uint16_t *offset, const
  * mean over a region's sampled points, visionllmv2/model/region_encoder.py:24-47, 127-141.
  * input [N, C, H, W] fp32 (contiguous NCHW), coords [N, P, 2] (x, y) in [0, 1], valid [N, P] uint8.
  * ------------------------------------------------------------------------------------------------ */
+/* Alignment (both): coords 8 bytes. */
 int vllm_point_sample_f32(const float *input, const float *coords, int N, int C, int H, int W, int P, float *out /* [N,C,P] */,
                           vllm_stream_t stream);
 /* out[n, c] = sum_p valid * sample / sum_p valid, 0 for a region without points ((x / 0).nan_to_num() of the reference). */
@@ -297,6 +309,7 @@ int vllm_point_sample_mean_f32(const float *input, const float *coords, const ui
  * K % 64 == 0, N % 4 == 0, 16-byte aligned operands.  bias/scale may be NULL.  For VLLM_EPI_EMBED `res` is the
  * position table [P+1, N] (row stride ldr) and P the patches per image; output row of input row m is
  * (m / P) * (P + 1) + 1 + m % P. */
+/* Alignment (every vllm_gemm_bf16*): X and W 16 bytes, Y 8 bytes (16 with VLLM_EPI_F32), scratch 16 bytes. */
 int vllm_gemm_bf16(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y,
                    int M, int N, int K, int ldx, int ldw, int ldy, int epilogue,
                    const uint16_t *scale, const uint16_t *res, int ldr, int P, vllm_stream_t stream);
@@ -339,6 +352,7 @@ int vllm_gemm_bf16_ln(const uint16_t *X, const uint16_t *W, const uint16_t *bias
 
 /* B5: InternRMSNorm / apex FusedRMSNorm (modeling_intern_vit.py:33-58): y = w * bf16(x * rsqrt(mean(x^2)+eps)).
  * Row strides allow the in-place QK-RMSNorm over the q / k column blocks of the qkv buffer (:131-134). */
+/* Alignment (both norms): x, y, weight and bias 16 bytes. */
 int vllm_rmsnorm_bf16(const uint16_t *x, int ldx, const uint16_t *weight, uint16_t *y, int ldy,
                       long rows, int C, float eps, vllm_stream_t stream);
 /* nn.LayerNorm (CLIP pre_layrnorm / layer_norm1,2; vl_bridge LayerNorm, modeling_visionllmv2.py:166-167). */
@@ -347,6 +361,7 @@ int vllm_layernorm_bf16(const uint16_t *x, int ldx, const uint16_t *weight, cons
 
 /* B4: FlashAttention.forward(qkv[B,S,3,H,D]) -> out[B,S,H,D], non-causal, no mask, dropout 0
  * (visionllmv2/model/internvit/flash_attention.py:30-75).  D in {64,128}. */
+/* Alignment (both): qkv 16 bytes, out 8 bytes. */
 int vllm_attn_fwd_qkvpacked_bf16(const uint16_t *qkv, uint16_t *out, int B, int S, int H, int D,
                                  float softmax_scale, vllm_stream_t stream);
 /* The same for IEEE-half qkv / out (round 4): the reference's module accepts both dtypes (`assert qkv.dtype in [torch.float16,
@@ -361,11 +376,13 @@ int vllm_im2col_patches(const void *pixels, int pixel_is_f32, uint16_t *A, int N
 
 /* pixel_shuffle(scale 0.5) of modeling_visionllmv2.py:381-392 applied to hidden[:, tok0:]:
  * hidden [N, tok0+hw*hw, C] (tile stride / row stride in elements, tok0 = 1 skips CLS) -> out [N, (hw/2)^2, 4C]. */
+/* Alignment: hidden and out 16 bytes. */
 int vllm_pixel_shuffle_bf16(const uint16_t *hidden, long tile_stride, int ld, int tok0, uint16_t *out,
                             int N, int hw, int C, vllm_stream_t stream);
 
 /* Visual-token splice (modeling_visionllmv2.py:582-605): dst[idx[i], :] = src[i, :] for i < n.  `idx` (device int64)
  * holds the flattened [B*L_txt] positions of the <im_patch> slots; rows with idx outside [0, dst_rows) are skipped. */
+/* Alignment: src and dst 16 bytes. */
 int vllm_scatter_rows_bf16(const uint16_t *src, const int64_t *idx, uint16_t *dst, long n, int C, long dst_rows,
                            vllm_stream_t stream);
 
@@ -380,6 +397,7 @@ int vllm_scatter_rows_bf16(const uint16_t *src, const int64_t *idx, uint16_t *ds
  * (tiles of samples with an image x T), error, <im_patch> slots}; status: device int32 [4] or NULL -> {slots, tokens offered, error,
  * tiles kept}. */
 long vllm_splice_workspace_ints(int B, int L, int n_tiles);
+/* Alignment: image_features and inputs_embeds 16 bytes. */
 int vllm_splice_visual_tokens_bf16(const int64_t *input_ids, long imp_token_id, const uint16_t *image_features,
                                    const int32_t *tiles_per_sample, int B, int L, int n_tiles, int T, int C,
                                    uint16_t *inputs_embeds, int32_t *workspace, int32_t *status, vllm_stream_t stream);
@@ -388,6 +406,7 @@ int vllm_splice_visual_tokens_bf16(const int64_t *input_ids, long imp_token_id, 
  * <region> slots, :775-787 [EMB] hidden states -> text_query) as index bookkeeping + ONE row mover:
  * dst[dst_idx[i], :] = src[src_idx[i], :] for i < n (device int64 indices; NULL = the identity; rows whose index falls
  * outside [0, src_rows) / [0, dst_rows) are skipped).  Rows are C bf16, C % 8 == 0. */
+/* Alignment: src and dst 16 bytes. */
 int vllm_copy_rows_bf16(const uint16_t *src, const int64_t *src_idx, uint16_t *dst, const int64_t *dst_idx, long n,
                         int C, long src_rows, long dst_rows, vllm_stream_t stream);
 
@@ -449,6 +468,8 @@ long vllm_vit_workspace_bytes(const VllmVitDesc *desc, int n_tiles);
  * [n_tiles, 1+P, C] bf16 contiguous (entry i = input of layer i, last = final output, exactly the tuple
  * InternVisionEncoder returns with output_hidden_states=True).  Entries may be NULL except the last: the
  * library then keeps that state in its workspace (nobody reads it). */
+/* Alignment: every parameter of the descriptor and every hidden-state pointer 16 bytes (GEMM / norm operands); workspace 16
+ * bytes.  pixels: element alignment only. */
 int vllm_vit_forward(const VllmVitDesc *desc, const void *pixels, int n_tiles,
                      uint16_t *const *hidden_states, void *workspace, long workspace_bytes,
                      vllm_stream_t stream);
@@ -480,6 +501,7 @@ long vllm_bridge_workspace_bytes(const VllmBridgeDesc *desc, int n_tiles, int to
 /* hidden: the selected hidden state [n_tiles, skip_cls+T, C] bf16; out
  * [n_tiles, T or T/4, out_features] bf16 -- row-major [tile, token, C_llm], the layout the token splice
  * (modeling_visionllmv2.py:582-605) consumes. */
+/* Alignment: hidden, out, the LayerNorm and Linear parameters and the workspace 16 bytes. */
 int vllm_bridge_forward(const VllmBridgeDesc *desc, const uint16_t *hidden, int n_tiles, int T, int C,
                         uint16_t *out, void *workspace, long workspace_bytes, vllm_stream_t stream);
 

@@ -102,6 +102,16 @@ def check(rc: int, what: str = ""):
         raise RuntimeError(f"{what or 'libvllm_hip'} failed ({rc}): {msg}")
 
 
+def aligned(t, align=16):
+    """``t`` as a contiguous tensor whose data pointer is a multiple of ``align`` bytes.  A tensor that already is one is returned
+    as it is (no copy, so aligned calls launch what they always did); a view at another storage offset is copied into a fresh
+    allocation (the caching allocator's blocks start 512-byte aligned).  For entry points that require the alignment."""
+    t = t.contiguous()
+    if t.data_ptr() % align:
+        t = t.clone()
+    return t
+
+
 def ptr(t):
     """Device pointer of a torch tensor (0 for None / empty)."""
     if t is None:
@@ -161,10 +171,14 @@ _workspaces = {}
 
 
 def workspace(device, nbytes, slot=0):
-    """Grow-only per-device scratch buffer (torch owns the memory; the library never allocates).  ``slot`` names
-    independent buffers for work that runs concurrently on different streams."""
+    """Grow-only scratch buffer per (device, caller's current stream, ``slot``) (torch owns the memory; the library never
+    allocates).  Keying by stream keeps work enqueued on different streams off each other's scratch: a buffer is only ever
+    used by work on the stream it was allocated for, so when it grows the old one goes back to the caching allocator on that
+    same stream, behind every kernel that may still read it.  ``slot`` names further independent buffers of one stream (the
+    encoder's chunks, which it enqueues on side streams ordered behind the caller's).  Repeated calls on one stream with no
+    growth allocate nothing."""
     import torch
-    key = (str(device), slot)
+    key = (str(device), torch.cuda.current_stream(device).cuda_stream, slot)
     buf = _workspaces.get(key)
     if buf is None or buf.numel() < nbytes:
         buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)

@@ -28,7 +28,7 @@ def pixel_shuffle(x, scale_factor=0.5):
     n, w, h, c = x.shape
     if w != h:
         raise ValueError("pixel_shuffle: square token grid expected")
-    x = x.contiguous()
+    x = _lib.aligned(x)   # (16-byte aligned rows: a view at another storage offset is copied)
     out = torch.empty((n, w // 2, h // 2, 4 * c), dtype=x.dtype, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().vllm_pixel_shuffle_bf16(_lib.ptr(x), w * h * c, c, 0, _lib.ptr(out), n, w, c,
@@ -36,8 +36,16 @@ def pixel_shuffle(x, scale_factor=0.5):
     return out
 
 
-def _desc_for(mod, kind, pixel_shuffle_flag, skip_cls):
-    P = _lib.ptr
+def _desc_for(mod, kind, pixel_shuffle_flag, skip_cls, keep):
+    """-> descriptor of the projector's parameters.  The GEMMs and the LayerNorm read them as 16-byte vectors: a parameter that is
+    a view at another storage offset is passed as an aligned copy, appended to ``keep`` (alive until the launch is enqueued)."""
+    def P(t):
+        if t is None:
+            return None
+        a = _lib.aligned(t.detach())
+        if a.data_ptr() != t.data_ptr():
+            keep.append(a)
+        return _lib.ptr(a)
     if kind == "linear":
         lin = [mod]
         ln = None
@@ -55,8 +63,8 @@ def _desc_for(mod, kind, pixel_shuffle_flag, skip_cls):
                             ln_eps=ln.eps if ln is not None else 0.0, ln_w=P(ln.weight) if ln is not None else None,
                             ln_b=P(ln.bias) if ln is not None else None)
     for i, m in enumerate(lin):
-        d.w[i] = m.weight.data_ptr()
-        d.b[i] = m.bias.data_ptr() if m.bias is not None else None
+        d.w[i] = P(m.weight).value
+        d.b[i] = P(m.bias).value if m.bias is not None else None
     return d
 
 
@@ -84,10 +92,11 @@ class _BridgeMixin:
             # grad_fn: refuse loudly instead of silently cutting the gradient
             raise RuntimeError("vl_bridge (native): forward-only kernels -- call under torch.no_grad() or freeze the "
                                "projector and its input (requires_grad_(False)); training the projector needs the torch modules")
-        x = x.contiguous()
+        x = _lib.aligned(x)   # (the GEMM loaders need 16-byte aligned rows: a view at another storage offset is copied)
         n, rows, C = x.shape
         T = rows - 1 if skip_cls else rows
-        return _run(_desc_for(self, self.vl_bridge_type, pixel_shuffle_flag, skip_cls), x, n, T, C)
+        keep = []
+        return _run(_desc_for(self, self.vl_bridge_type, pixel_shuffle_flag, skip_cls, keep), x, n, T, C)
 
     def forward(self, x):  # what modeling_visionllmv2.py:579 calls
         lead = x.shape[:-2] if x.dim() > 3 else None

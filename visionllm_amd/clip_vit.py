@@ -14,7 +14,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .vit_common import (EncoderPlan, _require_bf16_cuda, fold_norm_into_linear, kpad_for, model_output, norm_folding_applies,
+from .vit_common import (EncoderPlan, _require_bf16_cuda, fold_norm_into_linear, kpad_for, model_output, norm_folding_applies, plan_ptr,
                          padded_patch_weight, run_encoder)
 
 try:
@@ -117,7 +117,7 @@ class CLIPVisionModel(nn.Module):
         plan.keep = [pw]
         L = len(vm.encoder.layers)
         layers = (_lib.VllmVitLayer * L)()
-        P = _lib.ptr
+        P = plan_ptr(plan)
         for i, lyr in enumerate(vm.encoder.layers):
             a = lyr.self_attn
             qkv_w = torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0).detach().contiguous()
@@ -164,8 +164,9 @@ class CLIPVisionModel(nn.Module):
         n, S, C = last.shape
         pooled = torch.empty((n, C), dtype=last.dtype, device=last.device)
         pl = self.vision_model.post_layernorm
+        plw, plb = _lib.aligned(pl.weight.detach()), _lib.aligned(pl.bias.detach())   # (16-byte aligned: views are copied)
         with torch.cuda.device(last.device):
-            _lib.check(_lib.lib().vllm_layernorm_bf16(_lib.ptr(last), S * C, _lib.ptr(pl.weight), _lib.ptr(pl.bias),
+            _lib.check(_lib.lib().vllm_layernorm_bf16(_lib.ptr(last), S * C, _lib.ptr(plw), _lib.ptr(plb),
                                                       _lib.ptr(pooled), C, n, C, pl.eps,
                                                       _lib.current_stream(last.device)), "vllm_layernorm_bf16")
         hs = tuple(states) if output_hidden_states else None

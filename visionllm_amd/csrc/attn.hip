@@ -309,7 +309,7 @@ int attn_fwd_launch(AttnArgs a, int D, hipStream_t st)
     VLLM_REQUIRE(aligned16(a.q) && aligned16(a.k) && aligned16(a.v) && (reinterpret_cast<uintptr_t>(a.out) & 7u) == 0 &&
                      a.q_ts % 8 == 0 && a.k_ts % 8 == 0 && a.v_ts % 8 == 0 && a.q_hs % 8 == 0 && a.k_hs % 8 == 0 &&
                      a.v_hs % 8 == 0 && a.q_bs % 8 == 0 && a.k_bs % 8 == 0 && a.v_bs % 8 == 0,
-                 "attn: q/k/v must be 16-byte aligned with strides multiple of 8 elements");
+                 "attn: q/k/v must be 16-byte aligned with strides multiple of 8 elements, out 8-byte aligned");
     // attn_variant: 32 = automatic (deferred rescale, O through LDS, class-token split).  bit 1: deferred rescale; bit 4: no padding
     // trim (and no split); bit 6: O through LDS; bit 7: NO class-token split; bit 10: class token out of the KEY tiling only (what
     // automatic does anyway when the body rows leave no spare wave).  Bits 0, 2, 3 (rounds 2-5 schedules) are ignored.

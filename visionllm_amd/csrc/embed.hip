@@ -240,7 +240,7 @@ int pixel_shuffle_launch(const uint16_t *in, long in_tile_stride, int ldin, int 
 {
     VLLM_REQUIRE(in && out, "pixel_shuffle: null pointer");
     VLLM_REQUIRE(hw % 2 == 0 && C % 8 == 0 && ldin % 8 == 0 && in_tile_stride % 8 == 0 && aligned16(in) && aligned16(out),
-                 "pixel_shuffle: needs even grid, C %% 8 == 0 and 16-byte alignment");
+                 "pixel_shuffle: needs even grid, C %% 8 == 0 and 16-byte aligned hidden / out");
     if (N == 0) return VLLM_OK;
     VLLM_LAUNCH(pixel_shuffle_kernel, dim3(grid_for((long)N * hw * hw * C / 8)), dim3(256), 0, st, in,
                        in_tile_stride, ldin, tok0, out, N, hw, C);
@@ -268,7 +268,7 @@ extern "C" int vllm_scatter_rows_bf16(const uint16_t *src, const int64_t *idx, u
 {
     VLLM_REQUIRE(n >= 0 && C > 0 && C % 8 == 0, "scatter_rows: C must be a positive multiple of 8");
     if (n == 0) return VLLM_OK;
-    VLLM_REQUIRE(src && idx && dst && aligned16(src) && aligned16(dst), "scatter_rows: null or unaligned pointer");
+    VLLM_REQUIRE(src && idx && dst && aligned16(src) && aligned16(dst), "scatter_rows: null pointer, or src / dst not 16-byte aligned");
     VLLM_LAUNCH(scatter_rows_kernel, dim3(grid_for(n * 64)), dim3(256), 0, (hipStream_t)stream, src, idx, dst, n, C,
                 dst_rows);
     VLLM_CHECK_LAUNCH("scatter_rows_kernel");
@@ -284,8 +284,8 @@ extern "C" int vllm_splice_visual_tokens_bf16(const int64_t *input_ids, long imp
     VLLM_REQUIRE(B >= 0 && L >= 0 && n_tiles >= 0 && T >= 0 && C > 0 && C % 8 == 0, "splice_visual_tokens: bad sizes (C must be a positive multiple of 8)");
     VLLM_REQUIRE(B <= SPL_MAXB && (long)B * L < (1L << 31) && (long)n_tiles * T < (1L << 31), "splice_visual_tokens: too many samples / positions / tokens for one call");
     VLLM_REQUIRE(workspace, "splice_visual_tokens: null workspace");
-    VLLM_REQUIRE((long)B * L == 0 || (input_ids && inputs_embeds && aligned16(inputs_embeds)), "splice_visual_tokens: null or unaligned pointer");
-    VLLM_REQUIRE((long)n_tiles * T == 0 || (image_features && aligned16(image_features)), "splice_visual_tokens: null or unaligned image_features");
+    VLLM_REQUIRE((long)B * L == 0 || (input_ids && inputs_embeds && aligned16(inputs_embeds)), "splice_visual_tokens: null pointer, or inputs_embeds not 16-byte aligned");
+    VLLM_REQUIRE((long)n_tiles * T == 0 || (image_features && aligned16(image_features)), "splice_visual_tokens: null image_features, or not 16-byte aligned");
     SplTiles tv;
     int mode = 0;
     const int32_t *tdev = nullptr;
@@ -314,7 +314,7 @@ extern "C" int vllm_copy_rows_bf16(const uint16_t *src, const int64_t *src_idx, 
 {
     VLLM_REQUIRE(n >= 0 && C > 0 && C % 8 == 0, "copy_rows: C must be a positive multiple of 8");
     if (n == 0) return VLLM_OK;
-    VLLM_REQUIRE(src && dst && aligned16(src) && aligned16(dst), "copy_rows: null or unaligned pointer");
+    VLLM_REQUIRE(src && dst && aligned16(src) && aligned16(dst), "copy_rows: null pointer, or src / dst not 16-byte aligned");
     VLLM_LAUNCH(copy_rows_kernel, dim3(grid_for(n * 64)), dim3(256), 0, (hipStream_t)stream, src, src_idx, dst, dst_idx, n, C,
                 src_rows, dst_rows);
     VLLM_CHECK_LAUNCH("copy_rows_kernel");

@@ -257,7 +257,7 @@ int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
     VLLM_REQUIRE(a.N % 4 == 0, "gemm: N=%d must be a multiple of 4", a.N);
     VLLM_REQUIRE(a.ldx % 8 == 0 && a.ldw % 8 == 0 && a.ldy % 4 == 0 && aligned16(a.X) && aligned16(a.W) &&
                      (reinterpret_cast<uintptr_t>(a.Y) & (epi == EPI_F32 || epi == EPI_MSDA ? 15u : 7u)) == 0,
-                 "gemm: operands must be 16-byte aligned with row strides multiple of 8 elements");
+                 "gemm: X and W must be 16-byte aligned, Y 8-byte aligned (16-byte for fp32 output), row strides multiples of 8 elements");
     VLLM_REQUIRE(epi != EPI_RESIDUAL || (a.res && a.ldr % 4 == 0), "gemm: residual epilogue needs res");
     VLLM_REQUIRE(epi != EPI_EMBED || (a.res && a.P > 0), "gemm: embed epilogue needs the position table and P");
     // tall, skinny K = 256 problems (the linears of a deformable-attention layer): weight-stationary streaming kernel, bit-identical
@@ -269,7 +269,7 @@ int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
                          a.nsplit % BN == 0 && a.nsplit > 0 && a.nsplit < a.N && (a.N - a.nsplit) % 16 == 0 && a.ldy2 % 4 == 0 &&
                          aligned16(a.W2) && aligned16(a.Y2) && aligned16(a.Y) && (a.ref_dim == 2 || a.ref_dim == 4) &&
                          (reinterpret_cast<uintptr_t>(a.ref) & (a.ref_dim == 4 ? 15u : 7u)) == 0,
-                     "gemm: bad operands for the MSDA sampling epilogue");
+                     "gemm: bad operands for the MSDA sampling epilogue (16-byte aligned W2 / Y2 / Y; reference points 8-byte aligned, 16-byte with ref_dim 4)");
     }
     if (epi == EPI_MSDA) a.variant = 1;
     if (a.variant == 4) { a.variant = 2; a.variant256 = 5; }   // 8-phase schedule on the 32x32x16 instruction

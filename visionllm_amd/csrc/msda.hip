@@ -565,7 +565,7 @@ extern "C" int vllm_msda_forward_bf16(const uint16_t *value, const int64_t *shap
     if ((long)B * Lq == 0) return VLLM_OK;
     VLLM_REQUIRE(value && shapes && lsi && loc && attw && out, "msda_forward_bf16: null pointer");
     VLLM_REQUIRE(vec_ok(D, 8, L, P, value, out) && (reinterpret_cast<uintptr_t>(loc) & 7u) == 0,
-                 "msda_forward_bf16: needs D in {8,16,...,512} (D/8 a power of two) and 16-byte aligned tensors (D=%d)", D);
+                 "msda_forward_bf16: needs D in {8,16,...,512} (D/8 a power of two), 16-byte aligned value / out and 8-byte aligned loc (D=%d)", D);
     hipStream_t st = (hipStream_t)stream;
     // encoder self-attention shape on a pyramid: the LDS-tiled kernel (value converted to fp32 while it is staged); it
     // returns at once for any other geometry and the gather kernel behind it then does the work

@@ -87,6 +87,9 @@ def dcnv3_backward(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, 
     if input.dtype == torch.float16:
         # half operands, fp32 arithmetic on widened copies in a workspace this call owns, every gradient rounded once (the native
         # entry point does the widening / zero fill / narrowing; dcnv3_cuda.cu:147 dispatches AND_HALF)
+        # the entry point needs 16-byte aligned tensors; a contiguous view at another storage offset (a batch slice of `mask` when
+        # Ho*Wo*G*kh*kw % 8 != 0) is accepted by the reference, so such an operand is copied (the gradients are fresh allocations)
+        input, offset, mask, grad_output = (_lib.aligned(t) for t in (input, offset, mask, grad_output))
         grad_input, grad_offset, grad_mask = torch.empty_like(input), torch.empty_like(offset), torch.empty_like(mask)
         nbytes = L.vllm_dcnv3_backward_f16_workspace(N, H, W, group, group_channels, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
                                                      dilation_h, dilation_w)

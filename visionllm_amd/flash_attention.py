@@ -25,7 +25,7 @@ class FlashAttention(nn.Module):
         # the reference accepts fp16 and bf16 (flash_attention.py:39-41: `assert qkv.dtype in [torch.float16, torch.bfloat16]`)
         if qkv.dtype not in (torch.bfloat16, torch.float16) or not qkv.is_cuda or qkv.dim() != 5 or qkv.shape[2] != 3:
             raise RuntimeError("native FlashAttention: qkv must be a bf16 / fp16 CUDA tensor [B, S, 3, H, D] (flash_attention.py:39-41)")
-        qkv = qkv.contiguous()
+        qkv = _lib.aligned(qkv)   # (the kernel needs 16-byte aligned q / k / v: a view at another storage offset is copied)
         B, S, _, H, D = qkv.shape
         out = torch.empty((B, S, H, D), dtype=qkv.dtype, device=qkv.device)
         scale = self.softmax_scale if self.softmax_scale is not None else D ** -0.5

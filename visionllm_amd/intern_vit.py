@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .vit_common import (EncoderPlan, _require_bf16_cuda, fold_norm_into_linear, kpad_for, model_output, norm_folding_applies,
+from .vit_common import (EncoderPlan, _require_bf16_cuda, fold_norm_into_linear, kpad_for, model_output, norm_folding_applies, plan_ptr,
                          padded_patch_weight, run_encoder)
 
 try:
@@ -68,10 +68,11 @@ class InternRMSNorm(nn.Module):
     def forward(self, hidden_states):
         x = hidden_states
         _require_bf16_cuda("hidden_states", x)
-        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        x2 = _lib.aligned(x.reshape(-1, x.shape[-1]))   # (16-byte aligned rows and weight: views at another offset are copied)
+        w = _lib.aligned(self.weight.detach())
         y = torch.empty_like(x2)
         with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().vllm_rmsnorm_bf16(_lib.ptr(x2), x2.shape[1], _lib.ptr(self.weight), _lib.ptr(y),
+            _lib.check(_lib.lib().vllm_rmsnorm_bf16(_lib.ptr(x2), x2.shape[1], _lib.ptr(w), _lib.ptr(y),
                                                     x2.shape[1], x2.shape[0], x2.shape[1], self.variance_epsilon,
                                                     _lib.current_stream(x.device)), "vllm_rmsnorm_bf16")
         return y.view_as(x)
@@ -186,7 +187,7 @@ class InternVisionModel(nn.Module):
         plan.keep = [pw]
         L = len(self.encoder.layers)
         layers = (_lib.VllmVitLayer * L)()
-        P = _lib.ptr
+        P = plan_ptr(plan)
         for i, lyr in enumerate(self.encoder.layers):
             a = lyr.attn
             fold = {}

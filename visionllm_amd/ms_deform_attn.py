@@ -61,6 +61,8 @@ def ms_deform_attn_forward(value, spatial_shapes, level_start_index, sampling_lo
     B, S, M, D, L, Lq, P = _check_inputs(value, spatial_shapes, level_start_index, sampling_loc, attn_weight,
                                          im2col_step)
     lib = _lib.lib()
+    if value.dtype == torch.bfloat16:   # (the bf16 entry point requires a 16-byte aligned value and 8-byte aligned locations)
+        value, sampling_loc = _lib.aligned(value, 16), _lib.aligned(sampling_loc, 8)
     out = torch.empty((B, Lq, M * D), dtype=value.dtype, device=value.device)
     with torch.cuda.device(value.device):
         st = _lib.current_stream(value.device)
@@ -373,13 +375,14 @@ def msda_layer_prepare(query, reference_points, input_flatten, spatial_shapes, l
     keep = []
     for name, lin in (("value_proj", value_proj), ("sampling_offsets", sampling_offsets),
                       ("attention_weights", attention_weights), ("output_proj", output_proj)):
-        w, b = lin.weight.detach().contiguous(), lin.bias.detach().to(torch.bfloat16).contiguous()
+        w, b = _lib.aligned(lin.weight.detach()), _lib.aligned(lin.bias.detach().to(torch.bfloat16))
         keep += [w, b]
         setattr(desc, name + "_w", w.data_ptr())
         setattr(desc, name + "_b", b.data_ptr())
-    q = query.contiguous()
-    x = input_flatten.contiguous()
-    ref = reference_points.to(torch.float32).contiguous()
+    q = _lib.aligned(query)           # (the GEMMs need 16-byte aligned rows: views at another storage offset are copied)
+    x = _lib.aligned(input_flatten)
+    # (the sampling epilogue reads a query's reference point as one 8-byte / 16-byte vector: a view that is not aligned so is copied)
+    ref = _lib.aligned(reference_points.to(torch.float32), 16 if reference_points.shape[-1] == 4 else 8)
     shapes = spatial_shapes.to(device=q.device, dtype=torch.int64).contiguous()
     lsi = level_start_index.to(device=q.device, dtype=torch.int64).contiguous()
     mask = None if padding_mask is None else padding_mask.to(torch.uint8).contiguous()

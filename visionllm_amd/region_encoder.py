@@ -42,7 +42,7 @@ def point_sample(input, point_coords, **kwargs):
     _check_ps(input, point_coords, kwargs)
     N, C, H, W = input.shape
     grid = point_coords.dim() == 4
-    pts = point_coords.reshape(N, -1, 2).to(torch.float32).contiguous()
+    pts = _lib.aligned(point_coords.reshape(N, -1, 2).to(torch.float32), 8)   # (coordinate pairs are read as 8-byte vectors)
     x = input.to(torch.float32).contiguous()
     P = pts.shape[1]
     out = torch.empty((N, C, P), dtype=torch.float32, device=x.device)
@@ -60,7 +60,7 @@ def point_sample_masked_mean(input, point_coords, valid):
     """Fused form of region_encoder.py:135-140: mean over the valid points of every region, (N, C)."""
     _check_ps(input, point_coords, {})
     N, C, H, W = input.shape
-    pts = point_coords.to(torch.float32).contiguous()
+    pts = _lib.aligned(point_coords.to(torch.float32), 8)   # (coordinate pairs are read as 8-byte vectors)
     P = pts.shape[1]
     x = input.to(torch.float32).contiguous()
     v = valid.to(torch.uint8).contiguous()

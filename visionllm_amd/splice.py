@@ -35,7 +35,7 @@ def splice_visual_tokens(inputs_embeds, input_ids, imp_token_id, image_features,
     feats = image_features.to(device=dev, dtype=torch.bfloat16)
     if feats.dim() != 3 or feats.shape[-1] != C:
         raise RuntimeError(f"splice_visual_tokens: image_features must be [n_tiles, T, {C}], got {tuple(feats.shape)}")
-    feats = feats.contiguous()
+    feats = _lib.aligned(feats)   # (the entry point needs 16-byte aligned rows: views at another storage offset are copied)
     n_tiles, T = int(feats.shape[0]), int(feats.shape[1])
     tps = None
     if split_sizes is not None:
@@ -44,10 +44,13 @@ def splice_visual_tokens(inputs_embeds, input_ids, imp_token_id, image_features,
         tps = (ctypes.c_int32 * B)(*[int(v) for v in split_sizes])   # host array: travels as a kernel argument
     L_ = _lib.lib()
     ws = torch.empty(int(L_.vllm_splice_workspace_ints(B, L, n_tiles)), dtype=torch.int32, device=dev)
+    embeds = _lib.aligned(inputs_embeds)   # written in place: a view at another storage offset is staged and copied back
     with torch.cuda.device(dev):
         _lib.check(L_.vllm_splice_visual_tokens_bf16(_lib.ptr(ids), int(imp_token_id), _lib.ptr(feats), tps, B, L, n_tiles, T, C,
-                                                     _lib.ptr(inputs_embeds), _lib.ptr(ws), None, _lib.current_stream(dev)),
+                                                     _lib.ptr(embeds), _lib.ptr(ws), None, _lib.current_stream(dev)),
                    "vllm_splice_visual_tokens_bf16")
+    if embeds is not inputs_embeds:
+        inputs_embeds.copy_(embeds)
     if check:
         _, n_vit, bad, n_sel = (int(v) for v in ws[:4].cpu())
         if bad:
@@ -78,10 +81,15 @@ def _copy_rows(src, src_idx, dst, dst_idx, n):
         return dst
     si = None if src_idx is None else src_idx.to(torch.int64).contiguous()
     di = None if dst_idx is None else dst_idx.to(torch.int64).contiguous()
+    # the entry point needs 16-byte aligned rows: a source view at another storage offset is copied, a destination one is staged
+    # and copied back
+    src, out = _lib.aligned(src), _lib.aligned(dst)
     with torch.cuda.device(dst.device):
-        _lib.check(_lib.lib().vllm_copy_rows_bf16(_lib.ptr(src), _lib.ptr(si), _lib.ptr(dst), _lib.ptr(di), int(n), C,
-                                                  src.numel() // C, dst.numel() // C, _lib.current_stream(dst.device)),
+        _lib.check(_lib.lib().vllm_copy_rows_bf16(_lib.ptr(src), _lib.ptr(si), _lib.ptr(out), _lib.ptr(di), int(n), C,
+                                                  src.numel() // C, out.numel() // C, _lib.current_stream(dst.device)),
                    "vllm_copy_rows_bf16")
+    if out is not dst:
+        dst.copy_(out)
     return dst
 
 

@@ -29,6 +29,20 @@ class EncoderPlan:
         return tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in params)
 
 
+def plan_ptr(plan):
+    """-> P(t): device pointer of parameter ``t`` for the descriptor.  The kernels read parameters as 16-byte vectors; a parameter
+    that is a view at another storage offset (weights loaded into one packed buffer) is copied once into an aligned tensor that
+    the plan keeps (the plan is rebuilt when a parameter's pointer or version changes)."""
+    def P(t):
+        if t is None:
+            return None
+        a = _lib.aligned(t.detach())
+        if a.data_ptr() != t.data_ptr():
+            plan.keep.append(a)
+        return _lib.ptr(a)
+    return P
+
+
 def padded_patch_weight(conv_weight, kpad):
     """Conv2d weight [C,3,ps,ps] -> [C, kpad] (k = c*ps*ps + ky*ps + kx, zero padded)."""
     C = conv_weight.shape[0]
