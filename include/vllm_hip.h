@@ -47,15 +47,10 @@ const char *vllm_last_error(void);
 /* Fills name[0..cap) with the device's gcnArchName; returns CU count or negative error. */
 int vllm_device_info(char *name, int cap);
 /* Tuning / test knobs (process-wide).  "msda_tiled": encoder-shaped (Lq == S) MSDA forward kernel, same results to fp32
- * rounding: 0 plain gather kernel; 1 automatic (default): generation 9 since the end of round 4 (msda_tiled9.hip: pyramid items, two
- * teams of waves half a period apart, software-pipelined gather; round 3: generation 8, round 2: generation 7)
- * when the level maps are nested halves -- decided on the device, no host sync -- else generation 4;
- * 2 generation 4 with 8 waves per block; 5 generation 4 with the phase clock (vllm_debug_counters);
- * 8 generation 4, 560-pixel windows, 2 blocks per CU; 9 generation 4, 360 pixels, 3 blocks per CU (the round-1 default);
- * 10-14 generation 6 (msda_tiled6.hip; 10 / 14 with phase clock, 11-13 gather / staging variants); 17 generation 6; 20 generation 9
- * (= automatic), 21 generation 9 with the phase clock.  Rejected (VLLM_EINVAL): 15 / 16 (generation 7, since round 4:
- * tools/experiments/msda_tiled7.hip) and 3 / 18 / 19 (generations 2 and 8, which left the library in round 5:
- * tools/experiments/msda_tiled2.hip, msda_tiled8.hip).  "gemm_variant": 0 auto, 1 128x128 kernel, 2 256x256 8-phase
+ * rounding: 0 plain gather kernel; 1 automatic (default): fp32 values on nested level maps generation 9 (msda_tiled9.hip; decided on
+ * the device, no host sync, or by the vllm_msda_forward_f32_geo hint), on any other maps generation 4 (msda_tiled4.hip), bf16 values
+ * on exact 2x pyramids generation 6 (msda_tiled6.hip); 21 as 1, with generation 9's phase clock (vllm_debug_counters).  Any other
+ * value is rejected (VLLM_EINVAL).  "gemm_variant": 0 auto, 1 128x128 kernel, 2 256x256 8-phase
  * kernel, 4 8-phase kernel on the 32x32x16 MFMA.  "gemm_direct_store": the 8-phase kernel's epilogue goes 0 through LDS
  * (row-contiguous 16-byte stores), 1 straight from the accumulator layout, 2 automatic (default; same results either way).
  * "attn_variant": 32 automatic (default) = 2 | 64 with the class-token split.  bit1 deferred rescale, bit4 do not trim padding keys /
@@ -92,9 +87,9 @@ int vllm_set_option(const char *name, int value);
  * whole process; VLLM_GEMM_TRACE (a raw device address the 8-phase GEMM writes per-block timestamps to) exists only in
  * builds with -DVLLM_GEMM_TRACE_ENABLE, where the address is validated as device memory first.
  * (VLLM_GEMM_PROF=1 in the environment: the 8-phase GEMM's prologue / main loop / epilogue ticks + block count;
- * "dcnv3_tiled" = 2: the DCNv3 kernel's phases; otherwise:) with "msda_tiled" = 5 / 10 / 14 / 16 the LDS-tiled MSDA kernel of that generation adds per-phase
- * shader-clock ticks to 16 device counters; this reads the current generation's into out[0..n) and clears them.  Returns the
- * number of counters written. */
+ * "dcnv3_tiled" = 2 / 4: the DCNv3 kernel's phases; otherwise:) with "msda_tiled" = 21 the MSDA forward's generation 9 adds
+ * per-phase shader-clock ticks to 16 device counters; this reads them into out[0..n) and clears them.  Returns the number of
+ * counters written. */
 int vllm_debug_counters(long *out, int n);
 /* In-step kernel timing (measurement; process-wide, off by default).  vllm_prof_enable(1) starts a recording: every
  * operator the library enqueues is preceded by a HIP event on its stream; vllm_prof_read waits for the last one and returns,

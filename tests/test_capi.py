@@ -290,19 +290,21 @@ def test_attention_lane_swaps_read_both_results(tmp_path):
 
 
 
-def test_retired_msda_tiled_values_are_rejected():
-    """msda_tiled 3 (generation 2) and 18 / 19 (generation 8) left the library: vllm_set_option refuses them, as it refuses 4, 6, 7,
-    15, 16 and out-of-range values, and leaves the option as it was."""
+def test_msda_tiled_accepts_only_0_1_21():
+    """msda_tiled accepts 0 (gather kernel), 1 (automatic) and 21 (generation 9's phase clock).  The values of the builds that left
+    the library -- generations 2 (3), 7 (15 / 16) and 8 (18 / 19), generation 4's other configurations and phase clock (2, 5, 8, 9),
+    generation 6 on fp32 values (10-14, 17) and the alias 20 -- are refused, as are 4, 6, 7 and out-of-range values, and the option
+    stays as it was."""
     L = _lib.lib()
-    old = _lib.set_option("msda_tiled", 9)
+    old = _lib.set_option("msda_tiled", 21)
     try:
-        for v in (-1, 3, 4, 6, 7, 15, 16, 18, 19, 22):
+        for v in (-1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 22):
             assert _lib.set_option("msda_tiled", v) == -1, v                 # VLLM_EINVAL
             assert "msda_tiled must be one of" in L.vllm_last_error().decode()
-            assert _lib.set_option("msda_tiled", 9) == 9, v                  # unchanged
-        for v in (0, 1, 2, 5, 8, 9, 10, 11, 12, 13, 14, 17, 20, 21):
+            assert _lib.set_option("msda_tiled", 21) == 21, v                # unchanged
+        for v in (0, 1, 21):
             _lib.set_option("msda_tiled", v)
-            assert _lib.set_option("msda_tiled", 9) == v
+            assert _lib.set_option("msda_tiled", 21) == v
     finally:
         _lib.set_option("msda_tiled", old)
 

@@ -25,6 +25,45 @@ def _run(g, dtype=torch.float32):
                                     _t(g["attw"], fd), 64)
 
 
+def _run_general(g):
+    """fp32 forward with the host's geometry hint forced to VLLM_GEO_GENERAL: at the encoder shape (Lq == S, D 32, P 4) the library
+    then runs generation 4 (msda_tiled4.hip) on any level maps, nested ones included."""
+    from visionllm_amd import _lib
+    v, ss, lsi, loc, w = _t(g["value"]), _t(g["shapes"]), _t(g["lsi"]), _t(g["loc"]), _t(g["attw"])
+    B, S, M, D = v.shape
+    Lq, L, P = loc.shape[1], loc.shape[3], loc.shape[4]
+    out = torch.empty((B, Lq, M * D), dtype=torch.float32, device=DEV)
+    _lib.check(_lib.lib().vllm_msda_forward_f32_geo(_lib.ptr(v), _lib.ptr(ss), _lib.ptr(lsi), _lib.ptr(loc), _lib.ptr(w), B, S, M, D, L,
+                                                    Lq, P, A.GEO_GENERAL, _lib.ptr(out), _lib.current_stream(v.device)))
+    return out
+
+
+def _check_bf16_route(g):
+    """vllm_msda_forward_bf16 (generation 6 on exact 2x pyramids, the gather kernel otherwise): two runs bit-identical, finite,
+    the oracle on the bf16-rounded value within the bound of test_generation6_bf16_value, and the bf16 gather route
+    (msda_tiled = 0) within one bf16 ulp (+ the 2e-6 floor of the fp32 kernel comparisons, for sums that cancel)."""
+    from visionllm_amd import _lib
+    vb = torch.from_numpy(g["value"]).to(torch.bfloat16)
+    ref = O.forward(vb.float().numpy(), g["shapes"], g["lsi"], g["loc"], g["attw"])
+    run = lambda: A.ms_deform_attn_forward(vb.to(DEV), _t(g["shapes"]), _t(g["lsi"]), _t(g["loc"]), _t(g["attw"]), 64)
+    old = _lib.set_option("msda_tiled", 1)
+    try:
+        auto, again = run(), run()
+        _lib.set_option("msda_tiled", 0)
+        gather = run()
+    finally:
+        _lib.set_option("msda_tiled", old)
+    assert auto.dtype == torch.bfloat16 and gather.dtype == torch.bfloat16
+    assert torch.equal(auto, again), "race: two runs of the bf16 operator differ"
+    assert torch.isfinite(auto).all()
+    a, b = auto.float().cpu().numpy(), gather.float().cpu().numpy()
+    err = np.abs(a - ref)
+    assert (err <= 2.0 ** -8 * np.abs(ref) + 1e-6).all(), err.max()   # one rounding to bf16 (half an ulp = 2^-9 relative)
+    m = np.maximum(np.abs(a), np.abs(b))
+    ulp = np.exp2(np.floor(np.log2(np.where(m > 0, m, 1.0))) - 7)    # bf16: 8 significant bits
+    assert (np.abs(a - b) <= ulp + 2e-6).all(), np.abs(a - b).max()
+
+
 GOLD = ["msda_kat_seed3.npz", "msda_stress_small.npz", "msda_stress_d32.npz", "msda_odd_channels.npz"]
 
 
@@ -124,31 +163,30 @@ def test_tiled_kernel_matches_gather_kernel(mode):
     if mode == "wide_offsets":      # far-away samples: windows exceed the LDS budget -> per-level global fallback
         rng = np.random.default_rng(0)
         g["loc"] = (g["loc"] + rng.standard_normal(g["loc"].shape).astype(np.float32) * 0.2).astype(np.float32)
+    ref = O.forward(g["value"], g["shapes"], g["lsi"], g["loc"], g["attw"])
     old = _lib.set_option("msda_tiled", 0)
     try:
         plain = _run(g)
-        ref = O.forward(g["value"], g["shapes"], g["lsi"], g["loc"], g["attw"])
-        for variant in (1, 17, 9):  # automatic (generation 9 on nested maps, else 4); 17: generation 6 (the bf16 operator's kernel, here on fp32 values); 9: generation 4 (any geometry).  Round 5: one kernel per geometry class -- generations 2 and 8 left the library (tools/experiments/)
-            _lib.set_option("msda_tiled", variant)
-            tiled = _run(g)
-            again = _run(g)
-            assert torch.equal(tiled, again), "race: two runs of the same kernel differ"
-            # same arithmetic per (query, point); only the compiler's contraction choices may differ between kernels
-            torch.testing.assert_close(tiled, plain, rtol=2e-6, atol=2e-6)
-            np.testing.assert_allclose(tiled.cpu().numpy(), ref, rtol=4e-6, atol=4e-6)
+        _lib.set_option("msda_tiled", 1)
+        # automatic (generation 9 on nested maps, else 4); generation 4 on any maps through the GEO_GENERAL hint
+        runs = {"automatic": (_run(g), _run(g)), "generation 4": (_run_general(g), _run_general(g))}
     finally:
         _lib.set_option("msda_tiled", old)
+    for variant, (tiled, again) in runs.items():
+        assert torch.equal(tiled, again), f"race: two runs of the same kernel differ ({variant})"
+        # same arithmetic per (query, point); only the compiler's contraction choices may differ between kernels
+        torch.testing.assert_close(tiled, plain, rtol=2e-6, atol=2e-6)
+        np.testing.assert_allclose(tiled.cpu().numpy(), ref, rtol=4e-6, atol=4e-6)
 
 
 
-MSDA_TILED_ACCEPTED = (0, 1, 2, 5, 8, 9, 10, 11, 12, 13, 14, 17, 20, 21)
+MSDA_TILED_ACCEPTED = (0, 1, 21)
 
 
-def test_every_accepted_msda_tiled_value_matches_the_oracle():
+def test_msda_tiled_0_1_21_match_the_oracle():
     """Every value vllm_set_option("msda_tiled") accepts, at the cfg-4 encoder shape (nested 2x pyramid, Lq == S, D = 32, P = 4,
-    L = 4: every generation applies): 0 gather; 1 / 20 generation 9 (21 + phase clock); 2 / 8 / 9 generation 4 (5 + phase clock);
-    10-14 / 17 generation 6 (10 / 14 + phase clock).  The phase-clock builds produce the profiles' numbers: their results must be the
-    oracle's too.  Each value: oracle tolerance of test_tiled_kernel_matches_gather_kernel, two runs bit-identical."""
+    L = 4): 0 gather; 1 generation 9; 21 generation 9 with its phase clock.  The phase-clock build produces the profiles' numbers: its
+    results must be the oracle's too.  Each value: oracle tolerance of test_tiled_kernel_matches_gather_kernel, two runs bit-identical."""
     from visionllm_amd import _lib
     g = make_inputs(2, 8, 32, CFG4_SHAPES, 4, mode="encoder_like", seed=1)
     ref = O.forward(g["value"], g["shapes"], g["lsi"], g["loc"], g["attw"])
@@ -178,10 +216,11 @@ PYRAMIDS = {
 @pytest.mark.parametrize("name", sorted(PYRAMIDS))
 @pytest.mark.parametrize("mode", ["encoder_like", "mixed", "uniform"])
 def test_generation6_pyramid_items(name, mode):
-    """Generation 6 (exact 2x pyramids: one item = an 8 x 16 region of level 0 with the queries of every level): partial
-    tiles, 1-4 levels, windows that fit the arena (encoder_like), a mix of staged and global-memory levels (far
-    offsets on a third of the points, rejected / non-finite points), and everything from global memory (uniform
-    locations).  Equal to the gather kernel and to the oracle; two runs are bit-identical (race screen)."""
+    """The pyramid-item kernels (one item = an 8 x 16 region of level 0 with the queries of every level): generation 9 (fp32, the
+    automatic choice) and generation 6 (the bf16-value operator, exact 2x pyramids): partial tiles, 1-4 levels, windows that fit
+    the arena (encoder_like), a mix of staged and global-memory levels (far offsets on a third of the points, rejected /
+    non-finite points), and everything from global memory (uniform locations).  Equal to the gather kernel and to the oracle;
+    two runs are bit-identical (race screen)."""
     from visionllm_amd import _lib
     shapes = PYRAMIDS[name]
     g = make_inputs(2, 8, 32, shapes, 4, mode="encoder_like", seed=len(shapes))
@@ -200,17 +239,15 @@ def test_generation6_pyramid_items(name, mode):
     old = _lib.set_option("msda_tiled", 0)
     try:
         plain = _run(g)
-        res = {}
-        for variant in (1, 17):   # automatic = generation 9; 17 = generation 6 (the bf16-value operator's kernel on fp32 values); generations 7 / 8 left the library (tools/experiments/)
-            _lib.set_option("msda_tiled", variant)
-            res[variant] = (_run(g), _run(g))
+        _lib.set_option("msda_tiled", 1)    # automatic = generation 9
+        t9, again = _run(g), _run(g)
     finally:
         _lib.set_option("msda_tiled", old)
-    for variant, (t6, again) in res.items():
-        assert torch.equal(t6, again), f"race: two runs of kernel variant {variant} differ"
-        assert torch.isfinite(t6).all()
-        torch.testing.assert_close(t6, plain, rtol=2e-6, atol=2e-6)
-        np.testing.assert_allclose(t6.cpu().numpy(), ref, rtol=4e-6, atol=4e-6)
+    assert torch.equal(t9, again), "race: two runs of generation 9 differ"
+    assert torch.isfinite(t9).all()
+    torch.testing.assert_close(t9, plain, rtol=2e-6, atol=2e-6)
+    np.testing.assert_allclose(t9.cpu().numpy(), ref, rtol=4e-6, atol=4e-6)
+    _check_bf16_route(g)
 
 
 def test_generation6_bf16_value():
@@ -271,13 +308,18 @@ def test_nan_and_inf_sampling_locations_contribute_nothing():
     flat[12::59] = -np.inf
     ref = O.forward(g["value"], g["shapes"], g["lsi"], loc, g["attw"])
     assert np.isfinite(ref).all()
-    for tiled in (0, 1, 17, 2, 8, 9):   # (3 = generation 2 left the library in round 5)
+    outs = []
+    for tiled in (0, 1):
         old = _lib.set_option("msda_tiled", tiled)
         try:
-            out = A.ms_deform_attn_forward(_t(g["value"]), _t(g["shapes"]), _t(g["lsi"]), _t(loc), _t(g["attw"]), 64)
+            outs.append(A.ms_deform_attn_forward(_t(g["value"]), _t(g["shapes"]), _t(g["lsi"]), _t(loc), _t(g["attw"]), 64))
+            if tiled == 1:
+                outs.append(_run_general(dict(g, loc=loc)))   # generation 4
         finally:
             _lib.set_option("msda_tiled", old)
+    for out in outs:
         np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=2e-5, atol=2e-5)
+    _check_bf16_route(dict(g, loc=loc))
 
 
 def test_edge_cases_and_errors():

@@ -19,7 +19,7 @@ import pytest
 import torch
 
 from msda_inputs import CFG4_SHAPES, make_inputs
-from test_msda_gpu import PYRAMIDS
+from test_msda_gpu import PYRAMIDS, _run_general
 from visionllm_amd import _lib
 from visionllm_amd import ms_deform_attn as A
 
@@ -30,7 +30,7 @@ N_LAUNCH = 100
 
 def _mixed(shapes, seed):
     """Locations that exposed the round-4 race: a third of the points far away (late + global-memory levels), rejected,
-    NaN and inf points in between (tools/gpu_passes/dbg_msda9_race.py)."""
+    NaN and inf points in between."""
     g = make_inputs(2, 8, 32, shapes, 4, mode="encoder_like", seed=seed)
     rng = np.random.default_rng(7)
     loc = g["loc"].copy()
@@ -60,8 +60,8 @@ def test_msda_automatic_forward_100_launches_identical(name):
         for i in range(N_LAUNCH):
             out = _fwd(_dev(g))                     # fresh tensors every launch: new addresses, cold caches (as the tests do)
             assert torch.equal(out, first), f"{name}: launch {i} differs from the first (max {float((out - first).abs().max()):.3g})"
-        _lib.set_option("msda_tiled", 9)            # generation 4 (any geometry): plain compiler-visible LDS reads, same arithmetic per point
-        torch.testing.assert_close(first, _fwd(_dev(g)), rtol=2e-6, atol=2e-6)
+        # generation 4 (any geometry, through the GEO_GENERAL hint): plain compiler-visible LDS reads, same arithmetic per point
+        torch.testing.assert_close(first, _run_general(g), rtol=2e-6, atol=2e-6)
         _lib.set_option("msda_tiled", 0)            # gather kernel
         torch.testing.assert_close(first, _fwd(_dev(g)), rtol=2e-6, atol=2e-6)
     finally:

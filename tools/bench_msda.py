@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""MSDA forward micro-benchmark at BASELINE cfg 4 (run on the GPU box)."""
+"""MSDA forward micro-benchmark at BASELINE cfg 4 (run on the GPU box).  Routes: fp32 automatic (generation 9 on nested maps, else 4),
+fp32 with the general-geometry hint (generation 4 on any maps), fp32 gather kernel, bf16 automatic (generation 6 on exact pyramids),
+bf16 gather kernel; + the backward."""
 import argparse
 import json
 import os
@@ -12,7 +14,34 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 from msda_inputs import CFG4_SHAPES, make_inputs  # noqa: E402
+from visionllm_amd import _lib  # noqa: E402
 from visionllm_amd import ms_deform_attn as A  # noqa: E402
+
+
+def set_tiled(value):
+    """vllm_set_option("msda_tiled", value) -> the previous value; stops on a refused value (carrying on would time the previous
+    mode under the new label)."""
+    old = _lib.set_option("msda_tiled", value)
+    if old < 0:
+        sys.exit(f"msda_tiled = {value} refused: {_lib.lib().vllm_last_error().decode()}")
+    return old
+
+
+def forward_general(t):
+    """fp32 forward with the VLLM_GEO_GENERAL hint: at the encoder shape, generation 4 on any level maps."""
+    v, loc = t["value"], t["loc"]
+    B, S, M, D = v.shape
+    Lq, L, P = loc.shape[1], loc.shape[3], loc.shape[4]
+    out = torch.empty((B, Lq, M * D), dtype=torch.float32, device=v.device)
+    _lib.check(_lib.lib().vllm_msda_forward_f32_geo(_lib.ptr(v), _lib.ptr(t["shapes"]), _lib.ptr(t["lsi"]), _lib.ptr(loc),
+                                                    _lib.ptr(t["attw"]), B, S, M, D, L, Lq, P, A.GEO_GENERAL, _lib.ptr(out),
+                                                    _lib.current_stream(v.device)), "vllm_msda_forward_f32_geo")
+    return out
+
+
+# route -> (value dtype, msda_tiled, general-geometry hint)
+ROUTES = {"f32_auto": ("f32", 1, False), "f32_general": ("f32", 1, True), "f32_gather": ("f32", 0, False),
+          "bf16_auto": ("bf16", 1, False), "bf16_gather": ("bf16", 0, False)}
 
 
 def algorithmic_bytes(B, S, M, D, L, Lq, P, vbytes=4):
@@ -56,13 +85,14 @@ def main():
                     t[k] = t[k] + 0.01 * torch.randn_like(t[k])
             B, S, M, D = t["value"].shape
             Lq, L, P = t["loc"].shape[1], t["loc"].shape[3], t["loc"].shape[4]
-            for dt in ("f32_auto", "f32_gen6", "f32_gen4", "f32_gen2", "f32_gather", "bf16_auto", "bf16_gather"):
-                v = t["value"] if not dt.startswith("bf16") else t["value"].bfloat16()
-                from visionllm_amd import _lib
-                # f32_auto: generation 7 on pyramids (msda_tiled7.hip), generation 4 otherwise; bf16_auto: generation 6 / gather kernel
-                _lib.set_option("msda_tiled", {"f32_gather": 0, "bf16_gather": 0, "f32_auto": 1, "f32_gen4_w8": 2, "f32_gen2": 3,
-                                               "f32_gen4_560": 8, "f32_gen4": 9, "f32_gen6": 17}.get(dt, 1))
-                sec = timeit(lambda: A.ms_deform_attn_forward(v, t["shapes"], t["lsi"], t["loc"], t["attw"], 64), a.iters)
+            for dt, (vt, tiled, general) in ROUTES.items():
+                tv = dict(t, value=t["value"] if vt == "f32" else t["value"].bfloat16())
+                set_tiled(tiled)
+                if general:
+                    fn = lambda: forward_general(tv)
+                else:
+                    fn = lambda: A.ms_deform_attn_forward(tv["value"], tv["shapes"], tv["lsi"], tv["loc"], tv["attw"], 64)
+                sec = timeit(fn, a.iters)
                 ab = algorithmic_bytes(B, S, M, D, L, Lq, P, 2 if dt.startswith("bf16") else 4)
                 gathered = B * Lq * M * L * P * 4 * D * (2 if dt.startswith("bf16") else 4)
                 r = dict(mode=mode, dtype=dt, B=B, Lq=Lq, us=sec * 1e6, algo_GBs=ab / sec / 1e9,
@@ -75,11 +105,10 @@ def main():
     for k in ("value", "loc", "attw"):
         t[k] = t[k].repeat(a.B, *([1] * (t[k].dim() - 1))).contiguous()
     go = torch.randn(a.B, t["loc"].shape[1], 256, device=dev)
-    from visionllm_amd import _lib
     for name, mode in (("f32_backward_tiled", 1), ("f32_backward_plain_atomics", 0)):
-        old = _lib.set_option("msda_tiled", mode)
+        old = set_tiled(mode)
         sec = timeit(lambda: A.ms_deform_attn_backward(t["value"], t["shapes"], t["lsi"], t["loc"], t["attw"], go, 64), 5)
-        _lib.set_option("msda_tiled", old)
+        set_tiled(old)
         print(json.dumps(dict(mode="encoder_like", dtype=name, B=a.B, Lq=int(t["loc"].shape[1]), us=sec * 1e6)))
     return res
 

@@ -31,7 +31,7 @@ namespace vllm {
 
 bool msda_tiled_ok(int D, int L, int P, int Lq, int S, int B, int M, const void *value, const void *out, const void *loc);
 int msda_tiled_enabled();   // runtime.cpp
-bool msda_tiled6_ok(int D, int L, int P, int Lq, int S, int B, int M);   // msda_tiled6.hip
+bool msda_pyramid_items_ok(int D, int L, int P, int Lq, int S, int B, int M);   // msda_tiled.hip
 int msda_tiled6_launch_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *loc,
                             const float *attw, int B, int S, int M, int L, int Lq, uint16_t *out, hipStream_t st);
 int msda_tiled_launch(const float *value, const int64_t *shapes, const int64_t *lsi, const float *loc,
@@ -569,7 +569,7 @@ extern "C" int vllm_msda_forward_bf16(const uint16_t *value, const int64_t *shap
     hipStream_t st = (hipStream_t)stream;
     // encoder self-attention shape on a pyramid: the LDS-tiled kernel (value converted to fp32 while it is staged); it
     // returns at once for any other geometry and the gather kernel behind it then does the work
-    const bool t6 = msda_tiled_enabled() == 1 && msda_tiled6_ok(D, L, P, Lq, S, B, M) && aligned16(loc) && aligned16(attw);
+    const bool t6 = msda_tiled_enabled() != 0 && msda_pyramid_items_ok(D, L, P, Lq, S, B, M) && aligned16(loc) && aligned16(attw);
     if (t6)
         if (int e = msda_tiled6_launch_bf16(value, shapes, lsi, loc, attw, B, S, M, L, Lq, out, st)) return e;
     return dispatch_vec<true>(D / 8, value, shapes, lsi, loc, attw, B, S, M, L, Lq, P, out, st, t6 ? 1 : 0);

@@ -52,7 +52,7 @@ __device__ __forceinline__ SamplePoint<T> sample_point(T loc_w, T loc_h, int H, 
 
 // Do the level maps form an exact 2x pyramid (H_l * 2^l == H_0, W_l * 2^l == W_0) whose cells are the Lq queries?
 // Evaluated ON THE DEVICE from the shape tensor (block-uniform scalar loads), so that the launcher can enqueue the
-// pyramid kernel (msda_tiled6.hip) and its general-geometry fallback back to back without a host synchronisation:
+// pyramid kernel (msda_tiled6.hip) and the gather kernel back to back without a host synchronisation:
 // exactly one of the two does the work.
 __device__ __forceinline__ bool geometry_is_pyramid(const int64_t *shapes, int L, long Lq)
 {

@@ -1,5 +1,5 @@
-// Multi-scale deformable attention forward, LDS-tiled kernel, generation 4 ("msda_tiled" options 1 (default: 4 waves per
-// block, 360-pixel windows, 3 blocks per CU), 8 (560-pixel windows, 2 blocks per CU), 2 (8 waves), 5 (phase clock)).
+// Multi-scale deformable attention forward, LDS-tiled kernel, generation 4: the fp32 encoder-shape kernel for level maps that are
+// not nested halves (4 waves per block, 360-pixel windows, 3 blocks per CU).
 //
 // Same tiling as msda_tiled.hip (one 8x16 query tile of one level x one head per work item, persistent blocks,
 // per-level exact bounding window staged into LDS with LDS-DMA), re-organised around the instruction count, which the
@@ -28,20 +28,16 @@ namespace vllm {
 
 namespace {
 
-constexpr int T4_TH = 8, T4_TW = 16, T4_NQ = T4_TH * T4_TW;
-// Block shape: NW waves share one window.  A pass covers NW * 8 queries (8 lanes x 16 B = D 32 fp32 per query), so a
+constexpr int T4_TH = 8, T4_TW = 16;     // query tile: 8 x 16 queries of one level map
+// Block shape: NW waves share one window.  A pass covers QPP = NW * 8 queries (8 lanes x 16 B = D 32 fp32 per query), so a
 // lane serves NPASS = 16 / NW queries per item ("steps") and evaluates the points of NOWN = NPASS / 2 of them itself.
-template <int NW, int TH = T4_TH>
-struct T4Shape {
-    static constexpr int THREADS = NW * 64, QPP = NW * 8, NPASS = TH * T4_TW / QPP, NOWN = NPASS / 2;
-    static_assert(NW == 4 || NW == 8, "4 or 8 waves");
-};
+constexpr int T4_NW = 4, T4_THREADS = T4_NW * 64, T4_QPP = T4_NW * 8, T4_NPASS = T4_TH * T4_TW / T4_QPP, T4_NOWN = T4_NPASS / 2;
+constexpr int T4_BPC = 3;                  // blocks per CU the launch is sized for
 constexpr int T4_ZPX = 48;                 // zero strip ahead of the window [pixels]; the pitch must stay <= ZPX - 2
-constexpr int T4_WIN = 560;                // window budget [pixels] of the 2-blocks-per-CU configuration
-constexpr int T4_WIN3 = 360;               // ... of the 3-blocks-per-CU configuration (see msda_tiled4_launch)
+constexpr int T4_WIN = 360;                // window budget [pixels] (see msda_tiled4_launch)
 constexpr int T4_SLACK = 8;                // the last LDS-DMA instruction of a window may write up to 7 pixels past it
 constexpr int T4_MAXL = 8;
-constexpr size_t t4_lds(int win) { return (size_t)(T4_ZPX + win + T4_SLACK) * 128; }
+constexpr size_t T4_LDS = (size_t)(T4_ZPX + T4_WIN + T4_SLACK) * 128;
 constexpr int T4_BIG = 0x3fffffff;
 struct T4Item { int b, m, q0, qW, qH, ty, tx; };   // one work item: batch, head, query tile of level-map (qH x qW) at q0
 
@@ -90,43 +86,26 @@ __device__ __forceinline__ int row16_min(int v)
     return v;
 }
 
-// Phase clock (diagnostics build of the same kernel, "msda_tiled" option 5): wave 0 of every block adds the shader-clock
-// ticks it spends in each phase (accumulated in LDS, added to g_t4_prof once at the end of the block);
-// vllm_debug_counters() reads and clears them.
-__device__ unsigned long long g_t4_prof[16];
-#define T4_TICK(slot)                                                            \
-    if (PROF) {                                                                  \
-        const unsigned now__ = (unsigned)__builtin_amdgcn_s_memtime();           \
-        pacc[slot] += now__ - tprev;                                             \
-        tprev = now__;                                                           \
-    }
-
-// __launch_bounds__(threads, waves per SIMD): two blocks per CU
-// WIN: window budget in pixels, BPC: blocks per CU the launch is sized for (LDS = (ZPX + WIN + SLACK) * 128 B per block)
-// TH: query tile rows (tile = TH x 16 queries)
-template <bool PROF, int NW, int WIN = T4_WIN, int BPC = 2, int TH = T4_TH>
-__global__ __launch_bounds__(NW * 64, NW * BPC / 4) void msda_fwd_tiled4_kernel(
+// __launch_bounds__(threads, waves per SIMD): BPC blocks per CU; LDS = (ZPX + WIN + SLACK) * 128 B per block
+__global__ __launch_bounds__(T4_THREADS, T4_NW * T4_BPC / 4) void msda_fwd_tiled4_kernel(
     const float *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
     const float *__restrict__ loc, const float *__restrict__ attw, int B, int S, int M, int L, int Lq,
-    float *__restrict__ out, int skip_pyramid)
+    float *__restrict__ out, int skip_nested)
 {
-    constexpr int D = 32, PT = 4;
-    // served by the kernel launched ahead of this one: 1 = an exact-pyramid kernel (generations 6 / 8), 2 = generation 7 (nested maps)
-    if (skip_pyramid == 1 && geometry_is_pyramid(shapes, L, Lq)) return;
-    if (skip_pyramid == 2 && geometry_is_nested(shapes, L, Lq)) return;
-    constexpr int T4_THREADS = T4Shape<NW, TH>::THREADS, T4_QPP = T4Shape<NW, TH>::QPP, T4_NPASS = T4Shape<NW, TH>::NPASS;
-    constexpr int NOWN = T4Shape<NW, TH>::NOWN;
+    constexpr int D = 32, PT = 4, TH = T4_TH, NOWN = T4_NOWN;
+    // skip_nested (0 / 1; an int: a bool argument costs the entry test a bit extraction): nested maps are served by generation 9,
+    // launched ahead of this one
+    if (skip_nested && geometry_is_nested(shapes, L, Lq)) return;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *win = reinterpret_cast<float *>(smem + T4_ZPX * 128);   // window pixel 0; the zero strip sits below it
     __shared__ int s_H[T4_MAXL], s_W[T4_MAXL], s_q0[T4_MAXL], s_tc[T4_MAXL + 1];
     __shared__ long s_v0[T4_MAXL];
-    __shared__ __attribute__((aligned(16))) int s_red[NW][4];   // per wave: min hl, min -hl, min wl, min -wl
+    __shared__ __attribute__((aligned(16))) int s_red[T4_NW][4];   // per wave: min hl, min -hl, min wl, min -wl
     __shared__ int s_geo_ok;
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int sub = tid & 7;                     // 16-byte channel chunk of this lane
-    unsigned pacc[16] = {};   // (dead in the production instantiation)
     // The two quads of a query's 8 lanes split the point arithmetic: quad hq owns steps 0,1 = passes 2*hq, 2*hq+1 and
     // receives the other two from its mirror lane (7 - i) with one DPP row_half_mirror per value.  A lane's step s is
     // pass (s + 2*hq) & 3; quad 0 lane k evaluates point k, quad 1 lane k point 3 - k, so that after the exchange every
@@ -159,7 +138,6 @@ __global__ __launch_bounds__(NW * 64, NW * BPC / 4) void msda_fwd_tiled4_kernel(
     const unsigned blocks_per_xcd = gridDim.x >> 3;
     const float *zsrc = g_t4_zero_px + sub * 4;
     const char *wbase = reinterpret_cast<const char *>(win) + sub * 16;
-    unsigned tprev = PROF ? (unsigned)__builtin_amdgcn_s_memtime() : 0u;
 
     // work item -> (batch, head, query tile); block-uniform, 32-bit arithmetic only
     auto decode = [&](unsigned item) -> T4Item {
@@ -221,7 +199,6 @@ __global__ __launch_bounds__(NW * 64, NW * BPC / 4) void msda_fwd_tiled4_kernel(
         bool nqok[NOWN];
 #pragma unroll
         for (int p = 0; p < NOWN; ++p) nq01[p] = pair_of(nxt, p, nqok[p]);
-        T4_TICK(12)   // next item's decode
         float2_t acc2[T4_NPASS][2];   // this lane's 4 channels of each step's query, as two 2-wide halves
 #pragma unroll
         for (int p = 0; p < T4_NPASS; ++p) acc2[p][0] = acc2[p][1] = (float2_t){0.f, 0.f};
@@ -236,7 +213,6 @@ __global__ __launch_bounds__(NW * 64, NW * BPC / 4) void msda_fwd_tiled4_kernel(
                 nshH = shapes[2 * ln]; nshW = shapes[2 * ln + 1]; nlsi = lsi[ln];
             }
 
-            T4_TICK(11)   // level constants from LDS
             // ---- A: this lane's point of its two own steps; weights (x attention weight); corner bounding box ----
             int hl[T4_NPASS], wl[T4_NPASS];
             float w1[T4_NPASS], w2[T4_NPASS], w3[T4_NPASS], w4[T4_NPASS];
@@ -256,12 +232,10 @@ __global__ __launch_bounds__(NW * 64, NW * BPC / 4) void msda_fwd_tiled4_kernel(
                 r0 = min(r0, ok ? sp.h_low : T4_BIG); r1 = min(r1, ok ? -sp.h_low : T4_BIG);
                 r2 = min(r2, ok ? sp.w_low : T4_BIG); r3 = min(r3, ok ? -sp.w_low : T4_BIG);
             }
-            T4_TICK(9)   // point arithmetic
             // wave minimum: DPP inside each row of 16, the four rows through SGPRs; lane 0 publishes the wave's box
             r0 = wave_min(row16_min(r0)); r1 = wave_min(row16_min(r1));
             r2 = wave_min(row16_min(r2)); r3 = wave_min(row16_min(r3));
             if (lane == 0) *reinterpret_cast<int4 *>(&s_red[wave_s][0]) = make_int4(r0, r1, r2, r3);
-            T4_TICK(10)   // box reduction
             // The next level's (behind the last level: the next item's first level's) locations / weights travel while
             // this level is staged and gathered.  ONE unconditional load site: with the loads in two branches the
             // compiler merged them through register copies and waited for the data right here, every level.
@@ -275,21 +249,18 @@ __global__ __launch_bounds__(NW * 64, NW * BPC / 4) void msda_fwd_tiled4_kernel(
                     la[p] = attw[(size_t)e];
                 }
             }
-            T4_TICK(1)   // prefetch issue
             __syncthreads();   // (B) box complete; every wave has finished gathering the previous window
-            T4_TICK(2)   // barrier B
             // (the next writes to s_red happen behind barrier (C), which every path below executes)
             // lane i reads wave (i mod NW)'s box; a row of 16 lanes then holds every wave's at least once
-            const int4 bw = *reinterpret_cast<const int4 *>(&s_red[lane & (NW - 1)][0]);
+            const int4 bw = *reinterpret_cast<const int4 *>(&s_red[lane & (T4_NW - 1)][0]);
             const int y0 = __builtin_amdgcn_readfirstlane(row16_min(bw.x)), ny1 = __builtin_amdgcn_readfirstlane(row16_min(bw.y));
             const int x0 = __builtin_amdgcn_readfirstlane(row16_min(bw.z)), nx1 = __builtin_amdgcn_readfirstlane(row16_min(bw.w));
             const int wh = (-ny1 + 1) - y0 + 1, ww = (-nx1 + 1) - x0 + 1;   // rows y0 .. max(hl)+1, columns x0 .. max(wl)+1
             const int npix = wh * ww;
-            if (__builtin_expect(y0 == T4_BIG || npix > WIN || ww > T4_ZPX - 2, 0)) {
+            if (__builtin_expect(y0 == T4_BIG || npix > T4_WIN || ww > T4_ZPX - 2, 0)) {
                 // Cold (block-uniform): no accepted point at this level, or a window beyond the LDS budget.  The latter
                 // gathers the level from global memory in a compact ROLLED loop (locations / weights re-read from
                 // global, they are L2-hot): unrolled, this path was 1300 instructions in the middle of the hot loop.
-                if (PROF) { pacc[y0 != T4_BIG ? 13 : 14] += 1; }
                 if (y0 != T4_BIG) {
                     okmask |= (unsigned)hm((int)okmask) << NOWN;
 #pragma unroll
@@ -325,7 +296,6 @@ __global__ __launch_bounds__(NW * 64, NW * BPC / 4) void msda_fwd_tiled4_kernel(
                     }
                 }
                 __syncthreads();
-                T4_TICK(15)   // cold path
                 continue;
             }
 #pragma unroll
@@ -333,7 +303,6 @@ __global__ __launch_bounds__(NW * 64, NW * BPC / 4) void msda_fwd_tiled4_kernel(
                 w1[NOWN + p] = hm(w1[p]); w2[NOWN + p] = hm(w2[p]); w3[NOWN + p] = hm(w3[p]); w4[NOWN + p] = hm(w4[p]);
             }
 
-            T4_TICK(3)   // box read, weight exchange
             // ---- B: stage the window (LDS-DMA, 8 pixels of 128 B per wave instruction); ring pixels come from the zero line
             {
                 const unsigned magic = (1u << 20) / (unsigned)ww + 1u;      // pix / ww for pix * ww < 2^20
@@ -370,7 +339,6 @@ __global__ __launch_bounds__(NW * 64, NW * BPC / 4) void msda_fwd_tiled4_kernel(
                     }
                 }
             }
-            T4_TICK(4)   // DMA issue loop
             // one LDS byte offset per point; a rejected point reads the zero strip
             const int pitchB = ww * 128;
             int o[T4_NPASS];
@@ -379,11 +347,8 @@ __global__ __launch_bounds__(NW * 64, NW * BPC / 4) void msda_fwd_tiled4_kernel(
                 o[p] = ((okmask >> p) & 1u) ? ((hl[p] - y0) * ww + (wl[p] - x0)) * 128 : -T4_ZPX * 128;
                 o[NOWN + p] = hm(o[p]);
             }
-            T4_TICK(5)   // offsets
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            T4_TICK(6)   // own DMA + prefetch complete
             __syncthreads();   // (C) window complete
-            T4_TICK(7)   // barrier C
 
             // ---- C: gather from LDS; the quad's lane K broadcasts point K's offset / weights (DPP) ----
             const char *wrow1 = wbase + pitchB;
@@ -408,7 +373,6 @@ __global__ __launch_bounds__(NW * 64, NW * BPC / 4) void msda_fwd_tiled4_kernel(
                 __builtin_amdgcn_sched_barrier(0);
             }
 #undef T4_POINT
-            T4_TICK(8)   // gather
         }
 #pragma unroll
         for (int p = 0; p < T4_NPASS; ++p) {
@@ -422,62 +386,30 @@ __global__ __launch_bounds__(NW * 64, NW * BPC / 4) void msda_fwd_tiled4_kernel(
         cur = nxt; have = have_next;
 #pragma unroll
         for (int p = 0; p < NOWN; ++p) { q01[p] = nq01[p]; qok[p] = nqok[p]; }
-        T4_TICK(0)   // item epilogue: stores
-    }
-    if (PROF && tid == 0) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) atomicAdd(&g_t4_prof[i], (unsigned long long)pacc[i]);
     }
 }
 
 }  // namespace
 
 int msda_tiled4_launch(const float *value, const int64_t *shapes, const int64_t *lsi, const float *loc,
-                       const float *attw, int B, int S, int M, int L, int Lq, float *out, int skip_pyramid,
+                       const float *attw, int B, int S, int M, int L, int Lq, float *out, bool skip_nested,
                        hipStream_t st)
 {
     const int cus = device_cus();
     static unsigned long long attr_mask = 0;
-    if (first_use_on_device(&attr_mask)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_fwd_tiled4_kernel<false, 4>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)t4_lds(T4_WIN));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_fwd_tiled4_kernel<false, 8>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)t4_lds(T4_WIN));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_fwd_tiled4_kernel<true, 4>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)t4_lds(T4_WIN));
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_fwd_tiled4_kernel<false, 4, T4_WIN3, 3>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)t4_lds(T4_WIN3));
-    }
-    const int mode = msda_tiled_enabled();
-#define T4_GO(PROF, NW, WIN, BPC)                                                                                     \
-    VLLM_LAUNCH((msda_fwd_tiled4_kernel<PROF, NW, WIN, BPC>), dim3((cus / 8) * 8 * BPC), dim3(NW * 64), t4_lds(WIN), st, value, \
-                shapes, lsi, loc, attw, B, S, M, L, Lq, out, skip_pyramid)
+    if (first_use_on_device(&attr_mask))
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_fwd_tiled4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)T4_LDS);
     // Window sizes at the cfg-4 encoder shape: median 108, mean 205, 90th percentile 308 pixels; 7.7 % of the (tile, level)
     // pairs exceed 360 against 6.9 % that exceed 560 (coarse query level -> fine value level either way).  A 360-pixel
     // budget is 52 KiB of LDS per block = THREE blocks per CU instead of two for 0.9 % more cold pairs: 582 vs 612 us.
     // (256-pixel windows and FOUR blocks per CU: 727 us -- 14 % cold pairs cost more than the fourth block hides.  Other
-    // tile shapes through the TH template parameter: 16x16 queries / 560 pixels / 2 blocks 651 us, 4x16 queries / 256
-    // pixels / 4 blocks 587 us against 594 us for the default on the same box -- inside the noise, not adopted.)
-    if (mode == 5) T4_GO(true, 4, T4_WIN, 2);          // phase clock (diagnostics)
-    else if (mode == 2) T4_GO(false, 8, T4_WIN, 2);    // 8 waves per block, 2 blocks per CU
-    else if (mode == 8) T4_GO(false, 4, T4_WIN, 2);    // 4 waves per block, 560-pixel windows, 2 blocks per CU (608 us)
-    else T4_GO(false, 4, T4_WIN3, 3);                  // 360-pixel windows, 3 blocks per CU (583 us, same box)
-#undef T4_GO
+    // tile shapes: 16x16 queries / 560 pixels / 2 blocks 651 us, 4x16 queries / 256 pixels / 4 blocks 587 us against 594 us
+    // for this configuration on the same box -- inside the noise, not adopted.)
+    VLLM_LAUNCH(msda_fwd_tiled4_kernel, dim3((cus / 8) * 8 * T4_BPC), dim3(T4_THREADS), T4_LDS, st, value, shapes, lsi, loc, attw, B, S,
+                M, L, Lq, out, skip_nested ? 1 : 0);
     VLLM_CHECK_LAUNCH("msda_fwd_tiled4_kernel");
     return VLLM_OK;
-}
-
-int msda_debug_counters(long *out, int n)
-{
-    unsigned long long h[16];
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_t4_prof), sizeof(h)) != hipSuccess) {
-        set_error("msda_debug_counters: device read failed");
-        return VLLM_ELAUNCH;
-    }
-    for (int i = 0; i < n && i < 16; ++i) out[i] = (long)h[i];
-    const unsigned long long z[16] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_t4_prof), z, sizeof(z));
-    return n < 16 ? n : 16;
 }
 
 }  // namespace vllm

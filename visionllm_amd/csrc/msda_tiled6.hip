@@ -1,5 +1,6 @@
-// Multi-scale deformable attention forward, LDS-tiled kernel, generation 6 ("msda_tiled" options 10-14 / 17; it serves the bf16-value
-// operator vllm_msda_forward_bf16; for fp32 values the automatic choice is generation 8 since round 3, msda_tiled8.hip).
+// Multi-scale deformable attention forward, LDS-tiled kernel, generation 6: the bf16-value operator vllm_msda_forward_bf16 (what the
+// fused layer hands over: bf16 value, bf16 output) on exact 2x pyramids.  The fp32 operator's pyramid kernel is generation 9
+// (msda_tiled9.hip), which grew out of this one.
 //
 // Generation 4 (msda_tiled4.hip) spends two thirds of its time in the per-(tile, level) skeleton: point arithmetic,
 // bounding-box reduction + exchange, two barriers, one DMA wait -- four times per item.  This kernel does that work ONCE
@@ -9,16 +10,15 @@
 //     in it (128 + 32 + 8 + 2 = 170 queries).  They sample the same neighbourhood of every value level, so one window per
 //     value level serves all of them: the 28 % of generation-4 items that tiled the coarse query levels -- the ones with
 //     the largest fine-level windows, mostly gathered from global memory by the cold path -- disappear, and the staged
-//     volume drops with them.  Other geometries fall back to one 8 x 16 query tile of one level per item ("flat").
+//     volume drops with them.  Other geometries are left to the gather kernel launched behind this one.
 //   * ALL LEVELS AT ONCE.  A lane owns ONE value level (lane & 3) of its queries: it loads that level's four sampling
 //     locations / weights with two 16-byte loads + one (a (query, head) pair's 128 + 64 bytes are read by the 4 lanes of
 //     a quad, fully coalesced), evaluates them, and the bounding boxes of all levels are reduced together: two DPP steps +
 //     four LDS integer atomics, ONE barrier.  The windows of all levels are then laid out back to back in one LDS arena and
-//     staged by one LDS-DMA phase (levels that do not fit together are split into groups; a level that does not fit at all,
-//     or has no accepted point, is gathered from global memory / skipped).  Per item: two barriers instead of eight.
+//     staged in one phase (levels that do not fit together are split into groups; a level that does not fit at all, or has
+//     no accepted point, is gathered from global memory / skipped).  Per item: two barriers instead of eight.
 //   * QUAD PER (query, head).  Four lanes x two 16-byte chunks cover the 32 channels; the level's owner lane K broadcasts
-//     offset and weights by DPP quad_perm fused INTO the consuming instruction (v_add_u32_dpp for the address, and
-//     v_fmac_f32_dpp for every multiply-add: no separate broadcast moves, no packed-math pairing).
+//     offset and weights by DPP quad_perm (v_add_u32_dpp for the address; DPP moves + v_pk_fma_f32 for the multiply-adds).
 //   * LDS BANKS.  A ds_read_b128 is served in 16-lane groups = 4 quads = 4 segments of 64 bytes.  Quads alternate which
 //     half of the 128-byte pixel row they read first, and the query <-> quad map pairs the two quads that read the same
 //     half with queries whose x differs in bits 0, 1 and 2, so for smooth offset fields their pixels fall into different
@@ -26,9 +26,10 @@
 // The integer part of a sampling point is msda_sample.hpp's sample_point() as everywhere else (index-exact contract); the
 // weighted sum is associated as in generation 4 (sum_c (w_c * a) * v_c, levels and points in reference order).
 //
+// The bf16 value is converted to fp32 while it is staged (through registers, four rounds of loads in flight), so the gather runs
+// on fp32 windows; the sums are rounded once to bf16.
+//
 // Reference semantics: ms_deform_im2col_cuda.cuh:236-321 (forward), :30-86 (bilinear with zero padding).
-// VT = float (operator ABI, B3) or bf16 (value written by the fused layer's value_proj epilogue; converted to fp32 while it
-// is staged, so the gather is the same); OT likewise.
 #include "common.hpp"
 #include <stdlib.h>
 #include "kernels.hpp"
@@ -39,13 +40,17 @@ namespace vllm {
 
 namespace {
 
-struct T6Item { int b, m, lq, ty, tx; };   // batch, head, (flat: query level), tile row / column
-
 // ---- window staging -------------------------------------------------------------------------------------------------
-// fp32 value: LDS-DMA, 8 lanes x 16 B = one 128-byte (pixel, head) row per lane group, NW * 8 pixels per round of the block.
-// Ring pixels (row -1 / H, column -1 / W) come from a 128-byte zero line in global memory.
-template <int NW>
-__device__ __forceinline__ void stage_window(const float *vl, char *dst, int y0, int x0, int wh, int ww, int H, int W,
+// 8 lanes per pixel (16 B of fp32 = 8 B of bf16 each), UN rounds of loads in flight before the first LDS write; ring pixels
+// (row -1 / H, column -1 / W) are written as zeros.
+__device__ __forceinline__ float4_t t6_ld_px(const uint16_t *p, bool inside)
+{
+    const uint2_t r = *reinterpret_cast<const uint2_t *>(p);
+    const float4_t t = {bf16lo_to_f32(r.x), bf16hi_to_f32(r.x), bf16lo_to_f32(r.y), bf16hi_to_f32(r.y)};
+    return inside ? t : (float4_t){0.f, 0.f, 0.f, 0.f};
+}
+template <int NW, int UN>
+__device__ __forceinline__ void stage_window(const uint16_t *vl, char *dst, int y0, int x0, int wh, int ww, int H, int W,
                                              unsigned MD, int wave_s, int lane)
 {
     constexpr int QPP = NW * 8;
@@ -57,60 +62,7 @@ __device__ __forceinline__ void stage_window(const float *vl, char *dst, int y0,
     const int wy = (int)(((unsigned)pix * magic) >> 20), wx = pix - wy * ww;
     int gy = y0 + wy, gx = x0 + wx;
     const int xend = x0 + ww;
-    const char *vlb = reinterpret_cast<const char *>(vl + sub * 4);
-    float *win = reinterpret_cast<float *>(dst);
-    if (y0 >= 0 && x0 >= 0 && y0 + wh + 6 / ww < H && xend <= W) {
-        // interior window: the source pointer advances by one of two constant steps; the tail lanes of the last
-        // instruction (up to 7 pixels = 6 / ww extra rows of a narrow window) still read inside the map
-        const unsigned stepA = (unsigned)(dq * W + dr) * MD * 4, stepB = stepA + (unsigned)(W - ww) * MD * 4;
-        const char *g = vlb + (size_t)((unsigned)(gy * W + gx) * MD) * 4;
-        for (int i0 = wave_s * 8; i0 < npix; i0 += QPP) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                             (__attribute__((address_space(3))) void *)(win + i0 * 32), 16, 0, 0);
-            gx += dr;
-            const bool wrap = gx >= xend;
-            gx -= wrap ? ww : 0;
-            g += wrap ? stepB : stepA;
-        }
-    } else {
-        const long zdelta = reinterpret_cast<const char *>(g_t6_zero_px + sub * 4) - vlb;
-        for (int i0 = wave_s * 8; i0 < npix; i0 += QPP) {
-            const bool inside = (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-            const long boff = inside ? (long)((size_t)((unsigned)(gy * W + gx) * MD) * 4) : zdelta;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(vlb + boff),
-                                             (__attribute__((address_space(3))) void *)(win + i0 * 32), 16, 0, 0);
-            gx += dr; gy += dq;
-            if (gx >= xend) { gx -= ww; ++gy; }
-        }
-    }
-}
-// Register-staged alternative (bf16 value always; fp32 value when STG == 1): 8 lanes per pixel, UN rounds of loads in flight
-// before the first LDS write; bf16 is converted to fp32 on the way (same LDS image).
-__device__ __forceinline__ float4_t t6_ld_px(const float *p, bool inside)
-{
-    const float4_t t = *reinterpret_cast<const float4_t *>(p);
-    return inside ? t : (float4_t){0.f, 0.f, 0.f, 0.f};
-}
-__device__ __forceinline__ float4_t t6_ld_px(const uint16_t *p, bool inside)
-{
-    const uint2_t r = *reinterpret_cast<const uint2_t *>(p);
-    const float4_t t = {bf16lo_to_f32(r.x), bf16hi_to_f32(r.x), bf16lo_to_f32(r.y), bf16hi_to_f32(r.y)};
-    return inside ? t : (float4_t){0.f, 0.f, 0.f, 0.f};
-}
-template <int NW, int UN, typename VT>
-__device__ __forceinline__ void stage_window_regs(const VT *vl, char *dst, int y0, int x0, int wh, int ww, int H, int W,
-                                                  unsigned MD, int wave_s, int lane)
-{
-    constexpr int QPP = NW * 8;
-    const int npix = wh * ww;
-    const int sub = lane & 7;
-    const unsigned magic = (1u << 20) / (unsigned)ww + 1u;
-    const int dq = (int)(((unsigned)QPP * magic) >> 20), dr = QPP - dq * ww;
-    const int pix = wave_s * 8 + (lane >> 3);
-    const int wy = (int)(((unsigned)pix * magic) >> 20), wx = pix - wy * ww;
-    int gy = y0 + wy, gx = x0 + wx;
-    const int xend = x0 + ww;
-    const VT *vlb = vl + sub * 4;
+    const uint16_t *vlb = vl + sub * 4;
     char *wdst = dst + (lane >> 3) * 128 + sub * 16;
     for (int i0 = wave_s * 8; i0 < npix; i0 += QPP * UN) {
         float4_t r[UN];
@@ -128,34 +80,21 @@ __device__ __forceinline__ void stage_window_regs(const VT *vl, char *dst, int y
                 *reinterpret_cast<float4_t *>(wdst + (size_t)(i0 + u * QPP) * 128) = r[u];
     }
 }
-template <int NW>
-__device__ __forceinline__ void stage_window(const uint16_t *vl, char *dst, int y0, int x0, int wh, int ww, int H, int W,
-                                             unsigned MD, int wave_s, int lane)
-{
-    stage_window_regs<NW, 4>(vl, dst, y0, x0, wh, ww, H, W, MD, wave_s, lane);
-}
 
 // ---- the kernel ---------------------------------------------------------------------------------------------------------
-// NW waves per block, NPASS passes of NW * 16 (query, head) pairs per item, WIN arena pixels, BPC blocks per CU.
+// NW waves per block, NPASS passes of NW * 16 (query, head) pairs per item (6 x 2 = 192 slots for the 170 queries of an item),
+// WIN arena pixels, BPC blocks per CU.
 // The kernel serves exact pyramids only (checked here, from the device-side shapes: no host sync); for any other geometry it
-// returns at once and the generation-4 kernel launched behind it does the work (msda_tiled6_launch).
-// Phase clock ("msda_tiled" option 10): wave 0 of every block adds the shader-clock ticks it spends in each phase.
-__device__ unsigned long long g_t6_prof[16];
-#define T6_TICK(slot)                                                            \
-    if (PROF) {                                                                  \
-        const unsigned now__ = (unsigned)__builtin_amdgcn_s_memtime();           \
-        pacc[slot] += now__ - tprev;                                             \
-        tprev = now__;                                                           \
-    }
+// returns at once and the gather kernel launched behind it does the work (vllm_msda_forward_bf16).
+constexpr int T6_NW = 6, T6_NPASS = 2, T6_WIN = 560, T6_BPC = 2;
+constexpr size_t T6_LDS = (size_t)(T6_ZPX + T6_WIN + T6_SLACK) * 128 + 128;
 
-// GV (gather arithmetic, for A/B): 0 v_fmac_f32_dpp (weights broadcast inside the multiply-add), 1 DPP moves + v_pk_fma_f32,
-// 2 DPP moves + v_fma_f32
-template <typename VT, typename OT, int NW, int NPASS, int WIN, int BPC, bool PROF = false, int GV = 0, int STG = 0>
-__global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_kernel(
-    const VT *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
+__global__ __launch_bounds__(T6_NW * 64, (T6_NW * T6_BPC + 3) / 4) void msda_fwd_tiled6_kernel(
+    const uint16_t *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
     const float *__restrict__ loc, const float *__restrict__ attw, int B, int S, int M, int L, int Lq,
-    OT *__restrict__ out)
+    uint16_t *__restrict__ out)
 {
+    constexpr int NW = T6_NW, NPASS = T6_NPASS, WIN = T6_WIN;
     constexpr int D = 32, PT = 4, THREADS = NW * 64, SPP = NW * 16;
     static_assert(NPASS * SPP >= 170, "an item has up to 170 queries");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -164,8 +103,6 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
 
     if (!geometry_is_pyramid(shapes, L, Lq)) return;
     const int tid = threadIdx.x, lane = tid & 63;
-    unsigned pacc[16] = {};   // (dead in the production instantiation)
-    unsigned tprev = PROF ? (unsigned)__builtin_amdgcn_s_memtime() : 0u;
     const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int k = lane & 3;                       // the value level this lane owns
     const unsigned MD = (unsigned)(M * D);
@@ -244,7 +181,6 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
     }
     int par = 0;
     while (have) {
-        T6_TICK(0)   // previous item's stores, loop control
         // ---- S1: this lane's 4 points per pass (level k): weights x attention weight, corner box ----
         float w1[NPASS][4], w2[NPASS][4], w3[NPASS][4], w4[NPASS][4];
         int o[NPASS][4];               // (h_low + 1) << 16 | (w_low + 1); replaced by the LDS byte offset when level k is hot (S5)
@@ -268,7 +204,6 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
                 r2 = min(r2, ok ? sp.w_low : T6_BIG); r3 = min(r3, ok ? -sp.w_low : T6_BIG);
             }
         }
-        T6_TICK(1)   // wait for the prefetched locations + point arithmetic
         // ---- S2: boxes of all levels: lanes of equal (lane & 3) inside a row of 16, then LDS integer minima ----
         r0 = dpp_min<0x128>(dpp_min<0x124>(r0)); r1 = dpp_min<0x128>(dpp_min<0x124>(r1));   // row_ror:4, row_ror:8
         r2 = dpp_min<0x128>(dpp_min<0x124>(r2)); r3 = dpp_min<0x128>(dpp_min<0x124>(r3));
@@ -279,9 +214,7 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
                          :: "v"(a), "v"(r0), "v"(r1), "v"(r2), "v"(r3) : "memory");
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        T6_TICK(2)   // box reduction
         __syncthreads();   // (B) boxes complete; every wave has finished gathering from the arena
-        T6_TICK(3)   // barrier B
         const int4 bx = *reinterpret_cast<const int4 *>(boxp + k * 4);   // lane l < 4: the box of level l
         if (tid < 16) s_box[(par ^ 1) * 16 + tid] = T6_BIG;   // (the other buffer was read for the last time before this barrier)
         par ^= 1;
@@ -328,7 +261,6 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
         for (int p = 0; p < NPASS; ++p)
 #pragma unroll
             for (int c = 0; c < 8; ++c) acc[p][c] = 0.f;
-        T6_TICK(4)   // arena layout, offsets
 
         // the next item
         j += blocks_per_xcd;
@@ -337,7 +269,7 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
         unsigned npr[NPASS];
         bool nqok[NPASS];
 
-        const VT *vb = value + ((size_t)cb * S * M + cm) * D;   // (b, pixel 0, head m)
+        const uint16_t *vb = value + ((size_t)cb * S * M + cm) * D;   // (b, pixel 0, head m)
         for (int g = 0; g < ngroups; ++g) {
             if (g > 0) __syncthreads();   // (D) the previous group has been gathered
             // ---- S4: stage the windows of this group ----
@@ -347,26 +279,18 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
                     const int y0 = __builtin_amdgcn_readlane(bx.x, l), ny1 = __builtin_amdgcn_readlane(bx.y, l);
                     const int x0 = __builtin_amdgcn_readlane(bx.z, l), nx1 = __builtin_amdgcn_readlane(bx.w, l);
                     const int v0l = __builtin_amdgcn_readlane(v0k, l);
-                    if constexpr (STG == 1)
-                        stage_window_regs<NW, 6>(vb + (size_t)v0l * MD, arena + (lay_l & 0xffff) * 128, y0, x0, (-ny1 + 1) - y0 + 1,
-                                                 (-nx1 + 1) - x0 + 1, H0 >> l, W0 >> l, MD, wave_s, lane);
-                    else
-                        stage_window<NW>(vb + (size_t)v0l * MD, arena + (lay_l & 0xffff) * 128, y0, x0, (-ny1 + 1) - y0 + 1,
-                                         (-nx1 + 1) - x0 + 1, H0 >> l, W0 >> l, MD, wave_s, lane);
+                    stage_window<NW, 4>(vb + (size_t)v0l * MD, arena + (lay_l & 0xffff) * 128, y0, x0, (-ny1 + 1) - y0 + 1,
+                                        (-nx1 + 1) - x0 + 1, H0 >> l, W0 >> l, MD, wave_s, lane);
                 }
             }
-            T6_TICK(5)   // DMA issue
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            T6_TICK(6)   // own DMA landed
             __syncthreads();   // (C) windows complete
-            T6_TICK(7)   // barrier C
             if (g == 0) {      // next item's locations / weights: in flight during the gather
                 if (have_next) decode(xcd * ipx + j, nb, nm, nty, ntx);
 #pragma unroll
                 for (int p = 0; p < NPASS; ++p) npr[p] = pair_of(nb, nm, nty, ntx, p, nqok[p]);
                 fetch(npr);
             }
-            T6_TICK(8)   // next item: decode + prefetch issue
             // ---- S6: gather.  Level LQ's owner is quad lane LQ: offset and weights arrive by DPP inside the consumer ----
 #define T6_HOT_POINT(P_, I_, LQ)                                                                                 \
     {                                                                                                            \
@@ -376,34 +300,16 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
         const float4_t a3 = *reinterpret_cast<const float4_t *>(s0 + pitch), a4 = *reinterpret_cast<const float4_t *>(s0 + pitch + 128); \
         const float4_t c1 = *reinterpret_cast<const float4_t *>(s1), c2 = *reinterpret_cast<const float4_t *>(s1 + 128); \
         const float4_t c3 = *reinterpret_cast<const float4_t *>(s1 + pitch), c4 = *reinterpret_cast<const float4_t *>(s1 + pitch + 128); \
-        if constexpr (GV == 0) {                                                                                 \
-            _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                      \
-                fmac_q<LQ>(acc[P_][c], w1[P_][I_], a1[c]); fmac_q<LQ>(acc[P_][c], w2[P_][I_], a2[c]);            \
-                fmac_q<LQ>(acc[P_][c], w3[P_][I_], a3[c]); fmac_q<LQ>(acc[P_][c], w4[P_][I_], a4[c]);            \
-            }                                                                                                    \
-            _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                      \
-                fmac_q<LQ>(acc[P_][4 + c], w1[P_][I_], c1[c]); fmac_q<LQ>(acc[P_][4 + c], w2[P_][I_], c2[c]);    \
-                fmac_q<LQ>(acc[P_][4 + c], w3[P_][I_], c3[c]); fmac_q<LQ>(acc[P_][4 + c], w4[P_][I_], c4[c]);    \
-            }                                                                                                    \
-        } else {                                                                                                 \
-            const float e1 = qbf<LQ>(w1[P_][I_]), e2 = qbf<LQ>(w2[P_][I_]), e3 = qbf<LQ>(w3[P_][I_]), e4 = qbf<LQ>(w4[P_][I_]); \
-            if constexpr (GV == 1) {                                                                             \
-                _Pragma("unroll") for (int c = 0; c < 4; c += 2) {                                               \
-                    float2_t t = {acc[P_][c], acc[P_][c + 1]};                                                   \
-                    t = t6_fma2(e1, (float2_t){a1[c], a1[c + 1]}, t); t = t6_fma2(e2, (float2_t){a2[c], a2[c + 1]}, t); \
-                    t = t6_fma2(e3, (float2_t){a3[c], a3[c + 1]}, t); t = t6_fma2(e4, (float2_t){a4[c], a4[c + 1]}, t); \
-                    acc[P_][c] = t.x; acc[P_][c + 1] = t.y;                                                      \
-                    float2_t u = {acc[P_][4 + c], acc[P_][5 + c]};                                               \
-                    u = t6_fma2(e1, (float2_t){c1[c], c1[c + 1]}, u); u = t6_fma2(e2, (float2_t){c2[c], c2[c + 1]}, u); \
-                    u = t6_fma2(e3, (float2_t){c3[c], c3[c + 1]}, u); u = t6_fma2(e4, (float2_t){c4[c], c4[c + 1]}, u); \
-                    acc[P_][4 + c] = u.x; acc[P_][5 + c] = u.y;                                                  \
-                }                                                                                                \
-            } else {                                                                                             \
-                _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                  \
-                    acc[P_][c] = fmaf(e4, a4[c], fmaf(e3, a3[c], fmaf(e2, a2[c], fmaf(e1, a1[c], acc[P_][c])))); \
-                    acc[P_][4 + c] = fmaf(e4, c4[c], fmaf(e3, c3[c], fmaf(e2, c2[c], fmaf(e1, c1[c], acc[P_][4 + c])))); \
-                }                                                                                                \
-            }                                                                                                    \
+        const float e1 = qbf<LQ>(w1[P_][I_]), e2 = qbf<LQ>(w2[P_][I_]), e3 = qbf<LQ>(w3[P_][I_]), e4 = qbf<LQ>(w4[P_][I_]); \
+        _Pragma("unroll") for (int c = 0; c < 4; c += 2) {                                                       \
+            float2_t t = {acc[P_][c], acc[P_][c + 1]};                                                           \
+            t = t6_fma2(e1, (float2_t){a1[c], a1[c + 1]}, t); t = t6_fma2(e2, (float2_t){a2[c], a2[c + 1]}, t);  \
+            t = t6_fma2(e3, (float2_t){a3[c], a3[c + 1]}, t); t = t6_fma2(e4, (float2_t){a4[c], a4[c + 1]}, t);  \
+            acc[P_][c] = t.x; acc[P_][c + 1] = t.y;                                                              \
+            float2_t u = {acc[P_][4 + c], acc[P_][5 + c]};                                                       \
+            u = t6_fma2(e1, (float2_t){c1[c], c1[c + 1]}, u); u = t6_fma2(e2, (float2_t){c2[c], c2[c + 1]}, u);  \
+            u = t6_fma2(e3, (float2_t){c3[c], c3[c + 1]}, u); u = t6_fma2(e4, (float2_t){c4[c], c4[c + 1]}, u);  \
+            acc[P_][4 + c] = u.x; acc[P_][5 + c] = u.y;                                                          \
         }                                                                                                        \
     }
 #define T6_LEVEL(LQ)                                                                                             \
@@ -415,7 +321,6 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
         }                                                                                                        \
     }
             T6_LEVEL(0) T6_LEVEL(1) T6_LEVEL(2) T6_LEVEL(3)
-            T6_TICK(9)   // gather
 #undef T6_LEVEL
 #undef T6_HOT_POINT
             // Cold levels of this group (window beyond the arena): the same lanes gather from global memory, one point at
@@ -425,7 +330,7 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
                 const int lay_l = __builtin_amdgcn_readlane(layk, l);
                 if ((lay_l >> 16) != (g | 0x200)) continue;   // this group and cold
                 const int Hc = H0 >> l, Wc = W0 >> l;
-                const VT *vc = vb + (size_t)__builtin_amdgcn_readlane(v0k, l) * MD;
+                const uint16_t *vc = vb + (size_t)__builtin_amdgcn_readlane(v0k, l) * MD;
                 const int src = ((lane & ~3) | l) << 2;
 #pragma unroll
                 for (int p = 0; p < NPASS; ++p) {
@@ -440,8 +345,8 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
                         const bool u0 = bh >= 0, u1 = bh + 1 <= Hc - 1, l0 = bw >= 0, l1 = bw + 1 <= Wc - 1;
                         const int h0 = min(max(bh, 0), Hc - 1), h1 = min(max(bh + 1, 0), Hc - 1);
                         const int c0 = min(max(bw, 0), Wc - 1), c1 = min(max(bw + 1, 0), Wc - 1);
-                        const VT *p1 = vc + (size_t)((unsigned)(h0 * Wc + c0) * MD), *p2 = vc + (size_t)((unsigned)(h0 * Wc + c1) * MD);
-                        const VT *p3 = vc + (size_t)((unsigned)(h1 * Wc + c0) * MD), *p4 = vc + (size_t)((unsigned)(h1 * Wc + c1) * MD);
+                        const uint16_t *p1 = vc + (size_t)((unsigned)(h0 * Wc + c0) * MD), *p2 = vc + (size_t)((unsigned)(h0 * Wc + c1) * MD);
+                        const uint16_t *p3 = vc + (size_t)((unsigned)(h1 * Wc + c0) * MD), *p4 = vc + (size_t)((unsigned)(h1 * Wc + c1) * MD);
                         const int eA = cA / 4, eB = (cA ^ 64) / 4;
                         const float4_t a1 = load4(p1 + eA), a2 = load4(p2 + eA), a3 = load4(p3 + eA), a4 = load4(p4 + eA);
                         const float4_t d1 = load4(p1 + eB), d2 = load4(p2 + eB), d3 = load4(p3 + eB), d4 = load4(p4 + eB);
@@ -456,17 +361,13 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-                if (PROF) pacc[12] += 1;
             }
-            T6_TICK(10)   // cold levels
-            if (PROF) pacc[13] += 1;   // groups
         }
-        if (PROF) pacc[14] += 1;       // items
         // ---- output: 2 x 16 bytes per lane ----
 #pragma unroll
         for (int p = 0; p < NPASS; ++p) {
             if (qok[p]) {
-                OT *op = out + (size_t)pr[p] * D;
+                uint16_t *op = out + (size_t)pr[p] * D;
                 store4(op + cA / 4, (float4_t){acc[p][0], acc[p][1], acc[p][2], acc[p][3]});
                 store4(op + (cA ^ 64) / 4, (float4_t){acc[p][4], acc[p][5], acc[p][6], acc[p][7]});
             }
@@ -475,73 +376,22 @@ __global__ __launch_bounds__(NW * 64, (NW * BPC + 3) / 4) void msda_fwd_tiled6_k
 #pragma unroll
         for (int p = 0; p < NPASS; ++p) { pr[p] = npr[p]; qok[p] = nqok[p]; }
     }
-    if (PROF && tid == 0) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) atomicAdd(&g_t6_prof[i], (unsigned long long)pacc[i]);
-    }
-}
-
-template <typename VT, typename OT, int NW, int NPASS, int WIN, int BPC, bool PROF = false, int GV = 0, int STG = 0>
-int t6_go(int cus, const VT *value, const int64_t *shapes, const int64_t *lsi, const float *loc, const float *attw, int B,
-          int S, int M, int L, int Lq, OT *out, hipStream_t st)
-{
-    constexpr size_t lds = (size_t)(T6_ZPX + WIN + T6_SLACK) * 128 + 128;
-    static unsigned long long attr_mask = 0;
-    if (first_use_on_device(&attr_mask)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_fwd_tiled6_kernel<VT, OT, NW, NPASS, WIN, BPC, PROF, GV, STG>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    VLLM_LAUNCH((msda_fwd_tiled6_kernel<VT, OT, NW, NPASS, WIN, BPC, PROF, GV, STG>), dim3((cus / 8) * 8 * BPC), dim3(NW * 64), lds, st,
-                value, shapes, lsi, loc, attw, B, S, M, L, Lq, out);
-    VLLM_CHECK_LAUNCH("msda_fwd_tiled6_kernel");
-    return VLLM_OK;
-}
-
-int t6_cus()
-{
-    const int cus = device_cus();
-    return cus;
 }
 
 }  // namespace
 
-// D == 32, P == 4, L <= 4, Lq == S, 32-bit pair / pixel offsets, 16-byte aligned tensors (checked by the caller)
-bool msda_tiled6_ok(int D, int L, int P, int Lq, int S, int B, int M)
-{
-    return D == 32 && P == 4 && L >= 1 && L <= 4 && Lq == S && Lq >= 4096 && (long)S * M * 32 < (1L << 29) &&
-           (long)B * Lq * M * L * P * 2 < (1L << 30);
-}
-
-int msda_tiled6_launch(const float *value, const int64_t *shapes, const int64_t *lsi, const float *loc, const float *attw,
-                       int B, int S, int M, int L, int Lq, float *out, hipStream_t st)
-{
-    // 6 waves x 2 passes = 192 (query, head) slots for the 170 queries of an item; 560-pixel arena, 2 blocks per CU
-    const int mode = msda_tiled_enabled();
-    if (mode == 10) return t6_go<float, float, 6, 2, 560, 2, true>(t6_cus(), value, shapes, lsi, loc, attw, B, S, M, L, Lq, out, st);
-    if (mode == 11) return t6_go<float, float, 6, 2, 560, 2, false, 1>(t6_cus(), value, shapes, lsi, loc, attw, B, S, M, L, Lq, out, st);
-    if (mode == 12) return t6_go<float, float, 6, 2, 560, 2, false, 2>(t6_cus(), value, shapes, lsi, loc, attw, B, S, M, L, Lq, out, st);
-    if (mode == 13) return t6_go<float, float, 6, 2, 560, 2, false, 1, 1>(t6_cus(), value, shapes, lsi, loc, attw, B, S, M, L, Lq, out, st);
-    if (mode == 14) return t6_go<float, float, 6, 2, 560, 2, true, 1, 1>(t6_cus(), value, shapes, lsi, loc, attw, B, S, M, L, Lq, out, st);
-    return t6_go<float, float, 6, 2, 560, 2, false, 1>(t6_cus(), value, shapes, lsi, loc, attw, B, S, M, L, Lq, out, st);
-}
-
 int msda_tiled6_launch_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *loc,
                             const float *attw, int B, int S, int M, int L, int Lq, uint16_t *out, hipStream_t st)
 {
-    return t6_go<uint16_t, uint16_t, 6, 2, 560, 2, false, 1>(t6_cus(), value, shapes, lsi, loc, attw, B, S, M, L, Lq, out, st);
-}
-
-int msda6_debug_counters(long *out, int n)
-{
-    unsigned long long h[16];
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpyFromSymbol(h, HIP_SYMBOL(g_t6_prof), sizeof(h)) != hipSuccess) {
-        set_error("msda6_debug_counters: device read failed");
-        return VLLM_ELAUNCH;
-    }
-    for (int i = 0; i < n && i < 16; ++i) out[i] = (long)h[i];
-    const unsigned long long z[16] = {};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_t6_prof), z, sizeof(z));
-    return n < 16 ? n : 16;
+    const int cus = device_cus();
+    static unsigned long long attr_mask = 0;
+    if (first_use_on_device(&attr_mask))
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&msda_fwd_tiled6_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)T6_LDS);
+    VLLM_LAUNCH(msda_fwd_tiled6_kernel, dim3((cus / 8) * 8 * T6_BPC), dim3(T6_NW * 64), T6_LDS, st, value, shapes, lsi, loc, attw, B, S, M, L,
+                Lq, out);
+    VLLM_CHECK_LAUNCH("msda_fwd_tiled6_kernel");
+    return VLLM_OK;
 }
 
 }  // namespace vllm

@@ -1,4 +1,4 @@
-// Helpers shared by the pyramid-item MSDA forward kernels (msda_tiled6.hip, msda_tiled7.hip).
+// Helpers shared by the pyramid-item MSDA forward kernels (msda_tiled6.hip, msda_tiled9.hip).
 #pragma once
 #include "common.hpp"
 
@@ -9,8 +9,6 @@ constexpr int T6_ZPX = 48;               // zero strip at the bottom of LDS [pix
 constexpr int T6_BIG = 0x3fffffff;
 constexpr int T6_SLACK = 8;              // windows are padded to 8 pixels (the last DMA instruction writes whole groups)
 
-__device__ __attribute__((aligned(128))) float g_t6_zero_px[32];   // zero-initialised: DMA source of out-of-image pixels
-
 template <int K>
 __device__ __forceinline__ int qbi(int x)   // value of lane K of this lane's quad
 {
@@ -20,16 +18,6 @@ template <int K>
 __device__ __forceinline__ float qbf(float x)
 {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), K * 0x55, 0xf, 0xf, true));
-}
-// acc += (w of quad lane K) * v in ONE VALU instruction
-template <int K>
-__device__ __forceinline__ void fmac_q(float &acc, float w, float v)
-{
-    static_assert(K >= 0 && K < 4, "quad lane");
-    if constexpr (K == 0) asm("v_fmac_f32_dpp %0, %1, %2 quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(w), "v"(v));
-    if constexpr (K == 1) asm("v_fmac_f32_dpp %0, %1, %2 quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(w), "v"(v));
-    if constexpr (K == 2) asm("v_fmac_f32_dpp %0, %1, %2 quad_perm:[2,2,2,2] row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(w), "v"(v));
-    if constexpr (K == 3) asm("v_fmac_f32_dpp %0, %1, %2 quad_perm:[3,3,3,3] row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(w), "v"(v));
 }
 __device__ __forceinline__ float2_t t6_fma2(float w, float2_t v, float2_t a)
 {

@@ -1,4 +1,4 @@
-// Multi-scale deformable attention forward, LDS-tiled kernel, generation 9 ("msda_tiled" option 20; the automatic choice since the end
+// Multi-scale deformable attention forward, LDS-tiled kernel, generation 9 (the automatic choice on nested maps since the end
 // of round 4): generation 8's pyramid items and two teams half a period apart with a software-pipelined gather and straight-line
 // halves.  LIBRARY BUILD: twelve waves (teams of six, T9_TW = 6 -- generation 8's occupancy), the gathering wave at s_setprio 1, and the
 // preparing team gathering level 0 of pass 0 of its own item at the end of its half (T9_EARLY = 1): 439.6 us against generation 8's

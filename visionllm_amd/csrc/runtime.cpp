@@ -69,12 +69,13 @@ int gemm_variant_override()
     }
     return g_gemm_variant;
 }
+// "msda_tiled": 0 gather kernel, 1 automatic (default), 21 automatic with generation 9's phase clock
+static bool msda_tiled_valid(int v) { return v == 0 || v == 1 || v == 21; }
 int msda_tiled_enabled()
 {
     if (g_msda_tiled < 0) {
         const char *e = getenv("VLLM_MSDA_TILED");
-        g_msda_tiled = e ? atoi(e) : 1;
-        if (g_msda_tiled < 0 || g_msda_tiled > 21 || g_msda_tiled == 4 || g_msda_tiled == 6 || g_msda_tiled == 7 || g_msda_tiled == 15 || g_msda_tiled == 16) g_msda_tiled = 1;
+        g_msda_tiled = e && msda_tiled_valid(atoi(e)) ? atoi(e) : 1;
     }
     return g_msda_tiled;
 }
@@ -85,10 +86,8 @@ extern "C" int vllm_set_option(const char *name, int value)
     if (!name) return VLLM_EINVAL;
     if (!strcmp(name, "msda_tiled")) {
         const int old = vllm::msda_tiled_enabled();
-        // 3 (generation 2) and 18 / 19 (generation 8) left the library in round 5: rejected here, as 15 / 16 are
-        if (value < 0 || value > 21 || value == 3 || value == 4 || value == 6 || value == 7 || value == 15 || value == 16 || value == 18 ||
-            value == 19) {
-            vllm::set_error("msda_tiled must be one of 0, 1, 2, 5, 8, 9, 10..14, 17, 20, 21");
+        if (!vllm::msda_tiled_valid(value)) {
+            vllm::set_error("msda_tiled must be one of 0, 1, 21 (got %d)", value);
             return VLLM_EINVAL;
         }
         vllm::g_msda_tiled = value;
@@ -112,15 +111,14 @@ extern "C" int vllm_set_option(const char *name, int value)
     vllm::set_error("unknown option %s", name);
     return VLLM_EINVAL;
 }
-namespace vllm { int dcnv3_pipe_debug_counters(long *out, int n); int gemm256_debug_counters(long *out, int n); int dcnv3_debug_counters(long *out, int n); int msda_debug_counters(long *out, int n); int msda6_debug_counters(long *out, int n); int msda9_debug_counters(long *out, int n); }
+namespace vllm { int dcnv3_pipe_debug_counters(long *out, int n); int gemm256_debug_counters(long *out, int n); int dcnv3_debug_counters(long *out, int n); int msda9_debug_counters(long *out, int n); }
 extern "C" int vllm_debug_counters(long *out, int n)
 {
     if (!out || n <= 0) { vllm::set_error("vllm_debug_counters: bad arguments"); return VLLM_EINVAL; }
     { static const int gp = [] { const char *e = getenv("VLLM_GEMM_PROF"); return e ? atoi(e) : 0; }(); if (gp) return vllm::gemm256_debug_counters(out, n); }
     if (vllm::dcnv3_tiled_enabled() == 2) return vllm::dcnv3_pipe_debug_counters(out, n);
     if (vllm::dcnv3_tiled_enabled() == 4) return vllm::dcnv3_debug_counters(out, n);
-    const int mode = vllm::msda_tiled_enabled();
-    return mode >= 20 ? vllm::msda9_debug_counters(out, n) : mode >= 10 ? vllm::msda6_debug_counters(out, n) : vllm::msda_debug_counters(out, n);
+    return vllm::msda9_debug_counters(out, n);
 }
 // ---- in-step kernel timing ----------------------------------------------------------------------------------------
 #include <vector>
