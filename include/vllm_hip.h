@@ -289,6 +289,8 @@ int vllm_point_sample_mean_f32(const float *input, const float *coords, const ui
 #define VLLM_EPI_F32 5         /* y = x W^T + b kept in fp32: Y is float*, ldy in floats (16-byte aligned rows); `res`, if
                                 * given, is a uint8 row mask [M]: masked rows are written as zeros (the key-padding
                                 * zero-fill of the MSDA value projection) */
+#define VLLM_EPI_GELU_BWD 6    /* y = (x W^T) * gelu_erf'(res[m, n]); `res` = the saved pre-activation [M, N] (row stride ldr, 8-byte
+                                * aligned), bias must be NULL (projector backward: dY_{i-1} = (dY_i W_i) * gelu'(H_{i-1}), W = W_i^T) */
 /* Kernel choice is automatic (256x256 8-phase schedule for M,N >= 1024, 128x128 otherwise); OR one of these into
  * `epilogue` to force a schedule (parity tests / tuning only). */
 #define VLLM_GEMM_FORCE_128 0x100
@@ -345,6 +347,17 @@ int vllm_gemm_bf16_ln(const uint16_t *X, const uint16_t *W, const uint16_t *bias
                       float *ln_out, const float *ln_in, int ln_slots, int ln_rms, float ln_eps,
                       const float *ln_colsum, const float *ln_bias, vllm_stream_t stream);
 
+/* Weight gradient of a Linear (projector backward): dW[n, k] = sum_m dY[m, n] A[m, k] and, if db != NULL, db[n] = sum_m dY[m, n];
+ * dY [M, N] (row stride ldy), A [M, K] (row stride lda) -- the Linear's output gradient and input --, dW [N, K] (row stride ldw), all
+ * bf16; fp32 accumulation, one rounding.  Any M (ragged rows are zero-padded); N, K multiples of 64.  When the output tiles do not fill
+ * the device the rows are split and fp32 partials meet in `workspace` (vllm_gemm_wgrad_workspace_bytes(M, N, K) bytes, 0 = not needed),
+ * summed in a fixed order: results are run-to-run identical. */
+/* Alignment: dY and A 16 bytes (ldy, lda multiples of 8), dW 8 bytes (ldw a multiple of 4), workspace 16 bytes. */
+long vllm_gemm_wgrad_workspace_bytes(int M, int N, int K);
+long vllm_gemm_wgrad_split_launches(void);   /* launches of this process that took the split route (tests / tuning) */
+int vllm_gemm_wgrad_bf16(const uint16_t *dY, int ldy, const uint16_t *A, int lda, int M, int N, int K, uint16_t *dW, int ldw,
+                         uint16_t *db, void *workspace, long workspace_bytes, vllm_stream_t stream);
+
 /* B5: InternRMSNorm / apex FusedRMSNorm (modeling_intern_vit.py:33-58): y = w * bf16(x * rsqrt(mean(x^2)+eps)).
  * Row strides allow the in-place QK-RMSNorm over the q / k column blocks of the qkv buffer (:131-134). */
 /* Alignment (both norms): x, y, weight and bias 16 bytes. */
@@ -353,6 +366,15 @@ int vllm_rmsnorm_bf16(const uint16_t *x, int ldx, const uint16_t *weight, uint16
 /* nn.LayerNorm (CLIP pre_layrnorm / layer_norm1,2; vl_bridge LayerNorm, modeling_visionllmv2.py:166-167). */
 int vllm_layernorm_bf16(const uint16_t *x, int ldx, const uint16_t *weight, const uint16_t *bias,
                         uint16_t *y, int ldy, long rows, int C, float eps, vllm_stream_t stream);
+/* Its backward (the InternVL projector's LayerNorm): x [rows, C] bf16, grad_y [rows, C] fp32 (row stride ldg), weight (gamma) [C].
+ * grad_x [rows, C] bf16 (row stride ldgx; NULL = not needed) = r (g - mean(g) - xhat mean(g xhat)), g = grad_y * gamma, with the row
+ * statistics recomputed in fp32; grad_w = sum_m grad_y xhat, grad_b = sum_m grad_y (bf16 [C]; either may be NULL) through per-block fp32
+ * partials in `workspace` (vllm_layernorm_backward_workspace_bytes) and a fixed-order reduce.  C % 64 == 0, C <= 16384. */
+/* Alignment: x, weight, grad_x 8 bytes (ldx, ldgx multiples of 4), grad_y and workspace 16 bytes (ldg a multiple of 4). */
+long vllm_layernorm_backward_workspace_bytes(long rows, int C);
+int vllm_layernorm_backward_bf16(const uint16_t *x, int ldx, const float *grad_y, int ldg, const uint16_t *weight, float eps, long rows,
+                                 int C, uint16_t *grad_x, int ldgx, uint16_t *grad_w, uint16_t *grad_b, void *workspace,
+                                 long workspace_bytes, vllm_stream_t stream);
 
 /* B4: FlashAttention.forward(qkv[B,S,3,H,D]) -> out[B,S,H,D], non-causal, no mask, dropout 0
  * (visionllmv2/model/internvit/flash_attention.py:30-75).  D in {64,128}. */
@@ -499,6 +521,26 @@ long vllm_bridge_workspace_bytes(const VllmBridgeDesc *desc, int n_tiles, int to
 /* Alignment: hidden, out, the LayerNorm and Linear parameters and the workspace 16 bytes. */
 int vllm_bridge_forward(const VllmBridgeDesc *desc, const uint16_t *hidden, int n_tiles, int T, int C,
                         uint16_t *out, void *workspace, long workspace_bytes, vllm_stream_t stream);
+
+/* Training the projector (the reference trains it: freeze_vl_bridge=False, visionllmv2/train/train.py:162-170; modeling_visionllmv2.py:579
+ * calls it with grad on a frozen input).  Both calls take the projector's input as forward(x) receives it: the descriptor must have
+ * pixel_shuffle = skip_cls = 0 (VLLM_EINVAL and a message otherwise).  x [rows, in_features], out [rows, out_features] bf16.
+ * Training forward: the GEMMs of vllm_bridge_forward (same schedules, same bits: out is identical to what vllm_bridge_forward writes for
+ * the same rows) and it keeps what the backward needs: for Linear i < depth - 1 its output before the GELU H_i (saved_pre[i]) and after
+ * it A_i (saved_act[i]), [rows, out_features] each; internvl_mlp: the LayerNorm output (saved_ln [rows, in_features]; NULL otherwise).
+ * Backward: grad_out [rows, out_features]; writes grad_w[i] (the Linear weights' shapes) for every Linear, grad_b[i] where it is not
+ * NULL, grad_ln_w / grad_ln_b (internvl_mlp; either may be NULL), grad_x [rows, in_features] when not NULL.  All gradients bf16 (fp32
+ * accumulation inside, fp32 LayerNorm input gradient), overwritten (the caller accumulates).  Run-to-run identical.
+ * workspace: vllm_bridge_backward_workspace_bytes(desc, rows, need_grad_x) bytes for the backward; the same size (with need_grad_x 0)
+ * also serves the training forward.  Nothing is allocated, nothing synchronised; one stream. */
+/* Alignment: x, out, grad_out, grad_x, every saved tensor and gradient, the descriptor's parameters and the workspace 16 bytes. */
+long vllm_bridge_backward_workspace_bytes(const VllmBridgeDesc *desc, long rows, int need_grad_x);
+int vllm_bridge_forward_train(const VllmBridgeDesc *desc, const uint16_t *x, long rows, uint16_t *out, uint16_t *const *saved_pre,
+                              uint16_t *const *saved_act, uint16_t *saved_ln, void *workspace, long workspace_bytes, vllm_stream_t stream);
+int vllm_bridge_backward(const VllmBridgeDesc *desc, const uint16_t *x, long rows, const uint16_t *grad_out,
+                         const uint16_t *const *saved_pre, const uint16_t *const *saved_act, const uint16_t *saved_ln,
+                         uint16_t *grad_x, uint16_t *const *grad_w, uint16_t *const *grad_b, uint16_t *grad_ln_w, uint16_t *grad_ln_b,
+                         void *workspace, long workspace_bytes, vllm_stream_t stream);
 
 #ifdef __cplusplus
 }

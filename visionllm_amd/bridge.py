@@ -87,11 +87,12 @@ class _BridgeMixin:
     def _native(self, x, pixel_shuffle_flag=False, skip_cls=False):
         if not x.is_cuda or x.dtype != torch.bfloat16:
             raise RuntimeError("vl_bridge: bf16 CUDA input required (no CPU path)")
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            # the reference trains this slot (tune_vl_bridge); the native kernels are forward-only and their output has no
-            # grad_fn: refuse loudly instead of silently cutting the gradient
-            raise RuntimeError("vl_bridge (native): forward-only kernels -- call under torch.no_grad() or freeze the "
-                               "projector and its input (requires_grad_(False)); training the projector needs the torch modules")
+        if _trains(self, x):
+            # the fused select / CLS-skip / pixel-shuffle path has no backward and its output no grad_fn: refuse loudly instead of
+            # silently cutting the gradient (forward(x) is the training entry, modeling_visionllmv2.py:579)
+            raise RuntimeError("vl_bridge.project_hidden_state (native): the fused select / pixel-shuffle path is inference-only -- "
+                               "call it under torch.no_grad() or with the projector and its input frozen; train the projector "
+                               "through forward(x), which has a native backward")
         x = _lib.aligned(x)   # (the GEMM loaders need 16-byte aligned rows: a view at another storage offset is copied)
         n, rows, C = x.shape
         T = rows - 1 if skip_cls else rows
@@ -99,6 +100,8 @@ class _BridgeMixin:
         return _run(_desc_for(self, self.vl_bridge_type, pixel_shuffle_flag, skip_cls, keep), x, n, T, C)
 
     def forward(self, x):  # what modeling_visionllmv2.py:579 calls
+        if _trains(self, x):
+            return self._train_forward(x)
         lead = x.shape[:-2] if x.dim() > 3 else None
         if x.dim() == 2:
             return self._native(x[None])[0]
@@ -110,6 +113,113 @@ class _BridgeMixin:
     def project_hidden_state(self, hidden_state, use_pixelshuffle=False):
         """hidden_state [n, 1+T, C] (a hidden_states[vis_output_layer] entry) -> [n, T or T/4, C_llm]."""
         return self._native(hidden_state, use_pixelshuffle, True)
+
+    def _train_forward(self, x):
+        """forward(x) with grad: vllm_bridge_forward_train / vllm_bridge_backward through _BridgeTrain (same output bits as the
+        no-grad call)."""
+        if not x.is_cuda or x.dtype != torch.bfloat16:
+            raise RuntimeError("vl_bridge: bf16 CUDA input required (no CPU path)")
+        lin, ln = _modules(self, self.vl_bridge_type)
+        params = [t for m in lin for t in (m.weight, m.bias)] + ([ln.weight, ln.bias] if ln is not None else [])
+        C = x.shape[-1]
+        x2 = _lib.aligned(x.reshape(-1, C))   # (16-byte aligned rows: a view at another storage offset is copied -- differentiably)
+        y = _BridgeTrain.apply(self.vl_bridge_type, len(lin), ln.eps if ln is not None else 0.0, x2, *params)
+        return y.reshape(*x.shape[:-1], y.shape[-1])
+
+
+def _trains(mod, x):
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in mod.parameters()))
+
+
+def _modules(mod, kind):
+    """-> (the Linear modules, the LayerNorm or None) of a projector built by build_vl_bridge."""
+    if kind == "linear":
+        return [mod], None
+    if kind in ("internvl_mlp", "internvl"):
+        return [mod[1], mod[3]], mod[0]
+    return [m for m in mod if isinstance(m, nn.Linear)], None
+
+
+def _ptr_array(ts):
+    return (ctypes.c_void_p * 4)(*([t.data_ptr() if t is not None else None for t in ts] + [None] * (4 - len(ts))))
+
+
+class _BridgeTrain(torch.autograd.Function):
+    """The projector as one autograd node.  Inputs: x [rows, in_features] (16-byte aligned) and the parameters
+    (weight_0, bias_0, ..., [ln_weight, ln_bias]; a missing bias is None).  The parameters are saved with save_for_backward, so an
+    in-place update between forward and backward fails autograd's version check instead of producing wrong gradients."""
+
+    @staticmethod
+    def _desc(kind, depth, eps, params, keep):
+        lin_w, lin_b = params[0:2 * depth:2], params[1:2 * depth:2]
+        ln_w, ln_b = (params[2 * depth], params[2 * depth + 1]) if len(params) > 2 * depth else (None, None)
+
+        def P(t):
+            if t is None:
+                return None
+            if not t.is_cuda or t.dtype != torch.bfloat16:
+                raise RuntimeError("vl_bridge parameters must be bf16 CUDA tensors (no CPU path)")
+            a = _lib.aligned(t.detach())
+            keep.append(a)
+            return a.data_ptr()
+        k = (_lib.BRIDGE_LINEAR if kind == "linear" else _lib.BRIDGE_INTERNVL_MLP if kind in ("internvl_mlp", "internvl")
+             else _lib.BRIDGE_MLP_GELU)
+        d = _lib.VllmBridgeDesc(kind=k, depth=depth, in_features=lin_w[0].shape[1], out_features=lin_w[-1].shape[0],
+                                pixel_shuffle=0, skip_cls=0, ln_eps=eps, ln_w=P(ln_w), ln_b=P(ln_b))
+        for i in range(depth):
+            d.w[i] = P(lin_w[i])
+            d.b[i] = P(lin_b[i])
+        return d
+
+    @staticmethod
+    def forward(ctx, kind, depth, eps, x, *params):
+        keep = []
+        d = _BridgeTrain._desc(kind, depth, eps, params, keep)
+        rows, cout, dev = x.shape[0], d.out_features, x.device
+        L = _lib.lib()
+        _lib.check_struct_layouts()
+        out = torch.empty((rows, cout), dtype=torch.bfloat16, device=dev)
+        pre = [torch.empty((rows, cout), dtype=torch.bfloat16, device=dev) for _ in range(depth - 1)]
+        act = [torch.empty((rows, cout), dtype=torch.bfloat16, device=dev) for _ in range(depth - 1)]
+        ln = torch.empty((rows, d.in_features), dtype=torch.bfloat16, device=dev) if d.kind == _lib.BRIDGE_INTERNVL_MLP else None
+        with torch.cuda.device(dev):
+            wsb = L.vllm_bridge_backward_workspace_bytes(ctypes.byref(d), rows, 0)
+            _lib.check(0 if wsb >= 0 else -1, "vllm_bridge_backward_workspace_bytes")
+            ws = _lib.workspace(dev, max(wsb, 1))
+            _lib.check(L.vllm_bridge_forward_train(ctypes.byref(d), _lib.ptr(x), rows, _lib.ptr(out), _ptr_array(pre), _ptr_array(act),
+                                                   _lib.ptr(ln), _lib.ptr(ws), wsb, _lib.current_stream(dev)), "vllm_bridge_forward_train")
+        ctx.meta = (kind, depth, eps)
+        ctx.save_for_backward(x, ln, *pre, *act, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        kind, depth, eps = ctx.meta
+        saved = ctx.saved_tensors
+        x, ln = saved[0], saved[1]
+        pre, act = list(saved[2:1 + depth]), list(saved[1 + depth:2 * depth])
+        params = list(saved[2 * depth:])
+        keep = []
+        d = _BridgeTrain._desc(kind, depth, eps, params, keep)
+        rows, dev = x.shape[0], x.device
+        need_x = ctx.needs_input_grad[3]
+        ivl = d.kind == _lib.BRIDGE_INTERNVL_MLP
+        need_ln = ivl and any(ctx.needs_input_grad[4 + 2 * depth:])
+        g = _lib.aligned(gout.to(torch.bfloat16))
+        gw = [torch.empty(p.shape, dtype=torch.bfloat16, device=dev) for p in params[0:2 * depth:2]]
+        gb = [torch.empty(p.shape, dtype=torch.bfloat16, device=dev) if p is not None else None for p in params[1:2 * depth:2]]
+        gln = [torch.empty(p.shape, dtype=torch.bfloat16, device=dev) for p in params[2 * depth:]] if need_ln else [None, None]
+        gx = torch.empty((rows, d.in_features), dtype=torch.bfloat16, device=dev) if need_x else None
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            wsb = L.vllm_bridge_backward_workspace_bytes(ctypes.byref(d), rows, int(need_x))
+            _lib.check(0 if wsb >= 0 else -1, "vllm_bridge_backward_workspace_bytes")
+            ws = _lib.workspace(dev, max(wsb, 1))
+            _lib.check(L.vllm_bridge_backward(ctypes.byref(d), _lib.ptr(x), rows, _lib.ptr(g), _ptr_array(pre), _ptr_array(act), _lib.ptr(ln),
+                                              _lib.ptr(gx), _ptr_array(gw), _ptr_array(gb), _lib.ptr(gln[0]), _lib.ptr(gln[1]),
+                                              _lib.ptr(ws), wsb, _lib.current_stream(dev)), "vllm_bridge_backward")
+        grads = [t for i in range(depth) for t in (gw[i], gb[i])] + (gln if ivl else [])
+        return (None, None, None, gx) + tuple(grads)
 
 
 class NativeBridgeLinear(_BridgeMixin, nn.Linear):

@@ -260,6 +260,10 @@ int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
                  "gemm: X and W must be 16-byte aligned, Y 8-byte aligned (16-byte for fp32 output), row strides multiples of 8 elements");
     VLLM_REQUIRE(epi != EPI_RESIDUAL || (a.res && a.ldr % 4 == 0), "gemm: residual epilogue needs res");
     VLLM_REQUIRE(epi != EPI_EMBED || (a.res && a.P > 0), "gemm: embed epilogue needs the position table and P");
+    VLLM_REQUIRE(epi != EPI_GELU_BWD || (a.res && !a.bias && a.ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(a.res) & 7u) == 0),
+                 "gemm: the GELU-backward epilogue needs the saved pre-activation `res` (8-byte aligned, ldr a multiple of 4) and no bias");
+    VLLM_REQUIRE(epi != EPI_GELU_SAVE || (a.pre && (reinterpret_cast<uintptr_t>(a.pre) & 7u) == 0),
+                 "gemm: the training-forward epilogue needs an 8-byte aligned pre-activation output");
     // tall, skinny K = 256 problems (the linears of a deformable-attention layer): weight-stationary streaming kernel, bit-identical
     // to the 128 x 128 kernel below where both serve the shape (its EPI_MSDA form also takes L = 1 ... 3 levels, which the tile
     // kernel's epilogue does not).  A forced variant (tests / tuning) keeps its kernel.
@@ -301,6 +305,8 @@ int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
     case EPI_EMBED: L(EPI_EMBED); break;
     case EPI_F32: L(EPI_F32); break;
     case EPI_MSDA: L(EPI_MSDA); break;
+    case EPI_GELU_BWD: L(EPI_GELU_BWD); break;
+    case EPI_GELU_SAVE: L(EPI_GELU_SAVE); break;
     default: set_error("gemm: unknown epilogue %d", epi); return VLLM_EINVAL;
     }
 #undef L

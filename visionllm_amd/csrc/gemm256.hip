@@ -880,6 +880,10 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
         b.sk_tiles = 0;
         b.mt = ceil_div(a.M, 64 * pmt);
         if (gemm256p_takes(epi, b, cus)) return a.dry_run ? VLLM_OK : gemm256p_launch(epi, pmt, b, cus, st);
+        // the training forward's GELU GEMM (EPI_GELU_SAVE) must give the bits of the inference forward's EPI_GELU: where the persistent
+        // schedule takes that one, one workgroup per tile WITHOUT a stream-K tail does (same MFMA sequence per tile, same epilogue
+        // arithmetic: test_gemm256_persistent_schedule), and stores the pre-activation as well
+        if (epi == EPI_GELU_SAVE && gemm256p_takes(EPI_GELU, b, cus)) a.sk_tiles = 0;
     }
     if (a.dry_run) return VLLM_EINVAL;   // (asked only whether the persistent schedule would take this GEMM: no message, no launch)
     VLLM_REQUIRE(!a.ln_wide, "gemm256: wide folded-norm statistics are implemented by the persistent schedule only (at least as many tiles as CUs, "
@@ -908,6 +912,7 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256_bf16_kernel<E, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256_bf16_kernel<E, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
         SETATTR(EPI_BIAS); SETATTR(EPI_GELU); SETATTR(EPI_QUICK_GELU); SETATTR(EPI_RESIDUAL); SETATTR(EPI_EMBED); SETATTR(EPI_F32);
+        SETATTR(EPI_GELU_BWD); SETATTR(EPI_GELU_SAVE);
 #undef SETATTR
     }
 #define L(E) do { if (mf32) VLLM_LAUNCH((gemm256_bf16_kernel<E, 4, true>), grid, block, lds, st, a); \
@@ -929,6 +934,8 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
     case EPI_RESIDUAL: L(EPI_RESIDUAL); break;
     case EPI_EMBED: L(EPI_EMBED); break;
     case EPI_F32: L(EPI_F32); break;
+    case EPI_GELU_BWD: L(EPI_GELU_BWD); break;
+    case EPI_GELU_SAVE: L(EPI_GELU_SAVE); break;
     default: set_error("gemm256: unknown epilogue %d", epi); return VLLM_EINVAL;
     }
 #undef L

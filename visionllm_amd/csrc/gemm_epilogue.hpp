@@ -21,6 +21,13 @@ __device__ __forceinline__ float fast_erf(float x)
     return copysignf(r, x);
 }
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + fast_erf(x * 0.70710678118654752440f)); }
+// d gelu_erf / dx = Phi(x) + x phi(x) = 1/2 (1 + erf(x / sqrt 2)) + x exp(-x^2 / 2) / sqrt(2 pi)   (projector backward, EPI_GELU_BWD)
+__device__ __forceinline__ float gelu_erf_grad(float x)
+{
+    const float cdf = 0.5f * (1.0f + fast_erf(x * 0.70710678118654752440f));
+    const float pdf = __builtin_amdgcn_exp2f(-0.72134752044448170368f * x * x) * 0.39894228040143267794f;
+    return fmaf(x, pdf, cdf);
+}
 __device__ __forceinline__ float quick_gelu(float x)
 {
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * x));
@@ -58,6 +65,19 @@ __device__ __forceinline__ void epi_value(const GemmArgs &a, int m, int n, const
     if (EPI == EPI_GELU) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+    } else if (EPI == EPI_GELU_SAVE) {
+        // training forward: EPI_GELU's arithmetic, and the pre-activation leaves too (bf16, row stride ldy) for the backward's gelu'
+        uint2_t h;
+        h.x = pack_bf16x2(v[0], v[1]);
+        h.y = pack_bf16x2(v[2], v[3]);
+        *reinterpret_cast<uint2_t *>(a.pre + (size_t)m * a.ldy + n) = h;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+    } else if (EPI == EPI_GELU_BWD) {
+        // y = acc * gelu'(res[m, n]), res = the saved pre-activation (no bias: the launcher refuses one)
+        const uint2_t rr = *reinterpret_cast<const uint2_t *>(a.res + (size_t)m * a.ldr + n);
+        v[0] *= gelu_erf_grad(bf16lo_to_f32(rr.x)); v[1] *= gelu_erf_grad(bf16hi_to_f32(rr.x));
+        v[2] *= gelu_erf_grad(bf16lo_to_f32(rr.y)); v[3] *= gelu_erf_grad(bf16hi_to_f32(rr.y));
     } else if (EPI == EPI_QUICK_GELU) {
         // x * sigmoid(1.702 x), x = acc + bias: the exponent -1.702 log2(e) (acc + bias) is ONE fma of the accumulator (the bias
         // times the constant is per column) instead of add + multiply -- 5.5 instead of 6.5 VALU per element of a tile whose

@@ -11,7 +11,9 @@ enum GemmEpilogue : int {
     EPI_RESIDUAL = VLLM_EPI_RESIDUAL,
     EPI_EMBED = VLLM_EPI_EMBED,
     EPI_F32 = VLLM_EPI_F32,
+    EPI_GELU_BWD = VLLM_EPI_GELU_BWD,
     EPI_MSDA = 100,   // internal (msda_layer.hip): offsets -> sampling locations, logits -> softmax weights, both fp32
+    EPI_GELU_SAVE = 101,   // internal (bridge_train.cpp): EPI_GELU that also stores the pre-activation to GemmArgs::pre
 };
 
 struct GemmArgs {
@@ -72,6 +74,7 @@ struct GemmArgs {
     int tile_rb = 0;                // persistent schedule, tile order: 0 = the dense XCD order of gemm256.hip; RB > 0 = banded (launcher)
     unsigned long long *trace = nullptr;   // VLLM_GEMM_TRACE=<device address of 3 x 8192 uint64>: per block {start, end} in
                                            // 100 MHz s_memrealtime ticks + HW_ID (which CU), for tools/prof_gemm256.py
+    uint16_t *pre = nullptr;   // EPI_GELU_SAVE: [M, N] bf16 pre-activation, row stride ldy (8-byte aligned)
 };
 
 int gemm_direct_store();       // VLLM_GEMM_DIRECT_STORE / vllm_set_option("gemm_direct_store")
@@ -99,6 +102,16 @@ int msda_layer_fused();        // VLLM_MSDA_LAYER_FUSED / vllm_set_option("msda_
 int msda_tiled_enabled();      // VLLM_MSDA_TILED / vllm_set_option("msda_tiled")
 
 int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st);
+
+// Projector backward (gemm_wgrad.hip, bridge_bwd.hip; orchestrated by bridge_train.cpp)
+long gemm_wgrad_workspace_bytes(int M, int N, int K);
+int gemm_wgrad_launch(const uint16_t *dY, int ldy, const uint16_t *A, int lda, int M, int N, int K, uint16_t *dW, int ldw,
+                      uint16_t *db, void *ws, long ws_bytes, hipStream_t st);
+// Wt[c, r] = W[r, c] for W [R, C] (R, C multiples of 64; 16-byte aligned, row strides multiples of 8)
+int transpose_bf16_launch(const uint16_t *w, int ldw, uint16_t *wt, int ldt, int R, int C, hipStream_t st);
+long ln_bwd_workspace_bytes(long rows, int C);
+int ln_bwd_launch(const uint16_t *x, int ldx, const float *dz, int ldz, const uint16_t *gamma, float eps, long rows, int C,
+                  uint16_t *dx, int lddx, uint16_t *grad_w, uint16_t *grad_b, void *ws, long ws_bytes, hipStream_t st);
 
 // In-step kernel timing (vllm_prof_enable / vllm_prof_read): when enabled, the orchestrators record a HIP event in front of
 // every operator they enqueue; the time from one mark to the next is attributed to the first one's tag, so a kernel is
