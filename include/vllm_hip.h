@@ -273,6 +273,32 @@ int vllm_point_sample_f32(const float *input, const float *coords, int N, int C,
 /* out[n, c] = sum_p valid * sample / sum_p valid, 0 for a region without points ((x / 0).nan_to_num() of the reference). */
 int vllm_point_sample_mean_f32(const float *input, const float *coords, const uint8_t *valid, int N, int C, int H, int W, int P,
                                float *out /* [N,C] */, vllm_stream_t stream);
+/* Backward with respect to the feature map.  Replaces: the autograd of region_encoder.py:135-140 (F.grid_sample's backward -- one
+ * float atomic add per (point, corner, channel) -- then the backward of the mask, the sum and the division).
+ * The masked mean is linear in the map, out[n, c] = (1 / cnt_n) sum_pix A[n, pix] in[n, c, pix] with A[n, pix] the sum of the corner
+ * weights the valid points put on pix, so
+ *     grad_in[n, c, pix] = (A[n, pix] / cnt_n) * grad_out[n, c]
+ * an outer product: every element of grad_in [N, C, H, W] is written exactly once (no zero-fill by the caller, no atomics on it, the
+ * same bits on every run), and the map itself is not an operand.  Weights are the forward's bit for bit.
+ * EMPTY REGION: a region without a valid point gets grad_in[n] = 0, the derivative of the constant 0 the forward returns for it; the
+ * reference's autograd puts NaN on every pixel one of the region's (invalid) points touches (0 * (1 / 0) in the division's
+ * backward).  Deliberate departure.
+ * grad_out [N, C] fp32; grad_in fp32 or bf16 (the fp32 value rounded to nearest even once).  With P == 0 grad_in is written as zeros.
+ * Maps too large for the on-chip accumulators (80 x 80, ...) build A in the caller's workspace: the query returns 0 where none is
+ * needed; the entry points clear what they use of it themselves.
+ * vllm_point_sample_backward_f32 is the unfused form, grad_in[n, c, pix] = sum_p w(p, pix) grad_out[n, c, p] with grad_out [N, C, P]:
+ * fully written as well, but summed with float atomics in arrival order -- the last bits may differ between runs.  It needs no
+ * workspace (NULL / 0 are accepted).
+ * Alignment (all three): coords 8 bytes, workspace 8 bytes; grad_in 4 bytes (2 for bf16) is enough, 16 bytes enables wide stores. */
+long vllm_point_sample_backward_workspace_bytes(int N, int C, int H, int W, int P);   /* 0 = none needed */
+int vllm_point_sample_mean_backward_f32(const float *coords, const uint8_t *valid, const float *grad_out /* [N,C] */, int N, int C, int H,
+                                        int W, int P, float *grad_in /* [N,C,H,W] */, void *workspace, long workspace_bytes,
+                                        vllm_stream_t stream);
+int vllm_point_sample_mean_backward_bf16(const float *coords, const uint8_t *valid, const float *grad_out /* [N,C] */, int N, int C, int H,
+                                         int W, int P, uint16_t *grad_in /* [N,C,H,W] */, void *workspace, long workspace_bytes,
+                                         vllm_stream_t stream);
+int vllm_point_sample_backward_f32(const float *coords, const float *grad_out /* [N,C,P] */, int N, int C, int H, int W, int P,
+                                   float *grad_in /* [N,C,H,W] */, void *workspace, long workspace_bytes, vllm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Building blocks of the ViT path (bf16 storage, fp32 accumulation).  Exposed individually so the parity

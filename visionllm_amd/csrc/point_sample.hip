@@ -5,63 +5,17 @@
 // ATen's arithmetic (grid_sampler_unnormalize / bilinear with per-corner bounds, GridSampler.h): g = 2*c - 1,
 // ix = ((g + 1) * W - 1) / 2, corners floor(ix), floor(ix)+1, a corner outside the map contributes nothing.
 #include "common.hpp"
+#include "point_sample_geo.hpp"   // ps_corner / ps_geo, PS_CCH, PS_LDS_MAX (shared with point_sample_bwd.hip)
 
 namespace vllm {
 namespace {
 
-struct PsCorner {
-    int x0, y0;
-    float w00, w01, w10, w11;   // weights of (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1), zero where out of the map
-    bool any;
-};
-
-__device__ __forceinline__ PsCorner ps_corner(float cx, float cy, int H, int W)
-{
-    PsCorner k;
-    const float gx = 2.0f * cx - 1.0f, gy = 2.0f * cy - 1.0f;
-    const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f, iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
-    // NaN / inf / far-away coordinates never reach address arithmetic
-    const bool fin = ix > -2.f && iy > -2.f && ix < (float)W + 1.f && iy < (float)H + 1.f;
-    const float fx = fin ? floorf(ix) : 0.f, fy = fin ? floorf(iy) : 0.f;
-    k.x0 = (int)fx; k.y0 = (int)fy;
-    const float tx = ix - fx, ty = iy - fy;
-    const bool xl = fin && k.x0 >= 0 && k.x0 < W, xh = fin && k.x0 + 1 >= 0 && k.x0 + 1 < W;
-    const bool yl = k.y0 >= 0 && k.y0 < H, yh = k.y0 + 1 >= 0 && k.y0 + 1 < H;
-    k.w00 = (xl && yl) ? (1.f - tx) * (1.f - ty) : 0.f;
-    k.w01 = (xh && yl) ? tx * (1.f - ty) : 0.f;
-    k.w10 = (xl && yh) ? (1.f - tx) * ty : 0.f;
-    k.w11 = (xh && yh) ? tx * ty : 0.f;
-    k.any = (xl || xh) && (yl || yh);
-    return k;
-}
-
-// Round 5: both kernels evaluate a point's corner geometry ONCE and walk a chunk of channels with it (rounds 1-4: one thread per
-// output element -- ~40 VALU of coordinate arithmetic per 4 loads and a store: 0.12 / 0.04 of the HBM roofline at the region
-// encoder's shapes, profiles/r05_bench_line.json).  The zero-weight guards (a NaN at a clamped address must not get through a zero
-// weight) are selects on the loaded values.
-struct PsGeo {
-    int o00, o01, o10, o11;     // clamped element offsets inside a plane
-    float w00, w01, w10, w11;
-};
-__device__ __forceinline__ PsGeo ps_geo(float cx, float cy, int H, int W)
-{
-    const PsCorner k = ps_corner(cx, cy, H, W);
-    PsGeo g;
-    const int x0 = min(max(k.x0, 0), W - 1), x1 = min(max(k.x0 + 1, 0), W - 1);
-    const int y0 = min(max(k.y0, 0), H - 1), y1 = min(max(k.y0 + 1, 0), H - 1);
-    g.o00 = y0 * W + x0; g.o01 = y0 * W + x1; g.o10 = y1 * W + x0; g.o11 = y1 * W + x1;
-    g.w00 = k.any ? k.w00 : 0.f; g.w01 = k.any ? k.w01 : 0.f; g.w10 = k.any ? k.w10 : 0.f; g.w11 = k.any ? k.w11 : 0.f;
-    return g;
-}
 __device__ __forceinline__ float ps_eval_geo(const float *__restrict__ plane, const PsGeo &g)
 {
     const float a = plane[g.o00], b = plane[g.o01], c = plane[g.o10], d = plane[g.o11];
     const float v00 = g.w00 != 0.f ? a : 0.f, v01 = g.w01 != 0.f ? b : 0.f, v10 = g.w10 != 0.f ? c : 0.f, v11 = g.w11 != 0.f ? d : 0.f;
     return v00 * g.w00 + v01 * g.w01 + v10 * g.w10 + v11 * g.w11;   // (the association of rounds 1-4: same bits)
 }
-
-constexpr int PS_CCH = 16;      // channel planes a block stages / a thread walks
-constexpr int PS_LDS_MAX = 48 * 1024;   // the planes of a block in LDS when they fit (24 x 24 x 16 x 4 B = 36 KiB at the region encoder's shape)
 
 // the block's PS_CCH planes [c][H * W] into LDS (coalesced 4-byte loads: a plane is only 16-byte aligned when H * W % 4 == 0)
 __device__ __forceinline__ void ps_stage(const float *__restrict__ planes, float *lds, int n_elems)
@@ -196,6 +150,8 @@ __global__ __launch_bounds__(256) void point_sample_mean_pix_kernel(const float 
                 const float4_t wv = *reinterpret_cast<const float4_t *>(A + i);
                 const float4_t xa = *reinterpret_cast<const float4_t *>(pa + i), xb = *reinterpret_cast<const float4_t *>(pb + i);
                 // (a non-finite value at a pixel no valid point touches must not get through its zero weight: selects, as in ps_eval_geo)
+                // (the scatter truncates a corner weight to a multiple of 2^-40: a weight below 2^-40 adds nothing, so a pixel touched only by
+                // such weights counts as untouched here -- and in the backward, which rebuilds the same A -- while the point walk keeps it)
                 float ta[4], tb[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { ta[k] = wv[k] != 0.f ? wv[k] * xa[k] : 0.f; tb[k] = wv[k] != 0.f ? wv[k] * xb[k] : 0.f; }

@@ -4,6 +4,10 @@ Same names and parameter layout as visionllmv2/model/region_encoder.py: ``LayerN
 (:24-47), ``rand_sample`` (:50-65), ``RegionEncoder`` (:68-147).  The convolutional mask embedding stays torch modules
 (MIOpen); the per-region pooling of the 'grid_sample' type -- bilinear sampling of up to 2304 points per region and their
 masked mean -- is ONE native call (libvllm_hip.so: vllm_point_sample_mean_f32) instead of grid_sample + mask + sum + div.
+Under autograd (the feature map requires grad: the reference trains the region encoder) the same forward kernels run inside
+``torch.autograd.Function``s whose backward is native too (vllm_point_sample_mean_backward_f32 / _bf16: an outer product of
+the region's pixel weights and grad_out, include/vllm_hip.h section f4); gradients with respect to the sampling positions
+are not implemented.
 """
 import torch
 import torch.nn.functional as F
@@ -37,18 +41,96 @@ def _check_ps(input, point_coords, kwargs):
         raise ValueError("point_sample: input must be (N, C, H, W) and point_coords (N, P, 2) or (N, Hg, Wg, 2)")
 
 
+def _no_coord_grad(who, point_coords):
+    if point_coords.requires_grad:
+        raise NotImplementedError(f"{who} (native): point_coords requires grad, and the native backward differentiates the "
+                                  "feature map only (VisionLLMv2 takes the sampling positions from nonzero())")
+
+
+def _train_map(input):
+    """The differentiable calls take the map in fp32 or bf16; any other dtype is converted here, under autograd."""
+    return input if input.dtype in (torch.float32, torch.bfloat16) else input.to(torch.float32)
+
+
+class _PointSampleMaskedMean(torch.autograd.Function):
+    """Masked mean under autograd.  It is linear in the map, so the backward needs only the points: the map is never saved.
+    grad_in = (pixel weights / count) (x) grad_out, written once, in the map's dtype (zeros for a region without points)."""
+
+    @staticmethod
+    def forward(ctx, input, pts, v):
+        N, C, H, W = input.shape
+        P = pts.shape[1]
+        x = input.to(torch.float32).contiguous()
+        out = torch.empty((N, C), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().vllm_point_sample_mean_f32(_lib.ptr(x), _lib.ptr(pts), _lib.ptr(v), N, C, H, W, P, _lib.ptr(out),
+                                                             _lib.current_stream(x.device)), "vllm_point_sample_mean_f32")
+        ctx.save_for_backward(pts, v)
+        ctx.map_shape, ctx.map_dtype = (N, C, H, W), input.dtype
+        return out.to(input.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        pts, v = ctx.saved_tensors
+        N, C, H, W = ctx.map_shape
+        P = pts.shape[1]
+        g = grad_out.to(torch.float32).contiguous()
+        grad_in = torch.empty(ctx.map_shape, dtype=ctx.map_dtype, device=g.device)
+        name = "vllm_point_sample_mean_backward_bf16" if ctx.map_dtype == torch.bfloat16 else "vllm_point_sample_mean_backward_f32"
+        with torch.cuda.device(g.device):
+            nbytes = _lib.lib().vllm_point_sample_backward_workspace_bytes(N, C, H, W, P)
+            _lib.check(min(nbytes, 0), "vllm_point_sample_backward_workspace_bytes")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device) if nbytes else None   # (allocations are 512-byte aligned)
+            _lib.check(getattr(_lib.lib(), name)(_lib.ptr(pts), _lib.ptr(v), _lib.ptr(g), N, C, H, W, P, _lib.ptr(grad_in),
+                                                 _lib.ptr(ws), nbytes, _lib.current_stream(g.device)), name)
+        return grad_in, None, None
+
+
+class _PointSample(torch.autograd.Function):
+    """point_sample under autograd: grad_in[n, c, pix] = sum_p w(p, pix) grad_out[n, c, p], an fp32 kernel that sums with float
+    atomics (the last bits may differ between runs).  Nothing in the model trains through this entry.  The map is not saved."""
+
+    @staticmethod
+    def forward(ctx, input, pts):
+        N, C, H, W = input.shape
+        P = pts.shape[1]
+        x = input.to(torch.float32).contiguous()
+        out = torch.empty((N, C, P), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().vllm_point_sample_f32(_lib.ptr(x), _lib.ptr(pts), N, C, H, W, P, _lib.ptr(out),
+                                                        _lib.current_stream(x.device)), "vllm_point_sample_f32")
+        ctx.save_for_backward(pts)
+        ctx.map_shape, ctx.map_dtype = (N, C, H, W), input.dtype
+        return out.to(input.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (pts,) = ctx.saved_tensors
+        N, C, H, W = ctx.map_shape
+        P = pts.shape[1]
+        g = grad_out.to(torch.float32).contiguous()
+        grad_in = torch.empty(ctx.map_shape, dtype=torch.float32, device=g.device)
+        with torch.cuda.device(g.device):
+            _lib.check(_lib.lib().vllm_point_sample_backward_f32(_lib.ptr(pts), _lib.ptr(g), N, C, H, W, P, _lib.ptr(grad_in), None, 0,
+                                                                 _lib.current_stream(g.device)), "vllm_point_sample_backward_f32")
+        return grad_in.to(ctx.map_dtype), None
+
+
 def point_sample(input, point_coords, **kwargs):
-    """(N, C, H, W), (N, P, 2) or (N, Hg, Wg, 2) in [0, 1]^2 -> (N, C, P) or (N, C, Hg, Wg)."""
+    """(N, C, H, W), (N, P, 2) or (N, Hg, Wg, 2) in [0, 1]^2 -> (N, C, P) or (N, C, Hg, Wg).  Differentiable in ``input``."""
     _check_ps(input, point_coords, kwargs)
     N, C, H, W = input.shape
     grid = point_coords.dim() == 4
     pts = _lib.aligned(point_coords.reshape(N, -1, 2).to(torch.float32), 8)   # (coordinate pairs are read as 8-byte vectors)
+    if torch.is_grad_enabled() and (input.requires_grad or point_coords.requires_grad):
+        _no_coord_grad("point_sample", point_coords)
+        out = _PointSample.apply(_train_map(input), pts).to(input.dtype)
+        return out.reshape(N, C, point_coords.shape[1], point_coords.shape[2]) if grid else out
     x = input.to(torch.float32).contiguous()
     P = pts.shape[1]
     out = torch.empty((N, C, P), dtype=torch.float32, device=x.device)
-    if torch.is_grad_enabled() and (input.requires_grad or point_coords.requires_grad):
-        raise RuntimeError("point_sample (native): forward-only kernel -- call under torch.no_grad(); the reference "
-                           "differentiates through F.grid_sample here")
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().vllm_point_sample_f32(_lib.ptr(x), _lib.ptr(pts), N, C, H, W, P, _lib.ptr(out),
                                                     _lib.current_stream(x.device)), "vllm_point_sample_f32")
@@ -57,17 +139,18 @@ def point_sample(input, point_coords, **kwargs):
 
 
 def point_sample_masked_mean(input, point_coords, valid):
-    """Fused form of region_encoder.py:135-140: mean over the valid points of every region, (N, C)."""
+    """Fused form of region_encoder.py:135-140: mean over the valid points of every region, (N, C).  Differentiable in ``input``
+    (region_encoder.py:135-140 trains mask_embedding through grid_sample: here through the native backward)."""
     _check_ps(input, point_coords, {})
     N, C, H, W = input.shape
     pts = _lib.aligned(point_coords.to(torch.float32), 8)   # (coordinate pairs are read as 8-byte vectors)
     P = pts.shape[1]
-    x = input.to(torch.float32).contiguous()
     v = valid.to(torch.uint8).contiguous()
-    out = torch.empty((N, C), dtype=torch.float32, device=x.device)
     if torch.is_grad_enabled() and (input.requires_grad or point_coords.requires_grad):
-        # region_encoder.py:135-140 trains mask_embedding through grid_sample; this kernel has no backward
-        raise RuntimeError("point_sample_masked_mean (native): forward-only kernel -- call under torch.no_grad()")
+        _no_coord_grad("point_sample_masked_mean", point_coords)
+        return _PointSampleMaskedMean.apply(_train_map(input), pts, v).to(input.dtype)
+    x = input.to(torch.float32).contiguous()
+    out = torch.empty((N, C), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         _lib.check(_lib.lib().vllm_point_sample_mean_f32(_lib.ptr(x), _lib.ptr(pts), _lib.ptr(v), N, C, H, W, P, _lib.ptr(out),
                                                          _lib.current_stream(x.device)), "vllm_point_sample_mean_f32")
