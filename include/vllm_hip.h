@@ -444,6 +444,24 @@ long vllm_splice_workspace_ints(int B, int L, int n_tiles);
 int vllm_splice_visual_tokens_bf16(const int64_t *input_ids, long imp_token_id, const uint16_t *image_features,
                                    const int32_t *tiles_per_sample, int B, int L, int n_tiles, int T, int C,
                                    uint16_t *inputs_embeds, int32_t *workspace, int32_t *status, vllm_stream_t stream);
+/* Backward of that splice.  Replaces: the autograd of modeling_visionllmv2.py:582-605 (`inputs_embeds[selected] * 0.0 + vit_embeds`,
+ * the index assignment, `image_features[has_image]`, the repeat of :597-603) -- several full [B L, C] passes and two host
+ * synchronisations there, one pass over grad_out here.
+ *   workspace: the forward call's, exactly as it left it (slot list, kept tiles, header): no second scan of input_ids, no host read,
+ *   no allocation.  grad_out [B, L, C]: gradient of the spliced embeddings.  B, L, n_tiles, T, C: the forward's.
+ *   grad_inputs_embeds [B, L, C]    = grad_out with the rows the forward overwrote set to zero;
+ *   grad_image_features [n_tiles, T, C]: visual token j of the kept tiles (tile kept[j / T], token j % T) gets the sum of
+ *     grad_out[slots[r]] over r = j, j + n_vit, ... below the rows moved -- one term when the counts were equal (a pure move), k terms
+ *     under the repeat rule, added in fp32 in ascending r and rounded to bf16 once; tiles of samples without an image get zero rows.
+ * A forward that wrote nothing (error flag set) gives grad_inputs_embeds = grad_out and grad_image_features = 0.
+ * Either output may be NULL (not needed: its rows cost no traffic).  An output that is passed is written completely by the call (no
+ * zero-fill by the caller, no atomics, the same bits on every run); every grad_out row is read once.  A refused call (VLLM_EINVAL)
+ * writes nothing; B L == 0 and n_tiles T == 0 are accepted.
+ * NON-FINITE grad_out AT A SLOT ROW: grad_inputs_embeds gets 0 there, the derivative of a row that was overwritten; the reference's
+ * autograd gives NaN (0.0 * inf in the backward of `* 0.0`).  Deliberate departure. */
+/* Alignment: grad_out, grad_inputs_embeds and grad_image_features 16 bytes. */
+int vllm_splice_visual_tokens_backward_bf16(const int32_t *workspace, const uint16_t *grad_out, int B, int L, int n_tiles, int T, int C,
+                                            uint16_t *grad_inputs_embeds, uint16_t *grad_image_features, vllm_stream_t stream);
 
 /* The per-sample token loops around the LLM (modeling_visionllmv2.py:440-527 [EMB] splice, :609-715 region features and
  * <region> slots, :775-787 [EMB] hidden states -> text_query) as index bookkeeping + ONE row mover:

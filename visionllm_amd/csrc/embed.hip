@@ -204,6 +204,89 @@ __global__ __launch_bounds__(256) void splice_move_kernel(const uint16_t *__rest
     }
 }
 
+// ---- backward of the splice: pure row movement again, driven by the workspace the forward left (slot list, kept tiles, header) ----
+// How many entries of the ascending list a[0, n) are below v.  Wave-uniform: 64 probes per step, so 2^18 entries take three steps.
+__device__ __forceinline__ int wave_lower_bound(const int32_t *__restrict__ a, int n, int v, int lane)
+{
+    int lo = 0, len = n;   // the answer lies in [lo, lo + len]
+    while (len > 0) {
+        const int step = (len + 63) / 64;
+        const long off = (long)(lane + 1) * step - 1;
+        const bool below = off < len && a[lo + off] < v;   // (ascending: true on a prefix of the lanes)
+        const int c = __popcll(__ballot(below));
+        const int rest = len - c * step;
+        lo += c * step;
+        len = rest < step - 1 ? rest : step - 1;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ void zero_row(uint16_t *__restrict__ d, int cch, int lane)
+{
+    const uint4_t z = {0u, 0u, 0u, 0u};
+    for (int ck = lane; ck < cch; ck += 64) *reinterpret_cast<uint4_t *>(d + ck * 8) = z;
+}
+
+// d = bf16(s[rows[0]] + s[rows[stride]] + ...), k terms added in fp32 in that order and rounded once
+__device__ __forceinline__ void sum_rows(const uint16_t *__restrict__ s, const int32_t *__restrict__ rows, long stride, int k,
+                                         long s_rows, int C, uint16_t *__restrict__ d, int cch, int lane)
+{
+    for (int ck = lane; ck < cch; ck += 64) {
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < k; ++t) {
+            const long r = rows[t * stride];
+            if (r < 0 || r >= s_rows) continue;
+            const uint4_t v = *reinterpret_cast<const uint4_t *>(s + r * C + ck * 8);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { acc[2 * e] += bf16lo_to_f32(v[e]); acc[2 * e + 1] += bf16hi_to_f32(v[e]); }
+        }
+        uint4_t o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(acc[2 * e], acc[2 * e + 1]);
+        *reinterpret_cast<uint4_t *>(d + ck * 8) = o;
+    }
+}
+
+// A wave per item.  Items [0, n_chunks): SPLB_ROWS consecutive rows of grad_embeds -- a slot row is zeroed, any other row is
+// grad_out's (one search of the slot list per chunk, then a walk).  Items behind them: one row of grad_feats each -- visual token j
+// of a kept tile sums grad_out over the slots r = j, j + n_vit, ... < rows moved; a dropped tile, or a forward that wrote nothing,
+// gives zeros.  Every grad_out row is read by exactly one of the two halves, every output row is written exactly once.  A half whose
+// output was not asked for has no items (n_chunks / n_frows == 0); n_tok = n_tiles * T either way.
+constexpr int SPLB_ROWS = 4;
+__global__ __launch_bounds__(256) void splice_backward_kernel(const int32_t *__restrict__ ws, const uint16_t *__restrict__ gout, long n,
+                                                              long n_chunks, long n_frows, long n_tok, int T, int C,
+                                                              uint16_t *__restrict__ gemb, uint16_t *__restrict__ gfeat)
+{
+    const int cch = C / 8, lane = threadIdx.x & 63;
+    const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
+    // (the header is the forward's; the clamps and the row checks below only keep a workspace that is NOT the forward's inside the tensors)
+    const int n_vit = ws[1] > 0 && ws[1] <= n_tok ? ws[1] : 0;
+    const int n_move = n_vit > 0 && ws[0] > 0 && ws[0] <= n ? ws[0] : 0;
+    const int32_t *slots = ws + SPL_HDR, *kept = ws + SPL_HDR + n;
+    for (long it = wave; it < n_chunks + n_frows; it += nwaves) {
+        if (it < n_chunks) {
+            const long r0 = it * SPLB_ROWS, r1 = r0 + SPLB_ROWS < n ? r0 + SPLB_ROWS : n;
+            int p = wave_lower_bound(slots, n_move, (int)r0, lane);
+            for (long r = r0; r < r1; ++r) {
+                if (p < n_move && slots[p] == r) { zero_row(gemb + r * C, cch, lane); ++p; }
+                else move_row(gout + r * C, gemb + r * C, cch, lane);
+            }
+        } else {
+            const long q = it - n_chunks;
+            const int tile = (int)(q / T), tok = (int)(q - (long)tile * T), n_kept = n_vit / T;
+            const int kt = n_move > 0 ? wave_lower_bound(kept, n_kept, tile, lane) : n_kept;
+            uint16_t *d = gfeat + q * C;
+            if (kt >= n_kept || kept[kt] != tile) { zero_row(d, cch, lane); continue; }
+            const int j = kt * T + tok, k = n_move / n_vit;
+            if (k == 1) {
+                const long s = slots[j];
+                if (s >= 0 && s < n) move_row(gout + s * C, d, cch, lane);
+                else zero_row(d, cch, lane);
+            } else sum_rows(gout, slots + j, n_vit, k, n, C, d, cch, lane);
+        }
+    }
+}
+
 static inline unsigned grid_for(long n)
 {
     long b = (n + 255) / 256;
@@ -306,6 +389,25 @@ extern "C" int vllm_splice_visual_tokens_bf16(const int64_t *input_ids, long imp
     VLLM_LAUNCH(splice_move_kernel, dim3(grid_for((long)B * L * 64)), dim3(256), 0, (hipStream_t)stream, image_features, workspace,
                 (long)B * L, T, C, inputs_embeds);
     VLLM_CHECK_LAUNCH("splice_move_kernel");
+    return VLLM_OK;
+}
+
+extern "C" int vllm_splice_visual_tokens_backward_bf16(const int32_t *workspace, const uint16_t *grad_out, int B, int L, int n_tiles, int T,
+                                                       int C, uint16_t *grad_inputs_embeds, uint16_t *grad_image_features,
+                                                       vllm_stream_t stream)
+{
+    VLLM_REQUIRE(B >= 0 && L >= 0 && n_tiles >= 0 && T >= 0 && C > 0 && C % 8 == 0, "splice_visual_tokens_backward: bad sizes (C must be a positive multiple of 8)");
+    VLLM_REQUIRE(B <= SPL_MAXB && (long)B * L < (1L << 31) && (long)n_tiles * T < (1L << 31), "splice_visual_tokens_backward: too many samples / positions / tokens for one call");
+    VLLM_REQUIRE(aligned16(grad_out) && aligned16(grad_inputs_embeds) && aligned16(grad_image_features),
+                 "splice_visual_tokens_backward: grad_out, grad_inputs_embeds and grad_image_features must be 16-byte aligned");
+    const long n = (long)B * L, n_tok = (long)n_tiles * T;
+    const long n_chunks = grad_inputs_embeds ? (n + SPLB_ROWS - 1) / SPLB_ROWS : 0, n_frows = grad_image_features ? n_tok : 0;
+    if (n_chunks + n_frows == 0) return VLLM_OK;
+    VLLM_REQUIRE(workspace, "splice_visual_tokens_backward: null workspace");
+    VLLM_REQUIRE(n == 0 || grad_out, "splice_visual_tokens_backward: null grad_out");
+    VLLM_LAUNCH(splice_backward_kernel, dim3(grid_for((n_chunks + n_frows) * 64)), dim3(256), 0, (hipStream_t)stream, workspace, grad_out, n,
+                n_chunks, n_frows, n_tok, T, C, grad_inputs_embeds, grad_image_features);
+    VLLM_CHECK_LAUNCH("splice_backward_kernel");
     return VLLM_OK;
 }
 

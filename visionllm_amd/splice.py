@@ -5,7 +5,9 @@ synchronisations, two full copies); here the whole splice -- slot list, ``has_im
 the token-count rule, the row movement -- is ONE native call (``vllm_splice_visual_tokens_bf16``, round 5; rounds 1-4:
 ``torch.nonzero`` + a scatter kernel).  The call itself does not synchronise; with ``check=True`` (the default, and what bench.py
 times) the wrapper then reads the 4-int status word back, which IS a host synchronisation -- the one the reference's error
-behaviour costs.  ``check=False`` skips it and hands the status tensor to the caller instead (``status=`` / ``return_status``).
+behaviour costs.  ``check=False`` skips it and hands the status tensor to the caller instead (``return_status=True``).
+Under autograd the call is an in-place node with a native backward (``vllm_splice_visual_tokens_backward_bf16``): the LLM loss reaches
+the projector through this statement and nothing else.
 Limit: B <= 4096 samples per call (the slot scan is one block; the torch implementation of rounds 1-4 had none)."""
 import ctypes
 
@@ -35,22 +37,19 @@ def splice_visual_tokens(inputs_embeds, input_ids, imp_token_id, image_features,
     feats = image_features.to(device=dev, dtype=torch.bfloat16)
     if feats.dim() != 3 or feats.shape[-1] != C:
         raise RuntimeError(f"splice_visual_tokens: image_features must be [n_tiles, T, {C}], got {tuple(feats.shape)}")
-    feats = _lib.aligned(feats)   # (the entry point needs 16-byte aligned rows: views at another storage offset are copied)
     n_tiles, T = int(feats.shape[0]), int(feats.shape[1])
     tps = None
     if split_sizes is not None:
         if len(split_sizes) != B:
             raise RuntimeError("splice_visual_tokens: one split size per sample required")
         tps = (ctypes.c_int32 * B)(*[int(v) for v in split_sizes])   # host array: travels as a kernel argument
-    L_ = _lib.lib()
-    ws = torch.empty(int(L_.vllm_splice_workspace_ints(B, L, n_tiles)), dtype=torch.int32, device=dev)
-    embeds = _lib.aligned(inputs_embeds)   # written in place: a view at another storage offset is staged and copied back
-    with torch.cuda.device(dev):
-        _lib.check(L_.vllm_splice_visual_tokens_bf16(_lib.ptr(ids), int(imp_token_id), _lib.ptr(feats), tps, B, L, n_tiles, T, C,
-                                                     _lib.ptr(embeds), _lib.ptr(ws), None, _lib.current_stream(dev)),
-                   "vllm_splice_visual_tokens_bf16")
-    if embeds is not inputs_embeds:
-        inputs_embeds.copy_(embeds)
+    ws = torch.empty(int(_lib.lib().vllm_splice_workspace_ints(B, L, n_tiles)), dtype=torch.int32, device=dev)
+    if torch.is_grad_enabled() and (inputs_embeds.requires_grad or feats.requires_grad):
+        # training: the same call as an in-place autograd node (a leaf inputs_embeds that requires grad fails in torch, as the
+        # reference's index assignment does)
+        inputs_embeds = _SpliceVisualTokens.apply(inputs_embeds, feats, ids, int(imp_token_id), tps, ws)
+    else:
+        _splice_forward(inputs_embeds, feats, ids, int(imp_token_id), tps, ws)
     if check:
         _, n_vit, bad, n_sel = (int(v) for v in ws[:4].cpu())
         if bad:
@@ -58,6 +57,55 @@ def splice_visual_tokens(inputs_embeds, input_ids, imp_token_id, image_features,
     if return_status:
         return inputs_embeds, ws[:4]
     return inputs_embeds
+
+
+def _splice_forward(inputs_embeds, feats, ids, imp_token_id, tps, ws):
+    """The native call: ``inputs_embeds`` written in place, ``ws`` filled (header, slot list, kept tiles)."""
+    B, L, C = inputs_embeds.shape
+    n_tiles, T = int(feats.shape[0]), int(feats.shape[1])
+    dev = inputs_embeds.device
+    feats = _lib.aligned(feats)   # (the entry point needs 16-byte aligned rows: views at another storage offset are copied)
+    embeds = _lib.aligned(inputs_embeds)   # written in place: a view at another storage offset is staged and copied back
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().vllm_splice_visual_tokens_bf16(_lib.ptr(ids), imp_token_id, _lib.ptr(feats), tps, B, L, n_tiles, T, C,
+                                                             _lib.ptr(embeds), _lib.ptr(ws), None, _lib.current_stream(dev)),
+                   "vllm_splice_visual_tokens_bf16")
+    if embeds is not inputs_embeds:
+        inputs_embeds.copy_(embeds)
+
+
+class _SpliceVisualTokens(torch.autograd.Function):
+    """The splice as an in-place autograd node.  The forward is the inference call; the workspace it fills (slot list, kept tiles,
+    token-count rule) is all the backward needs: ONE native call on the current stream (``vllm_splice_visual_tokens_backward_bf16``),
+    no second scan of ``input_ids``, no host read.  The gradient of ``inputs_embeds`` is ``grad_out`` with the overwritten rows
+    zeroed; that of ``image_features`` gathers ``grad_out`` at the slots (summed in fp32 where the tokens were repeated), zero for
+    the tiles of samples without an image.  A gradient nobody needs is not computed (NULL: no traffic).  The node returns only the
+    embeddings (torch does not allow an in-place node on a view to have several outputs): the workspace, and with it the status
+    word, is the caller's tensor."""
+
+    @staticmethod
+    def forward(ctx, inputs_embeds, feats, ids, imp_token_id, tps, ws):
+        _splice_forward(inputs_embeds, feats, ids, imp_token_id, tps, ws)
+        ctx.mark_dirty(inputs_embeds)
+        ctx.save_for_backward(ws)
+        ctx.feats_shape = tuple(feats.shape)
+        return inputs_embeds
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        (ws,) = ctx.saved_tensors
+        n_tiles, T, C = ctx.feats_shape
+        B, L = grad_out.shape[0], grad_out.shape[1]
+        dev = grad_out.device
+        g = _lib.aligned(grad_out)
+        g_embeds = torch.empty_like(g) if ctx.needs_input_grad[0] else None          # (both are written completely by the call)
+        g_feats = torch.empty(ctx.feats_shape, dtype=g.dtype, device=dev) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(dev):
+            _lib.check(_lib.lib().vllm_splice_visual_tokens_backward_bf16(_lib.ptr(ws), _lib.ptr(g), B, L, n_tiles, T, C, _lib.ptr(g_embeds),
+                                                                          _lib.ptr(g_feats), _lib.current_stream(dev)),
+                       "vllm_splice_visual_tokens_backward_bf16")
+        return g_embeds, g_feats, None, None, None, None
 
 
 def splice_status_ok(status):
