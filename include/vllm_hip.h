@@ -412,6 +412,37 @@ int vllm_attn_fwd_qkvpacked_bf16(const uint16_t *qkv, uint16_t *out, int B, int 
 int vllm_attn_fwd_qkvpacked_f16(const uint16_t *qkv, uint16_t *out, int B, int S, int H, int D,
                                 float softmax_scale, vllm_stream_t stream);
 
+/* Training forward of B4 (the reference's flash_attn_varlen_qkvpacked_func is an autograd function, flash_attention.py:30-75): the
+ * same launch as vllm_attn_fwd_qkvpacked_* -- `out` is bit for bit what that call writes for the same qkv and attn_variant -- which
+ * also writes lse [B, H, S] fp32 (every element), the natural log of sum_j exp(softmax_scale q_i.k_j) as the kernel summed it (over
+ * the 16-bit-rounded probabilities, which is what `out` was normalised by and what the backward recomputes P from).
+ * Alignment: qkv 16 bytes, out 8 bytes, lse 4 bytes. */
+int vllm_attn_fwd_train_qkvpacked_bf16(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, int D,
+                                       float softmax_scale, vllm_stream_t stream);
+int vllm_attn_fwd_train_qkvpacked_f16(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, int D,
+                                      float softmax_scale, vllm_stream_t stream);
+/* Its backward (replaces the backward of flash_attn_varlen_qkvpacked_func and of InternAttention._naive_attn,
+ * modeling_intern_vit.py:136-140; dense, non-causal, dropout 0).  qkv, grad_qkv [B, S, 3, H, D]; out (as the training forward saved
+ * it), grad_out [B, S, H, D]; lse [B, H, S] fp32 from the training forward; all contiguous.  D in {64, 128}, any S >= 1, B = 0 accepted.
+ *   p_ij = exp(scale q_i.k_j - lse_i), delta_i = sum_d dO_id O_id, dV_j = sum_i p_ij dO_i, dS_ij = p_ij (dO_i.v_j - delta_i),
+ *   dQ_i = scale sum_j dS_ij k_j, dK_j = scale sum_i dS_ij q_i
+ * on the 32x32x16 MFMA: P and dS are rounded to the 16-bit type as MFMA operands only, accumulation is fp32, every gradient element is
+ * rounded once (IEEE half: P and dS enter the MFMA times 2^14 / 2^4, exact scales taken out again in fp32, so that very small
+ * probabilities are not rounded as half subnormals.  Range in half: the dS operand therefore reaches infinity at |dS| = |p (dO.v - delta)|
+ * > 4094 instead of 65504 -- under loss-scaled fp16 training a grad_out that large gives inf in grad_q / grad_k (which a loss scaler
+ * answers by lowering the scale); P <= 1 loses nothing, and bf16 has fp32's range).  Two kernels (dQ, which also leaves delta [B, H, S] fp32 in `workspace`, then dK / dV).
+ * Written: every element of grad_qkv (no zero-fill by the caller).  Deterministic: each element is owned by one wave and summed in a
+ * fixed order -- no atomics, no workgroup waits on another, the same bits on every run.  A refused call (VLLM_EINVAL) writes nothing.
+ * Alignment: qkv, out, grad_out, grad_qkv, workspace 16 bytes; lse 4 bytes.
+ * vllm_attn_bwd_workspace_bytes is host-only arithmetic; < 0 for an unsupported D. */
+long vllm_attn_bwd_workspace_bytes(int B, int S, int H, int D);
+int vllm_attn_bwd_qkvpacked_bf16(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *grad_out,
+                                 int B, int S, int H, int D, float softmax_scale, uint16_t *grad_qkv,
+                                 void *workspace, long workspace_bytes, vllm_stream_t stream);
+int vllm_attn_bwd_qkvpacked_f16(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *grad_out,
+                                int B, int S, int H, int D, float softmax_scale, uint16_t *grad_qkv,
+                                void *workspace, long workspace_bytes, vllm_stream_t stream);
+
 /* Patch gather for the embedding GEMM: pixels [N,3,img,img] (bf16, or fp32 when pixel_is_f32) ->
  * A [N*(img/patch)^2, Kpad] bf16, k = c*patch^2 + ky*patch + kx, zero padded to Kpad. */
 int vllm_im2col_patches(const void *pixels, int pixel_is_f32, uint16_t *A, int N, int img, int patch,

@@ -30,7 +30,9 @@ namespace vllm {
 // as WHOLE ROWS, 16 bytes per lane, 8 (d = 64) or 4 (d = 128) full rows per instruction.
 // (Rounds 2-5 carried three more schedule bits -- software-pipelined K, s_setprio around the MFMA clusters, hoisted asm
 //  transpose reads; each measured as fast or slower on both shapes, none was the default: removed in round 6, history keeps them.)
-template <int D, bool DEFER, bool F16 = false, int EPI = 0>
+// LSE (the training forward): also writes the row log-sum-exp the backward recomputes P from; the inference instantiations
+// (LSE = false) are the code they were.
+template <int D, bool DEFER, bool F16 = false, int EPI = 0, bool LSE = false>
 __global__ __launch_bounds__(ATT_THREADS, D == 64 ? 4 : 2) void attn_fwd_kernel(const AttnArgs a)
 {
     constexpr int KS = D / 16;            // k-steps of the QK^T product
@@ -252,6 +254,12 @@ __global__ __launch_bounds__(ATT_THREADS, D == 64 ? 4 : 2) void attn_fwd_kernel(
     // ---- finalize: O / l ; lane holds d = 32*db + 8*(r>>2) + 4*hh + (r&3) of query l31 ----
     const float l_tot = halves_sum(l_run);
     const float inv = 1.0f / l_tot;
+    if constexpr (LSE) {
+        // ln of the sum AS IT WAS TAKEN: l_run adds the 16-bit-rounded probabilities and m_run may lag the true maximum (deferred
+        // rescale); the backward's exp(s - lse) then reproduces exactly the P that was normalised here.
+        if (hh == 0 && q_row < a.S)
+            a.lse[((long)b * a.H + head) * a.S + q_row] = 0.6931471805599453f * (m_run + __builtin_amdgcn_logf(l_tot));
+    }
     if constexpr (EPI == 1) {
         // Rows through LDS.  The ring is dead once EVERY wave has left its last tile (one extra barrier per block); a wave then
         // uses only ITS 32 rows x D x 2 bytes of it: no further synchronisation.  Row pitch D * 2 bytes (128 / 256: a multiple of
@@ -297,7 +305,8 @@ __global__ __launch_bounds__(ATT_THREADS, D == 64 ? 4 : 2) void attn_fwd_kernel(
 template <int D, bool DEFER, bool F16, int EPI>
 static void attn_launch_one(const AttnArgs &a, unsigned grid, hipStream_t st)
 {
-    VLLM_LAUNCH((attn_fwd_kernel<D, DEFER, F16, EPI>), dim3(grid), dim3(ATT_THREADS), 4 * (size_t)KVBLK * D * 2, st, a);
+    if (a.lse) VLLM_LAUNCH((attn_fwd_kernel<D, DEFER, F16, EPI, true>), dim3(grid), dim3(ATT_THREADS), 4 * (size_t)KVBLK * D * 2, st, a);
+    else VLLM_LAUNCH((attn_fwd_kernel<D, DEFER, F16, EPI>), dim3(grid), dim3(ATT_THREADS), 4 * (size_t)KVBLK * D * 2, st, a);
 }
 
 int attn_fwd_launch(AttnArgs a, int D, hipStream_t st)
@@ -348,8 +357,8 @@ int attn_fwd_launch(AttnArgs a, int D, hipStream_t st)
 using namespace vllm;
 
 // B4: FlashAttention.forward(qkv[B,S,3,H,D]) -> out[B,S,H,D]   (flash_attention.py:30-75)
-extern "C" int vllm_attn_fwd_qkvpacked_bf16(const uint16_t *qkv, uint16_t *out, int B, int S, int H, int D,
-                                            float softmax_scale, vllm_stream_t stream)
+static int attn_fwd_qkvpacked(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, int D, float softmax_scale,
+                              bool f16, vllm_stream_t stream)
 {
     AttnArgs a;
     const long C = (long)H * D;
@@ -359,20 +368,34 @@ extern "C" int vllm_attn_fwd_qkvpacked_bf16(const uint16_t *qkv, uint16_t *out, 
     a.q_hs = a.k_hs = a.v_hs = D;
     a.B = B; a.S = S; a.H = H; a.nqt = 0;
     a.scale_log2e = softmax_scale * 1.4426950408889634f;
+    a.f16 = f16 ? 1 : 0;
+    a.lse = lse;
     return attn_fwd_launch(a, D, (hipStream_t)stream);
+}
+extern "C" int vllm_attn_fwd_qkvpacked_bf16(const uint16_t *qkv, uint16_t *out, int B, int S, int H, int D,
+                                            float softmax_scale, vllm_stream_t stream)
+{
+    return attn_fwd_qkvpacked(qkv, out, nullptr, B, S, H, D, softmax_scale, false, stream);
 }
 // The same for IEEE-half qkv (the reference's FlashAttention accepts fp16 and bf16, flash_attention.py:39-41).
 extern "C" int vllm_attn_fwd_qkvpacked_f16(const uint16_t *qkv, uint16_t *out, int B, int S, int H, int D,
                                            float softmax_scale, vllm_stream_t stream)
 {
-    AttnArgs a;
-    const long C = (long)H * D;
-    a.q = qkv; a.k = qkv ? qkv + C : nullptr; a.v = qkv ? qkv + 2 * C : nullptr; a.out = out;
-    a.q_bs = a.k_bs = a.v_bs = (long)S * 3 * C;
-    a.q_ts = a.k_ts = a.v_ts = (int)(3 * C);
-    a.q_hs = a.k_hs = a.v_hs = D;
-    a.B = B; a.S = S; a.H = H; a.nqt = 0;
-    a.scale_log2e = softmax_scale * 1.4426950408889634f;
-    a.f16 = 1;
-    return attn_fwd_launch(a, D, (hipStream_t)stream);
+    return attn_fwd_qkvpacked(qkv, out, nullptr, B, S, H, D, softmax_scale, true, stream);
+}
+// Training forward: the same launch (same schedule, same `out` bits) from the kernel instantiations that also write
+// lse[B, H, S] = ln sum_j exp(scale q_i.k_j), for vllm_attn_bwd_qkvpacked_*.
+extern "C" int vllm_attn_fwd_train_qkvpacked_bf16(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, int D,
+                                                  float softmax_scale, vllm_stream_t stream)
+{
+    VLLM_REQUIRE(lse || B == 0, "attn: null lse");
+    VLLM_REQUIRE((reinterpret_cast<uintptr_t>(lse) & 3u) == 0, "attn: lse must be 4-byte aligned");
+    return attn_fwd_qkvpacked(qkv, out, lse, B, S, H, D, softmax_scale, false, stream);
+}
+extern "C" int vllm_attn_fwd_train_qkvpacked_f16(const uint16_t *qkv, uint16_t *out, float *lse, int B, int S, int H, int D,
+                                                 float softmax_scale, vllm_stream_t stream)
+{
+    VLLM_REQUIRE(lse || B == 0, "attn: null lse");
+    VLLM_REQUIRE((reinterpret_cast<uintptr_t>(lse) & 3u) == 0, "attn: lse must be 4-byte aligned");
+    return attn_fwd_qkvpacked(qkv, out, lse, B, S, H, D, softmax_scale, true, stream);
 }

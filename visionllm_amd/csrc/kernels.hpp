@@ -177,8 +177,11 @@ struct AttnArgs {
     int no_trim;                // 1: process padding keys / padding query waves like live ones (A/B switch; launcher)
     float scale_log2e;
     int f16 = 0;                // 1: q / k / v / out are IEEE half (flash_attention.py:39-41 accepts fp16 and bf16); fp32 softmax either way
+    float *lse = nullptr;       // training forward only: [B, H, S] fp32 row log-sum-exp (the inference instantiations never read it)
 };
 int attn_fwd_launch(AttnArgs a, int D, hipStream_t st);
+int attn_bwd_launch(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *grad_out, int B, int S, int H, int D,
+                    float softmax_scale, uint16_t *grad_qkv, void *workspace, long workspace_bytes, bool f16, hipStream_t st);
 
 int im2col_launch(const void *pixels, int pixel_is_f32, uint16_t *A, int N, int img, int ps, int Kpad, hipStream_t st);
 int cls_rows_launch(const uint16_t *cls, const uint16_t *pos, uint16_t *hidden, int N, int S, int C, hipStream_t st);
