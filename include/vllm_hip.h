@@ -402,6 +402,30 @@ int vllm_layernorm_backward_bf16(const uint16_t *x, int ldx, const float *grad_y
                                  int C, uint16_t *grad_x, int ldgx, uint16_t *grad_w, uint16_t *grad_b, void *workspace,
                                  long workspace_bytes, vllm_stream_t stream);
 
+/* Backward of InternRMSNorm (modeling_intern_vit.py:33-44 under autograd; with G = 2 the q_norm / k_norm pair over the flattened H*D,
+ * :131-134, on the q and k blocks of a [rows, 3C] qkv slab in ONE launch, mirroring the forward's column groups).  x, grad_y, grad_x
+ * [rows, G*C] bf16 with row strides ldx / ldg / ldgx (elements); weight (and weight2 for group 1) [C].  Row statistics are recomputed
+ * in fp32:  xhat = x r, g = grad_y w, grad_x = r (g - xhat mean(g xhat)) [+ grad_res], rounded once;  grad_w = sum_rows grad_y xhat with
+ * the UNROUNDED fp32 xhat.  grad_res (bf16 [rows, C], row stride ldgr; G = 1 only; NULL = none) is the gradient of a residual branch
+ * that left the normalised tensor, added before the rounding.  grad_x may alias grad_y (columns beyond G*C are never touched: the v
+ * block of a qkv gradient stays as it is).  grad_x, grad_w, grad_w2 may each be NULL (not needed).  Column sums: per-block fp32
+ * partials in `workspace` (vllm_rmsnorm_backward_workspace_bytes(rows, C, G); host-only arithmetic, < 0 for unsupported sizes) and a
+ * fixed-order reduce -- no atomics, the same bits on every run.  C % 8 == 0, C <= 8192.  A refused call writes nothing. */
+/* Alignment: x, grad_y, grad_x, grad_res, weight, weight2 and workspace 16 bytes (row strides multiples of 8); grad_w, grad_w2 2 bytes. */
+long vllm_rmsnorm_backward_workspace_bytes(long rows, int C, int G);
+int vllm_rmsnorm_backward_bf16(const uint16_t *x, int ldx, const uint16_t *grad_y, int ldg, const uint16_t *weight,
+                               const uint16_t *weight2, int G, float eps, long rows, int C, uint16_t *grad_x, int ldgx,
+                               const uint16_t *grad_res, int ldgr, uint16_t *grad_w, uint16_t *grad_w2, void *workspace,
+                               long workspace_bytes, vllm_stream_t stream);
+/* Backward of LayerScale + residual, out = res + y * ls (modeling_intern_vit.py:206-208): grad_y = bf16(grad_out * ls) [rows, C] (row
+ * stride ldgy), grad_ls = sum_rows grad_out * y [C] (fp32 partials in `workspace` and a fixed-order reduce, as above); the residual's
+ * gradient is grad_out itself.  Either output may be NULL (y is only read for grad_ls, ls only for grad_y).  C % 8 == 0, C <= 8192. */
+/* Alignment: grad_out, y, ls, grad_y and workspace 16 bytes (row strides multiples of 8); grad_ls 2 bytes. */
+long vllm_layerscale_backward_workspace_bytes(long rows, int C);
+int vllm_layerscale_backward_bf16(const uint16_t *grad_out, int ldgo, const uint16_t *y, int ldy, const uint16_t *ls, long rows, int C,
+                                  uint16_t *grad_y, int ldgy, uint16_t *grad_ls, void *workspace, long workspace_bytes,
+                                  vllm_stream_t stream);
+
 /* B4: FlashAttention.forward(qkv[B,S,3,H,D]) -> out[B,S,H,D], non-causal, no mask, dropout 0
  * (visionllmv2/model/internvit/flash_attention.py:30-75).  D in {64,128}. */
 /* Alignment (both): qkv 16 bytes, out 8 bytes. */
@@ -616,6 +640,62 @@ int vllm_bridge_backward(const VllmBridgeDesc *desc, const uint16_t *x, long row
                          const uint16_t *const *saved_pre, const uint16_t *const *saved_act, const uint16_t *saved_ln,
                          uint16_t *grad_x, uint16_t *const *grad_w, uint16_t *const *grad_b, uint16_t *grad_ln_w, uint16_t *grad_ln_b,
                          void *workspace, long workspace_bytes, vllm_stream_t stream);
+
+/* Training one InternViT encoder layer (InternVisionEncoderLayer.forward, modeling_intern_vit.py:182-210: norm1 -> InternAttention
+ * :93-164 -> ls1 + residual -> norm2 -> InternMLP :167-179 -> ls2 + residual; the encoder runs it under torch.utils.checkpoint,
+ * :259-262, and the reference trains the tower with freeze_vis_encoder=False, visionllmv2/train/train.py:163, 534).  Dropout and
+ * drop-path are 0.  x, out, grad_out, grad_x [B, S, hidden] bf16, contiguous.  hidden % 64 == 0 (<= 8192), inter % 64 == 0, head_dim
+ * 64 or 128.  These structs are additions: VllmVitLayer / VllmVitDesc and vllm_abi_version are unchanged. */
+typedef struct VllmVitLayerTrain {
+    int hidden, heads, inter;
+    float eps;
+    const uint16_t *norm1_w;
+    const uint16_t *qkv_w, *qkv_b;          /* [3C, C], [3C] or NULL */
+    const uint16_t *q_norm_w, *k_norm_w;    /* [C] each, or both NULL (qk_normalization=False) */
+    const uint16_t *proj_w, *proj_b, *ls1;
+    const uint16_t *norm2_w;
+    const uint16_t *fc1_w, *fc1_b, *fc2_w, *fc2_b, *ls2;
+} VllmVitLayerTrain;
+/* What the training forward keeps for the backward (caller buffers, all written by the forward; M = B * S rows):
+ *   qkv [M, 3C] the qkv Linear's output BEFORE the QK-norm;  ctx [M, C] attention output;  lse [B, heads, S] fp32;
+ *   y1 [M, C] proj output before LayerScale;  x1 [M, C] the hidden state between the two blocks;  h1 / a1 [M, inter] fc1 output before /
+ *   after the GELU;  y2 [M, C] fc2 output before LayerScale  -- (10 C + 4 inter) M bytes + lse.
+ * Recomputed by the backward instead of saved, one norm launch each: norm1(x), norm2(x1), the post-norm q / k. */
+typedef struct VllmVitLayerSaved {
+    uint16_t *qkv, *ctx;
+    float *lse;
+    uint16_t *y1, *x1, *h1, *a1, *y2;
+} VllmVitLayerSaved;
+/* Parameter gradients (bf16, the parameters' shapes, overwritten -- the caller accumulates), in the layer's parameter order.  NULL =
+ * not needed: that product is skipped, and everything only it needed (a frozen parameter costs no weight-gradient GEMM).  A bias
+ * gradient comes out of its weight gradient's launch: it needs the weight's pointer too. */
+typedef struct VllmVitLayerGrads {
+    uint16_t *norm1_w, *qkv_w, *qkv_b, *q_norm_w, *k_norm_w, *proj_w, *proj_b, *ls1, *norm2_w, *fc1_w, *fc1_b, *fc2_w, *fc2_b, *ls2;
+} VllmVitLayerGrads;
+int vllm_vit_layer_train_sizeof(void);
+int vllm_vit_layer_saved_sizeof(void);
+int vllm_vit_layer_grads_sizeof(void);
+/* Training forward: the statement order of vllm_vit_forward where it does not fold norms (the same kernels; below 1024 rows `out` is
+ * bit for bit the inference encoder's next hidden state; from 1024 rows on the two residual GEMMs run one workgroup per tile, where the
+ * inference encoder may take the persistent schedule: the same value to within the last bf16 bit).  Backward: grad_out -> grad_x (NULL
+ * allowed) and the gradients named in `grads`; fp32 accumulation, every gradient element rounded once, run-to-run identical.
+ * workspace: vllm_vit_layer_backward_workspace_bytes(desc, B, S) bytes serve both calls (< 0 for a refused descriptor; host-only
+ * arithmetic).  Nothing is allocated, nothing synchronised; one stream.  A refused call (VLLM_EINVAL) writes nothing. */
+/* Alignment: x, out, grad_out, grad_x, every saved tensor and gradient, the descriptor's parameters and the workspace 16 bytes. */
+long vllm_vit_layer_backward_workspace_bytes(const VllmVitLayerTrain *desc, int B, int S);
+int vllm_vit_layer_forward_train(const VllmVitLayerTrain *desc, const uint16_t *x, int B, int S, uint16_t *out,
+                                 const VllmVitLayerSaved *saved, void *workspace, long workspace_bytes, vllm_stream_t stream);
+int vllm_vit_layer_backward(const VllmVitLayerTrain *desc, const uint16_t *x, int B, int S, const uint16_t *grad_out,
+                            const VllmVitLayerSaved *saved, uint16_t *grad_x, const VllmVitLayerGrads *grads, void *workspace,
+                            long workspace_bytes, vllm_stream_t stream);
+/* Building block of the training forward (tests; the LayerScale + residual statements modeling_intern_vit.py:206-208 behind proj :139 and
+ * fc2 :178): vllm_gemm_bf16 with VLLM_EPI_RESIDUAL -- Y is bit for bit what that call stores with
+ * VLLM_GEMM_FORCE_TILEWISE set (below the 8-phase kernel's size, simply what it stores) -- which also writes pre [M, N] (row stride ldy)
+ * = bf16(x W^T + b), the output before LayerScale and residual.  `epilogue` = VLLM_EPI_RESIDUAL | VLLM_GEMM_FORCE_* bits. */
+/* Alignment: X, W 16 bytes; Y, pre, res, bias, scale 8 bytes. */
+int vllm_gemm_bf16_residual_save(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, uint16_t *pre, int M, int N,
+                                 int K, int ldx, int ldw, int ldy, int epilogue, const uint16_t *scale, const uint16_t *res, int ldr,
+                                 vllm_stream_t stream);
 
 #ifdef __cplusplus
 }

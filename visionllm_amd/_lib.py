@@ -155,12 +155,30 @@ class VllmMsdaLayerDesc(ctypes.Structure):
                                   "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
 
 
+class VllmVitLayerTrain(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("hidden", "heads", "inter")] + [("eps", ctypes.c_float)] + \
+               [(n, _P) for n in ("norm1_w", "qkv_w", "qkv_b", "q_norm_w", "k_norm_w", "proj_w", "proj_b", "ls1", "norm2_w",
+                                  "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2")]
+
+
+class VllmVitLayerSaved(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ("qkv", "ctx", "lse", "y1", "x1", "h1", "a1", "y2")]
+
+
+class VllmVitLayerGrads(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ("norm1_w", "qkv_w", "qkv_b", "q_norm_w", "k_norm_w", "proj_w", "proj_b", "ls1", "norm2_w",
+                                  "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2")]
+
+
 def check_struct_layouts():
     L = lib()
     assert ctypes.sizeof(VllmMsdaLayerDesc) == L.vllm_msda_layer_desc_sizeof(), "VllmMsdaLayerDesc layout mismatch"
     assert ctypes.sizeof(VllmVitDesc) == L.vllm_vit_desc_sizeof(), "VllmVitDesc layout mismatch"
     assert ctypes.sizeof(VllmVitLayer) == L.vllm_vit_layer_sizeof(), "VllmVitLayer layout mismatch"
     assert ctypes.sizeof(VllmBridgeDesc) == L.vllm_bridge_desc_sizeof(), "VllmBridgeDesc layout mismatch"
+    assert ctypes.sizeof(VllmVitLayerTrain) == L.vllm_vit_layer_train_sizeof(), "VllmVitLayerTrain layout mismatch"
+    assert ctypes.sizeof(VllmVitLayerSaved) == L.vllm_vit_layer_saved_sizeof(), "VllmVitLayerSaved layout mismatch"
+    assert ctypes.sizeof(VllmVitLayerGrads) == L.vllm_vit_layer_grads_sizeof(), "VllmVitLayerGrads layout mismatch"
 
 
 EPI_BIAS, EPI_GELU, EPI_QUICK_GELU, EPI_RESIDUAL, EPI_EMBED, EPI_F32 = 0, 1, 2, 3, 4, 5

@@ -258,11 +258,11 @@ int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
     VLLM_REQUIRE(a.ldx % 8 == 0 && a.ldw % 8 == 0 && a.ldy % 4 == 0 && aligned16(a.X) && aligned16(a.W) &&
                      (reinterpret_cast<uintptr_t>(a.Y) & (epi == EPI_F32 || epi == EPI_MSDA ? 15u : 7u)) == 0,
                  "gemm: X and W must be 16-byte aligned, Y 8-byte aligned (16-byte for fp32 output), row strides multiples of 8 elements");
-    VLLM_REQUIRE(epi != EPI_RESIDUAL || (a.res && a.ldr % 4 == 0), "gemm: residual epilogue needs res");
+    VLLM_REQUIRE(!epi_is_residual(epi) || (a.res && a.ldr % 4 == 0), "gemm: residual epilogue needs res");
     VLLM_REQUIRE(epi != EPI_EMBED || (a.res && a.P > 0), "gemm: embed epilogue needs the position table and P");
     VLLM_REQUIRE(epi != EPI_GELU_BWD || (a.res && !a.bias && a.ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(a.res) & 7u) == 0),
                  "gemm: the GELU-backward epilogue needs the saved pre-activation `res` (8-byte aligned, ldr a multiple of 4) and no bias");
-    VLLM_REQUIRE(epi != EPI_GELU_SAVE || (a.pre && (reinterpret_cast<uintptr_t>(a.pre) & 7u) == 0),
+    VLLM_REQUIRE((epi != EPI_GELU_SAVE && epi != EPI_RESIDUAL_SAVE) || (a.pre && (reinterpret_cast<uintptr_t>(a.pre) & 7u) == 0),
                  "gemm: the training-forward epilogue needs an 8-byte aligned pre-activation output");
     // tall, skinny K = 256 problems (the linears of a deformable-attention layer): weight-stationary streaming kernel, bit-identical
     // to the 128 x 128 kernel below where both serve the shape (its EPI_MSDA form also takes L = 1 ... 3 levels, which the tile
@@ -307,6 +307,7 @@ int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
     case EPI_MSDA: L(EPI_MSDA); break;
     case EPI_GELU_BWD: L(EPI_GELU_BWD); break;
     case EPI_GELU_SAVE: L(EPI_GELU_SAVE); break;
+    case EPI_RESIDUAL_SAVE: L(EPI_RESIDUAL_SAVE); break;
     default: set_error("gemm: unknown epilogue %d", epi); return VLLM_EINVAL;
     }
 #undef L
@@ -332,6 +333,22 @@ extern "C" int vllm_gemm_bf16(const uint16_t *X, const uint16_t *W, const uint16
     if (((epilogue >> 8) & 3) == 3) { a.variant = 2; a.variant256 = 3; }   // VLLM_GEMM_FORCE_192
     else if (((epilogue >> 8) & 3) == 2) a.variant256 = 4;
     return gemm_bf16_launch(epilogue & 0xff, a, (hipStream_t)stream);
+}
+
+extern "C" int vllm_gemm_bf16_residual_save(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, uint16_t *pre, int M,
+                                            int N, int K, int ldx, int ldw, int ldy, int epilogue, const uint16_t *scale,
+                                            const uint16_t *res, int ldr, vllm_stream_t stream)
+{
+    VLLM_REQUIRE(X && W && Y && pre && res, "vllm_gemm_bf16_residual_save: null pointer");
+    VLLM_REQUIRE((epilogue & 0xff) == EPI_RESIDUAL, "vllm_gemm_bf16_residual_save: the epilogue is VLLM_EPI_RESIDUAL (plus VLLM_GEMM_FORCE_* bits)");
+    GemmArgs a;
+    a.X = X; a.W = W; a.Y = Y; a.bias = bias; a.scale = scale; a.res = res; a.pre = pre;
+    a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldr = ldr; a.P = 0; a.mt = a.nt = 0; a.xP = 0; a.variant = gemm_variant_override(); a.variant256 = 0; a.direct_store = gemm_direct_store();
+    if ((epilogue >> 8) & 3) a.variant = (epilogue >> 8) & 3;   // VLLM_GEMM_FORCE_* as vllm_gemm_bf16 reads them
+    if (epilogue & 0x800) a.variant = 4;
+    if (((epilogue >> 8) & 3) == 3) { a.variant = 2; a.variant256 = 3; }
+    else if (((epilogue >> 8) & 3) == 2) a.variant256 = 4;
+    return gemm_bf16_launch(EPI_RESIDUAL_SAVE, a, (hipStream_t)stream);
 }
 
 extern "C" int vllm_gemm_bf16_ln(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, int M, int N, int K, int ldx,

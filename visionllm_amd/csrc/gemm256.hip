@@ -188,7 +188,7 @@ __global__ __launch_bounds__(G2_THREADS, 1) void gemm256_bf16_kernel(const GemmA
 
     // Residual as accumulator init (below) with a LayerScale needs 1 / ls: every block checks ITS 256 columns (finite, |ls| >=
     // 1e-4: the division must not blow the fp32 accumulation up) and keeps the plain epilogue otherwise -- block-uniform.
-    if (EPI == EPI_RESIDUAL && al.res_init && al.scale) {
+    if (epi_is_residual(EPI) && al.res_init && al.scale) {
         const int t = tid_l;
         bool ok = true;
         if (t < G2_BN && n0 + t < al.N) {
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(G2_THREADS, 1) void gemm256_bf16_kernel(const GemmA
         // in front of the prologue the same 18-24 K).  Here the tile comes in row-wise instead -- LDS-DMA, 16 bytes per lane, 512
         // contiguous bytes per row, into the (still empty) ring, 16-byte chunk c of row r at chunk c ^ (r & 31) -- and the
         // lanes pick their elements up with conflict-free ds_read_b64.
-        if (EPI == EPI_RESIDUAL && a.res_init) {
+        if (epi_is_residual(EPI) && a.res_init) {
             constexpr int RROWS = 64 * MT;                       // rows of the block tile
 #pragma unroll
             for (int s = 0; s < RROWS / 16; ++s) {               // 8 waves x 2 rows x 512 B per round
@@ -801,7 +801,7 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
             a.ln_inv_cols = 1.f / cnt;
         }
     }
-    a.res_init = (epi == EPI_RESIDUAL && a.variant256 != 5 && !res_init_disabled() && a.N % 8 == 0 && a.N >= 8 &&
+    a.res_init = (epi_is_residual(epi) && a.variant256 != 5 && !res_init_disabled() && a.N % 8 == 0 && a.N >= 8 &&
                   a.ldr % 8 == 0 && aligned16(a.res)) ? 1 : 0;
     { static const int pf = [] { const char *e = getenv("VLLM_GEMM_PROF"); return e ? atoi(e) : 0; }(); a.prof = pf; }
     // VLLM_GEMM_TRACE names a raw device address every block writes 24 bytes to: debug builds only (-DVLLM_GEMM_TRACE_ENABLE,
@@ -879,6 +879,8 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
         GemmArgs b = a;
         b.sk_tiles = 0;
         b.mt = ceil_div(a.M, 64 * pmt);
+        // (the training forward's residual GEMM, EPI_RESIDUAL_SAVE, has no persistent form: one workgroup per tile, with every other
+        //  decision -- tile height, stream-K tail, residual as initial value -- taken as for EPI_RESIDUAL with VLLM_GEMM_FORCE_TILEWISE)
         if (gemm256p_takes(epi, b, cus)) return a.dry_run ? VLLM_OK : gemm256p_launch(epi, pmt, b, cus, st);
         // the training forward's GELU GEMM (EPI_GELU_SAVE) must give the bits of the inference forward's EPI_GELU: where the persistent
         // schedule takes that one, one workgroup per tile WITHOUT a stream-K tail does (same MFMA sequence per tile, same epilogue
@@ -912,7 +914,7 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256_bf16_kernel<E, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256_bf16_kernel<E, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
         SETATTR(EPI_BIAS); SETATTR(EPI_GELU); SETATTR(EPI_QUICK_GELU); SETATTR(EPI_RESIDUAL); SETATTR(EPI_EMBED); SETATTR(EPI_F32);
-        SETATTR(EPI_GELU_BWD); SETATTR(EPI_GELU_SAVE);
+        SETATTR(EPI_GELU_BWD); SETATTR(EPI_GELU_SAVE); SETATTR(EPI_RESIDUAL_SAVE);
 #undef SETATTR
     }
 #define L(E) do { if (mf32) VLLM_LAUNCH((gemm256_bf16_kernel<E, 4, true>), grid, block, lds, st, a); \
@@ -936,6 +938,7 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
     case EPI_F32: L(EPI_F32); break;
     case EPI_GELU_BWD: L(EPI_GELU_BWD); break;
     case EPI_GELU_SAVE: L(EPI_GELU_SAVE); break;
+    case EPI_RESIDUAL_SAVE: L(EPI_RESIDUAL_SAVE); break;
     default: set_error("gemm256: unknown epilogue %d", epi); return VLLM_EINVAL;
     }
 #undef L

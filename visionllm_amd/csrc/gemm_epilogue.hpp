@@ -49,7 +49,7 @@ __device__ __forceinline__ EpiCols epi_cols(const GemmArgs &a, int n)
         const uint2_t b = *reinterpret_cast<const uint2_t *>(bias + n);
         c.bia[0] = bf16lo_to_f32(b.x); c.bia[1] = bf16hi_to_f32(b.x); c.bia[2] = bf16lo_to_f32(b.y); c.bia[3] = bf16hi_to_f32(b.y);
     }
-    if (EPI == EPI_RESIDUAL && a.scale) {
+    if (epi_is_residual(EPI) && a.scale) {
         const uint2_t s = *reinterpret_cast<const uint2_t *>(a.scale + n);
         c.scl[0] = bf16lo_to_f32(s.x); c.scl[1] = bf16hi_to_f32(s.x); c.scl[2] = bf16lo_to_f32(s.y); c.scl[3] = bf16hi_to_f32(s.y);
     }
@@ -86,12 +86,24 @@ __device__ __forceinline__ void epi_value(const GemmArgs &a, int m, int n, const
 #pragma unroll
         for (int r = 0; r < 4; ++r)
             v[r] = v[r] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(fmaf(acc[r], kq, c.bia[r] * kq)));
-    } else if (EPI == EPI_RESIDUAL && a.res_init) {
+    } else if (epi_is_residual(EPI) && a.res_init) {
         // the residual went in as the accumulators' initial value (gemm256), divided by the LayerScale where there is one:
         // (res / ls + X W^T + bias) * ls = res + (X W^T + bias) * ls   (scl = 1 without LayerScale)
+        if (EPI == EPI_RESIDUAL_SAVE) {
+            // training forward: the pre-LayerScale output X W^T + bias leaves too.  The accumulators carry res * (1 / ls) on top of it
+            // (the same product, formed the same way, that gemm256 started them from): taken off again, at a cost of 2^-24 |res / ls|
+            const uint2_t rr = *reinterpret_cast<const uint2_t *>(a.res + (size_t)m * a.ldr + n);
+            const float rf[4] = {bf16lo_to_f32(rr.x), bf16hi_to_f32(rr.x), bf16lo_to_f32(rr.y), bf16hi_to_f32(rr.y)};
+            float p[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) p[r] = v[r] - rf[r] * (a.scale ? __builtin_amdgcn_rcpf(c.scl[r]) : 1.f);
+            *reinterpret_cast<uint2_t *>(a.pre + (size_t)m * a.ldy + n) = (uint2_t){pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3])};
+        }
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] *= c.scl[r];
-    } else if (EPI == EPI_RESIDUAL) {
+    } else if (epi_is_residual(EPI)) {
+        if (EPI == EPI_RESIDUAL_SAVE)
+            *reinterpret_cast<uint2_t *>(a.pre + (size_t)m * a.ldy + n) = (uint2_t){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
         const uint2_t rr = *reinterpret_cast<const uint2_t *>(a.res + (size_t)m * a.ldr + n);
         v[0] = bf16lo_to_f32(rr.x) + v[0] * c.scl[0]; v[1] = bf16hi_to_f32(rr.x) + v[1] * c.scl[1];
         v[2] = bf16lo_to_f32(rr.y) + v[2] * c.scl[2]; v[3] = bf16hi_to_f32(rr.y) + v[3] * c.scl[3];

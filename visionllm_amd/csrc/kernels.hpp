@@ -14,7 +14,10 @@ enum GemmEpilogue : int {
     EPI_GELU_BWD = VLLM_EPI_GELU_BWD,
     EPI_MSDA = 100,   // internal (msda_layer.hip): offsets -> sampling locations, logits -> softmax weights, both fp32
     EPI_GELU_SAVE = 101,   // internal (bridge_train.cpp): EPI_GELU that also stores the pre-activation to GemmArgs::pre
+    EPI_RESIDUAL_SAVE = 102,   // internal (vit_train.cpp): EPI_RESIDUAL that also stores bf16(x W^T + b), the pre-LayerScale output, to GemmArgs::pre
 };
+// the residual epilogue and its training form share every schedule decision and the arithmetic of Y
+constexpr bool epi_is_residual(int epi) { return epi == EPI_RESIDUAL || epi == EPI_RESIDUAL_SAVE; }
 
 struct GemmArgs {
     const uint16_t *X;      // [M, K] row stride ldx
@@ -74,7 +77,7 @@ struct GemmArgs {
     int tile_rb = 0;                // persistent schedule, tile order: 0 = the dense XCD order of gemm256.hip; RB > 0 = banded (launcher)
     unsigned long long *trace = nullptr;   // VLLM_GEMM_TRACE=<device address of 3 x 8192 uint64>: per block {start, end} in
                                            // 100 MHz s_memrealtime ticks + HW_ID (which CU), for tools/prof_gemm256.py
-    uint16_t *pre = nullptr;   // EPI_GELU_SAVE: [M, N] bf16 pre-activation, row stride ldy (8-byte aligned)
+    uint16_t *pre = nullptr;   // EPI_GELU_SAVE / EPI_RESIDUAL_SAVE: [M, N] bf16 pre-activation / pre-LayerScale output, row stride ldy (8-byte aligned)
 };
 
 int gemm_direct_store();       // VLLM_GEMM_DIRECT_STORE / vllm_set_option("gemm_direct_store")
@@ -112,6 +115,15 @@ int transpose_bf16_launch(const uint16_t *w, int ldw, uint16_t *wt, int ldt, int
 long ln_bwd_workspace_bytes(long rows, int C);
 int ln_bwd_launch(const uint16_t *x, int ldx, const float *dz, int ldz, const uint16_t *gamma, float eps, long rows, int C,
                   uint16_t *dx, int lddx, uint16_t *grad_w, uint16_t *grad_b, void *ws, long ws_bytes, hipStream_t st);
+
+// InternViT layer backward, row-wise pieces (norm.hip; orchestrated by vit_train.cpp)
+long rms_bwd_workspace_bytes(long rows, int C, int G);
+int rms_bwd_launch(const uint16_t *x, int ldx, const uint16_t *gy, int ldgy, const uint16_t *w, const uint16_t *w2, int G, float eps, long rows,
+                   int C, uint16_t *gx, int ldgx, const uint16_t *gres, int ldgr, uint16_t *gw, uint16_t *gw2, void *ws, long ws_bytes,
+                   hipStream_t st);
+long ls_bwd_workspace_bytes(long rows, int C);
+int ls_bwd_launch(const uint16_t *go, int ldgo, const uint16_t *y, int ldy, const uint16_t *ls, long rows, int C, uint16_t *gy, int ldgy,
+                  uint16_t *gls, void *ws, long ws_bytes, hipStream_t st);
 
 // In-step kernel timing (vllm_prof_enable / vllm_prof_read): when enabled, the orchestrators record a HIP event in front of
 // every operator they enqueue; the time from one mark to the next is attributed to the first one's tag, so a kernel is

@@ -5,9 +5,17 @@ VisionLLMv2/visionllmv2/model/internvit/modeling_intern_vit.py (:61-90 embedding
 :182-210 layer, :213-276 encoder, :279-343 model) so HF state-dicts load unchanged
 (``embeddings.{class_embedding,patch_embedding.weight/bias,position_embedding}``,
 ``encoder.layers.{i}.{attn.qkv.weight, attn.q_norm.weight, attn.k_norm.weight, attn.proj.*, mlp.fc1/fc2.*,
-norm1/norm2.weight, ls1, ls2}``).  The modules below only HOLD the parameters; ``forward`` hands their device
-pointers to ``vllm_vit_forward`` (one C call for the whole encoder; hand-written HIP kernels underneath).
-Inference only (the reference runs the tower under ``torch.no_grad()``, modeling_visionllmv2.py:560).
+norm1/norm2.weight, ls1, ls2}``).
+
+Inference: ``InternVisionModel.forward`` hands every parameter's device pointer to ``vllm_vit_forward`` (one C call for the whole
+encoder under ``torch.no_grad()``, as the reference runs the frozen tower, modeling_visionllmv2.py:560).
+
+Training (``freeze_vis_encoder=False``, train/train.py:163, 534): ``InternVisionEncoder.forward(inputs_embeds)`` runs the layers as the
+reference does (:232-276, each under ``torch.utils.checkpoint`` when ``gradient_checkpointing and self.training``), and
+``InternVisionEncoderLayer.forward`` is ONE autograd node around ``vllm_vit_layer_forward_train`` / ``vllm_vit_layer_backward``
+(hand-written HIP underneath; dropout and drop-path are not implemented and raise in training mode).  ``InternRMSNorm.forward`` has
+its own node (``vllm_rmsnorm_backward_bf16``).  Gradients do not reach the embeddings: ``InternVisionModel.forward`` stays
+inference-only.
 """
 import ctypes
 
@@ -68,6 +76,10 @@ class InternRMSNorm(nn.Module):
     def forward(self, hidden_states):
         x = hidden_states
         _require_bf16_cuda("hidden_states", x)
+        if torch.is_grad_enabled() and (x.requires_grad or self.weight.requires_grad):
+            _require_bf16_cuda("weight", self.weight)
+            x2 = _lib.aligned(x.reshape(-1, x.shape[-1]))   # (differentiable: a view at another offset is copied by autograd ops)
+            return _RMSNormTrain.apply(x2, _lib.aligned(self.weight), self.variance_epsilon).view_as(x)
         x2 = _lib.aligned(x.reshape(-1, x.shape[-1]))   # (16-byte aligned rows and weight: views at another offset are copied)
         w = _lib.aligned(self.weight.detach())
         y = torch.empty_like(x2)
@@ -76,6 +88,39 @@ class InternRMSNorm(nn.Module):
                                                     x2.shape[1], x2.shape[0], x2.shape[1], self.variance_epsilon,
                                                     _lib.current_stream(x.device)), "vllm_rmsnorm_bf16")
         return y.view_as(x)
+
+
+class _RMSNormTrain(torch.autograd.Function):
+    """InternRMSNorm as one autograd node: vllm_rmsnorm_bf16 forward (the no-grad call's bits), vllm_rmsnorm_backward_bf16 backward.
+    x [rows, C] and weight [C], both 16-byte aligned; saved with save_for_backward (an in-place edit fails the version check)."""
+
+    @staticmethod
+    def forward(ctx, x, w, eps):
+        y = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().vllm_rmsnorm_bf16(_lib.ptr(x), x.shape[1], _lib.ptr(w), _lib.ptr(y), x.shape[1], x.shape[0], x.shape[1],
+                                                    eps, _lib.current_stream(x.device)), "vllm_rmsnorm_bf16")
+        ctx.eps = eps
+        ctx.save_for_backward(x, w)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w = ctx.saved_tensors
+        rows, C = x.shape
+        g = _lib.aligned(gy.to(torch.bfloat16))
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gx = torch.empty_like(x) if need_x else None
+        gw = torch.empty_like(w) if need_w else None
+        L = _lib.lib()
+        with torch.cuda.device(x.device):
+            wsb = L.vllm_rmsnorm_backward_workspace_bytes(rows, C, 1)
+            _lib.check(0 if wsb >= 0 else -1, "vllm_rmsnorm_backward_workspace_bytes")
+            ws = _lib.workspace(x.device, max(wsb, 1))
+            _lib.check(L.vllm_rmsnorm_backward_bf16(_lib.ptr(x), C, _lib.ptr(g), C, _lib.ptr(w), None, 1, ctx.eps, rows, C, _lib.ptr(gx), C,
+                                                    None, 0, _lib.ptr(gw), None, _lib.ptr(ws), wsb, _lib.current_stream(x.device)),
+                       "vllm_rmsnorm_backward_bf16")
+        return gx, gw, None
 
 
 class InternVisionEmbeddings(nn.Module):
@@ -117,24 +162,171 @@ class InternMLP(nn.Module):
         self.fc2 = nn.Linear(config.intermediate_size, config.hidden_size)
 
 
+_LAYER_PARAMS = ("norm1_w", "qkv_w", "qkv_b", "q_norm_w", "k_norm_w", "proj_w", "proj_b", "ls1", "norm2_w", "fc1_w", "fc1_b", "fc2_w",
+                 "fc2_b", "ls2")   # the order of VllmVitLayerTrain / VllmVitLayerGrads
+_SAVED = ("qkv", "ctx", "lse", "y1", "x1", "h1", "a1", "y2")   # VllmVitLayerSaved
+
+
+def _layer_desc(meta, params, keep):
+    heads, inter, eps = meta
+    fields = {}
+    for name, t in zip(_LAYER_PARAMS, params):
+        if t is None:
+            fields[name] = None
+            continue
+        _require_bf16_cuda(name, t)
+        a = _lib.aligned(t.detach())
+        keep.append(a)
+        fields[name] = a.data_ptr()
+    return _lib.VllmVitLayerTrain(hidden=params[0].shape[0], heads=heads, inter=inter, eps=eps, **fields)
+
+
+def _layer_forward(meta, x, params, want_saved):
+    """vllm_vit_layer_forward_train on x [B, S, C] (16-byte aligned) -> (out, the saved tensors in _SAVED order or None)."""
+    keep = []
+    d = _layer_desc(meta, params, keep)
+    B, S, C = x.shape
+    heads, inter, _ = meta
+    dev, M = x.device, B * S
+    L = _lib.lib()
+    _lib.check_struct_layouts()
+    bf = dict(dtype=torch.bfloat16, device=dev)
+    out = torch.empty((B, S, C), **bf)
+    saved = [torch.empty((M, 3 * C), **bf), torch.empty((M, C), **bf), torch.empty((B, heads, S), dtype=torch.float32, device=dev),
+             torch.empty((M, C), **bf), torch.empty((M, C), **bf), torch.empty((M, inter), **bf), torch.empty((M, inter), **bf),
+             torch.empty((M, C), **bf)]
+    sv = _lib.VllmVitLayerSaved(**{n: t.data_ptr() for n, t in zip(_SAVED, saved)})
+    with torch.cuda.device(dev):
+        wsb = L.vllm_vit_layer_backward_workspace_bytes(ctypes.byref(d), B, S)
+        _lib.check(0 if wsb >= 0 else -1, "vllm_vit_layer_backward_workspace_bytes")
+        ws = _lib.workspace(dev, max(wsb, 1))
+        _lib.check(L.vllm_vit_layer_forward_train(ctypes.byref(d), _lib.ptr(x), B, S, _lib.ptr(out), ctypes.byref(sv), _lib.ptr(ws), wsb,
+                                                  _lib.current_stream(dev)), "vllm_vit_layer_forward_train")
+    return out, (saved if want_saved else None)
+
+
+class _VitLayerTrain(torch.autograd.Function):
+    """One InternViT encoder layer as one autograd node.  Inputs: x [B, S, C] (16-byte aligned) and the parameters in _LAYER_PARAMS
+    order (a missing one is None).  Parameters and the kept activations go through save_for_backward, so an in-place update
+    between forward and backward fails autograd's version check instead of producing wrong gradients."""
+
+    @staticmethod
+    def forward(ctx, meta, x, *params):
+        out, saved = _layer_forward(meta, x, params, True)
+        ctx.meta = meta
+        ctx.save_for_backward(x, *saved, *params)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        meta = ctx.meta
+        t = ctx.saved_tensors
+        x, saved, params = t[0], t[1:1 + len(_SAVED)], t[1 + len(_SAVED):]
+        keep = []
+        d = _layer_desc(meta, params, keep)
+        B, S, C = x.shape
+        dev = x.device
+        need = list(ctx.needs_input_grad[2:])
+        need_x = ctx.needs_input_grad[1]
+        idx = {n: i for i, n in enumerate(_LAYER_PARAMS)}
+        for b, w in (("qkv_b", "qkv_w"), ("proj_b", "proj_w"), ("fc1_b", "fc1_w"), ("fc2_b", "fc2_w")):   # a bias gradient rides on its weight's launch
+            ask_w = need[idx[b]] and params[idx[b]] is not None
+            need[idx[w]] = need[idx[w]] or ask_w
+        g = _lib.aligned(gout.to(torch.bfloat16))
+        grads = [torch.empty(p.shape, dtype=torch.bfloat16, device=dev) if (n and p is not None) else None for n, p in zip(need, params)]
+        gx = torch.empty_like(x) if need_x else None
+        gs = _lib.VllmVitLayerGrads(**{n: (t_.data_ptr() if t_ is not None else None) for n, t_ in zip(_LAYER_PARAMS, grads)})
+        sv = _lib.VllmVitLayerSaved(**{n: t_.data_ptr() for n, t_ in zip(_SAVED, saved)})
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            wsb = L.vllm_vit_layer_backward_workspace_bytes(ctypes.byref(d), B, S)
+            _lib.check(0 if wsb >= 0 else -1, "vllm_vit_layer_backward_workspace_bytes")
+            ws = _lib.workspace(dev, max(wsb, 1))
+            _lib.check(L.vllm_vit_layer_backward(ctypes.byref(d), _lib.ptr(x), B, S, _lib.ptr(g), ctypes.byref(sv), _lib.ptr(gx),
+                                                 ctypes.byref(gs), _lib.ptr(ws), wsb, _lib.current_stream(dev)), "vllm_vit_layer_backward")
+        out = [t_ if n else None for t_, n in zip(grads, ctx.needs_input_grad[2:])]   # (a weight gradient computed only for its bias is dropped)
+        return (None, gx) + tuple(out)
+
+
 class InternVisionEncoderLayer(nn.Module):
     def __init__(self, config, drop_path_rate=0.0):
         super().__init__()
         self.embed_dim = config.hidden_size
+        self.intermediate_size = config.intermediate_size
         self.attn = InternAttention(config)
         self.mlp = InternMLP(config)
         self.norm1 = InternRMSNorm(self.embed_dim, eps=config.layer_norm_eps)
         self.norm2 = InternRMSNorm(self.embed_dim, eps=config.layer_norm_eps)
         self.ls1 = nn.Parameter(config.initializer_factor * torch.ones(self.embed_dim))
         self.ls2 = nn.Parameter(config.initializer_factor * torch.ones(self.embed_dim))
+        # (modeling_intern_vit.py:193-194, 111-112: DropPath / nn.Dropout modules hold no parameters; the rates are kept to refuse them)
+        self.drop_path_rate = float(drop_path_rate)
+        self._dropout = max(float(getattr(config, "dropout", 0.0) or 0.0), float(getattr(config, "attention_dropout", 0.0) or 0.0))
+        self._eps = config.layer_norm_eps
+        if getattr(config, "hidden_act", "gelu") != "gelu":
+            raise NotImplementedError(f"hidden_act {config.hidden_act!r}: the fused epilogue implements 'gelu' (erf)")
+
+    def _params(self):
+        a, m = self.attn, self.mlp
+        qn = a.q_norm.weight if a.qk_normalization else None
+        kn = a.k_norm.weight if a.qk_normalization else None
+        return (self.norm1.weight, a.qkv.weight, a.qkv.bias, qn, kn, a.proj.weight, a.proj.bias, self.ls1, self.norm2.weight,
+                m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias, self.ls2)
+
+    def forward(self, hidden_states):
+        """modeling_intern_vit.py:196-210 on a bf16 CUDA [B, S, C] tensor: vllm_vit_layer_forward_train, as one autograd node when
+        anything in it requires grad (same output bits either way)."""
+        x = hidden_states
+        if self.training and (self.drop_path_rate > 0.0 or self._dropout > 0.0):
+            raise NotImplementedError("InternVisionEncoderLayer (native): dropout / attention_dropout / drop_path_rate > 0 are not "
+                                      "implemented for training; set them to 0 (the released configs do) or call .eval()")
+        _require_bf16_cuda("hidden_states", x)
+        if x.dim() != 3 or x.shape[-1] != self.embed_dim:
+            raise ValueError(f"hidden_states must be [batch, seq_len, {self.embed_dim}], got {tuple(x.shape)}")
+        params = self._params()
+        meta = (self.attn.num_heads, self.intermediate_size, self._eps)
+        x = _lib.aligned(x)   # (16-byte aligned rows: a view at another storage offset is copied -- differentiably)
+        if torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params)):
+            return _VitLayerTrain.apply(meta, x, *params)
+        return _layer_forward(meta, x.detach(), params, False)[0]
 
 
 class InternVisionEncoder(nn.Module):
     def __init__(self, config):
         super().__init__()
         self.config = config
-        self.layers = nn.ModuleList([InternVisionEncoderLayer(config) for _ in range(config.num_hidden_layers)])
+        n = config.num_hidden_layers
+        # stochastic depth decay rule (modeling_intern_vit.py:226-229)
+        dpr = [x.item() for x in torch.linspace(0, float(getattr(config, "drop_path_rate", 0.0) or 0.0), n)]
+        self.layers = nn.ModuleList([InternVisionEncoderLayer(config, dpr[i]) for i in range(n)])
         self.gradient_checkpointing = True
+
+    def forward(self, inputs_embeds, output_hidden_states=None, return_dict=None):
+        """modeling_intern_vit.py:232-276: the training entry (gradients flow to ``inputs_embeds`` and every layer parameter)."""
+        import torch.utils.checkpoint
+        cfg = self.config
+        output_hidden_states = output_hidden_states if output_hidden_states is not None else getattr(cfg, "output_hidden_states", False)
+        return_dict = return_dict if return_dict is not None else getattr(cfg, "use_return_dict", True)
+        encoder_states = () if output_hidden_states else None
+        hidden_states = inputs_embeds
+        for layer in self.layers:
+            if output_hidden_states:
+                encoder_states = encoder_states + (hidden_states,)
+            if self.gradient_checkpointing and self.training:
+                # (non-reentrant: the layer's parameters get their gradients even when inputs_embeds itself does not require grad)
+                hidden_states = torch.utils.checkpoint.checkpoint(layer, hidden_states, use_reentrant=False)
+            else:
+                hidden_states = layer(hidden_states)
+        if output_hidden_states:
+            encoder_states = encoder_states + (hidden_states,)
+        if not return_dict:
+            return tuple(v for v in [hidden_states, encoder_states] if v is not None)
+        try:
+            from transformers.modeling_outputs import BaseModelOutput
+            return BaseModelOutput(last_hidden_state=hidden_states, hidden_states=encoder_states)
+        except Exception:  # transformers not importable: a minimal stand-in with the attributes the caller reads
+            from types import SimpleNamespace
+            return SimpleNamespace(last_hidden_state=hidden_states, hidden_states=encoder_states)
 
 
 class InternVisionModel(nn.Module):
