@@ -76,6 +76,9 @@ int vllm_device_info(char *name, int cap);
  * "gemm_half_tail" (round 4; VLLM_GEMM_HALF_TAIL): 1 (default) the persistent 8-phase GEMM runs the tiles of its last, incomplete round
  * as two half-height tiles each when they then still fit the grid (qkv at 40 ViT-L tiles: 4.27 rounds of work in 5 -> 4 + a half-tile
  * round); 0 whole tiles.  The same bits either way.
+ * "gemm_res_ring" (VLLM_GEMM_RES_RING): 1 (default) the persistent 8-phase GEMM with VLLM_EPI_RESIDUAL and no `scale` takes the residual
+ * tile through its operand ring and adds it on the matrix pipe (see VLLM_EPI_RESIDUAL below for the contract); 0 the epilogue reads it.
+ * The two differ in the fp32 order of the same three terms (bf16 results differ at ties only).
  * "msda_layer_value_bf16" (round 4; VLLM_MSDA_LAYER_VALUE_BF16): 1 (default) vllm_msda_layer_forward stores the projected value in
  * bf16 when the query set is not the value pyramid (decoder cross-attention: the gather kernel reads bf16 natively; the reference's
  * bf16 module rounds the value to bf16 too) and the streaming value GEMM serves the shape; 0 fp32 value everywhere.
@@ -311,6 +314,11 @@ int vllm_point_sample_backward_f32(const float *coords, const float *grad_out /*
 #define VLLM_EPI_GELU 1        /* y = gelu_erf(x W^T + b)                         (InternMLP.fc1+act, vl_bridge GELU) */
 #define VLLM_EPI_QUICK_GELU 2  /* y = z*sigmoid(1.702 z)                          (CLIP MLP) */
 #define VLLM_EPI_RESIDUAL 3    /* y = res + (x W^T + b) * scale                   (LayerScale + residual, modeling_intern_vit.py:206-208) */
+/* VLLM_EPI_RESIDUAL without `scale` on the persistent 8-phase GEMM ("gemm_res_ring", the default): the residual is added by the matrix
+ * pipe as res x I, y = (x W^T + res) + b with one rounding.  0 x Inf is NaN there: a NON-FINITE residual element makes every output of
+ * its row's aligned 32-column group [32 g, min(32 g + 32, N)) NaN instead of that element alone (finite residuals: exact; nothing
+ * beyond column N of a row is read).  With `scale`, with ldr not a multiple of 8, on every other kernel and with "gemm_res_ring" 0
+ * a non-finite element stays in its own output. */
 #define VLLM_EPI_EMBED 4       /* patch embedding: rows scattered past the CLS slot, + position embedding */
 #define VLLM_EPI_F32 5         /* y = x W^T + b kept in fp32: Y is float*, ldy in floats (16-byte aligned rows); `res`, if
                                 * given, is a uint8 row mask [M]: masked rows are written as zeros (the key-padding

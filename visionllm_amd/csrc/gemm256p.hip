@@ -15,8 +15,9 @@
 //     (4 registers in all), the tile / K-tile part is scalar -- nothing per-lane changes from tile to tile;
 //   * K tile 0 of a tile takes the MFMA's constant-zero accumulator; the two staggered wave groups are level around the epilogue.
 // The per-tile column vectors (bias, LayerScale; for the consumer of a folded norm the column sums, bias' and the rows'
-// statistics) come in by LDS-DMA one tile ahead into double-buffered LDS behind the ring.  The residual epilogue reads the
-// residual tile in the store layout with inline buffer loads and can produce a folded norm's row statistics (STATS).
+// statistics) come in by LDS-DMA one tile ahead into double-buffered LDS behind the ring.  The residual epilogue can produce a
+// folded norm's row statistics (STATS); its residual tile comes in through the operand ring as two virtual K tiles (no LayerScale:
+// RING, below) or is read by the epilogue in the store layout with inline buffer loads (LayerScale; "gemm_res_ring" 0).
 //
 // Scope: bias / GELU / quick-GELU / residual epilogues (qkv, fc1, proj, fc2 and the projector linears), N a multiple of 8, at
 // least as many tiles as CUs, no CLS-skipping loader; the launcher in gemm256.hip asks for this schedule before it considers a
@@ -99,18 +100,30 @@ __device__ __forceinline__ void store_piece(u32x4_t &o, __amdgpu_buffer_rsrc_t r
 // HALFT: the instantiation that can run the last round as half-height tiles (see the tile loop).  A separate instantiation because
 // the second K loop costs the whole-tile loop registers (210 -> 237 VGPRs, 4 -> 33 spilled SGPRs) and 2 % of its speed (fc1, same box:
 // 169 -> 173 us): launches whose last round stays whole keep the kernel they had.
-template <int EPI, int MT, bool LNC, int STATS = 0, bool HALFT = false>   // STATS: 0 none, 1 {mean, M2} pairs per (row, tile), 2 wide (RMSNorm: one float per (row, tile), ragged last tile allowed)
+// RING (residual epilogue without LayerScale): the residual tile comes in through the operand ring as two more "K tiles" of the
+// output tile and is added by the matrix pipe -- res + X W^T = [X | res] [W | I]^T, a bf16 value times bf16 1.0 is exact in the fp32
+// accumulator.  Virtual K tile v (0 / 1) carries the residual columns n0 + 128 v .. + 127 of the tile's rows, split over the stage's
+// four half-tile slots (A0 / A1: row half 0 / 1, first 64 columns; B0 / B1: row half 0 / 1, second 64 columns), ALL filled with the
+// A-side lane pattern, in the four phases and with the instruction counts of a normal K tile's refills: every counted wait of the
+// main loop keeps its meaning, no register load is in flight anywhere, the epilogue is the plain one (+ the statistics).
+// The route is the epilogue value EPI_ = EPI_RESIDUAL_RING (kernels.hpp says why it is a value and not a flag).
+template <int EPI_, int MT, bool LNC, int STATS = 0, bool HALFT = false>   // STATS: 0 none, 1 {mean, M2} pairs per (row, tile), 2 wide (RMSNorm: one float per (row, tile), ragged last tile allowed)
 __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a)
 {
+    constexpr bool RING = EPI_ == EPI_RESIDUAL_RING;
+    constexpr int EPI = RING ? (int)EPI_RESIDUAL : EPI_;
     static_assert(EPI == EPI_BIAS || EPI == EPI_GELU || EPI == EPI_QUICK_GELU || (EPI == EPI_RESIDUAL && !LNC),
                   "persistent schedule: bias / GELU / quick-GELU / residual epilogues");
     constexpr bool RES = EPI == EPI_RESIDUAL;
     static_assert(!STATS || RES, "row statistics for a folded norm: the residual epilogue produces them");
+    static_assert(!RING || (RES && !HALFT), "the ring route is the residual epilogue's");
+    constexpr bool RESV = RES && !RING;   // the residual tile is read by the epilogue, in the store layout
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int wr = wave >> 2, wc = wave & 3, fr = lane & 15, kq = lane >> 4;
     const int tid = wave * 64 + lane;
     const int nk = a.K / P_BK;
+    const int nkt = nk + (RING ? 2 : 0);   // K tiles of an output tile in the ring: the real ones, then (RING) the two that carry the residual
     const int T = a.mt * a.nt, G = gridDim.x;
     constexpr int BM = 64 * MT, HM = 32 * MT;     // block rows; rows of an A half
 
@@ -163,7 +176,7 @@ __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a
 
     // ---- a lane's part of the refill addresses: DMA slot s (0 / 1) of this wave is 8 rows of a half-tile; row r of the half,
     // 16-byte chunk c = (lane & 7) ^ (r & 7) of its 128 bytes (the source-side swizzle of gemm256.hip) ----
-    unsigned xvo[2], wvo[2];
+    unsigned xvo[2], wvo[2], rvr[RING ? 2 : 1];
     int lslot[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -173,21 +186,56 @@ __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a
         xvo[s] = ((unsigned)(xs * 8 + r8) * (unsigned)a.ldx + (unsigned)c * 8u) * 2u;
         wvo[s] = ((unsigned)(seg * 8 + r8) * (unsigned)a.ldw + (unsigned)c * 8u) * 2u;
         lslot[s] = seg * 1024;
+        if constexpr (RING) rvr[s] = ((unsigned)(xs * 8 + r8) * (unsigned)a.ldr + (unsigned)c * 8u) * 2u;   // (the A-side pattern over the residual's rows)
     }
-    // refill of one half-tile: K tile `tt` of the current tile, or (tt >= nk) K tile tt - nk of the next one
+    // RING: one half-tile slot of virtual K tile v from the residual: rows [m0 + half HM, + HM), 64 columns from n0 + 128 v + 64 colh.
+    // Rows beyond M are out of the descriptor's range (zeros).  A lane whose 8 columns lie beyond N (ragged last column tile) is sent
+    // out of range too: what follows a row in memory -- padding, the next row -- must not reach the row's last 32-column product.
+    const int rc8 = RING ? (((lane & 7) ^ ((lane >> 3) & 7)) + 1) * 8 : 0;   // end of the lane's 16-byte chunk inside a slot row (both DMA slots)
+    const __amdgpu_buffer_rsrc_t rrr = __builtin_amdgcn_make_buffer_rsrc((void *)a.res, 0, RING ? (int)(((unsigned)(a.M - 1) * (unsigned)a.ldr + (unsigned)a.N) * 2u) : 0, 0x00020000);
+    // refill of one half-tile: ring position `tt` of the current tile -- its K tile tt (tt < nk), with RING its residual's virtual
+    // tile tt - nk (nk <= tt < nkt) -- or (tt >= nkt) K tile tt - nkt of the next tile
     int m0 = 0, n0 = 0, m0n = 0, n0n = 0;
+    auto issue_R = [&](char *dst, int half, int v, int colh) {
+        if constexpr (RING) {
+            const int c0 = n0 + v * 128 + colh * 64;
+            const unsigned so = ((unsigned)(m0 + half * HM) * (unsigned)a.ldr + (unsigned)c0) * 2u;
+            const bool in = rc8 <= a.N - c0;
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rrr, (__attribute__((address_space(3))) void *)(dst + lslot[s]), 16, (int)(in ? rvr[s] : 0x80000000u), (int)so, 0, 0);
+        }
+    };
     auto issue_A = [&](int half, int stage, int tt) {
-        const bool nx = tt >= nk;
-        const unsigned so = ((unsigned)((nx ? m0n : m0) + half * HM) * (unsigned)a.ldx + (unsigned)((nx ? tt - nk : tt) * P_BK)) * 2u;
+        char *dst = smem + stage * P_STAGE + (half ? P_A1 : P_A0);
+        if (RING && tt >= nk && tt < nkt) { issue_R(dst, half, tt - nk, 0); return; }
+        const bool nx = tt >= nkt;
+        const unsigned so = ((unsigned)((nx ? m0n : m0) + half * HM) * (unsigned)a.ldx + (unsigned)((nx ? tt - nkt : tt) * P_BK)) * 2u;
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void *)(dst + lslot[s]), 16, (int)xvo[s], (int)so, 0, 0);
+    };
+    // (RING, LEAN: K tile tt is known to be a real K tile of the CURRENT tile -- the steady part of the K loop carries neither the
+    //  branch to the residual's refill nor the next tile's selects)
+    auto issue_A_cur = [&](int half, int stage, int tt) {
+        const unsigned so = ((unsigned)(m0 + half * HM) * (unsigned)a.ldx + (unsigned)(tt * P_BK)) * 2u;
         char *dst = smem + stage * P_STAGE + (half ? P_A1 : P_A0);
 #pragma unroll
         for (int s = 0; s < 2; ++s)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void *)(dst + lslot[s]), 16, (int)xvo[s], (int)so, 0, 0);
     };
-    auto issue_B = [&](int half, int stage, int tt) {
-        const bool nx = tt >= nk;
-        const unsigned so = ((unsigned)((nx ? n0n : n0) + half * 128) * (unsigned)a.ldw + (unsigned)((nx ? tt - nk : tt) * P_BK)) * 2u;
+    auto issue_B_cur = [&](int half, int stage, int tt) {
+        const unsigned so = ((unsigned)(n0 + half * 128) * (unsigned)a.ldw + (unsigned)(tt * P_BK)) * 2u;
         char *dst = smem + stage * P_STAGE + (half ? P_B1 : P_B0);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void *)(dst + lslot[s]), 16, (int)wvo[s], (int)so, 0, 0);
+    };
+    auto issue_B = [&](int half, int stage, int tt) {
+        char *dst = smem + stage * P_STAGE + (half ? P_B1 : P_B0);
+        if (RING && tt >= nk && tt < nkt) { issue_R(dst, half, tt - nk, 1); return; }
+        const bool nx = tt >= nkt;
+        const unsigned so = ((unsigned)((nx ? n0n : n0) + half * 128) * (unsigned)a.ldw + (unsigned)((nx ? tt - nkt : tt) * P_BK)) * 2u;
 #pragma unroll
         for (int s = 0; s < 2; ++s)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void *)(dst + lslot[s]), 16, (int)wvo[s], (int)so, 0, 0);
@@ -220,7 +268,7 @@ __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.bias + c8),
                                                  (__attribute__((address_space(3))) void *)(smem + P_COL + buf * 2048), 16, 0, 0);
             }
-            if (RES && wave == 1 && a.scale) {   // LayerScale of the residual epilogue, the same way, 1 KiB further
+            if (RESV && wave == 1 && a.scale) {   // LayerScale of the residual epilogue, the same way, 1 KiB further
                 int c8 = nn + (lane < 32 ? lane : 31) * 8;
                 c8 = c8 + 8 <= a.N ? c8 : a.N - 8;
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.scale + c8),
@@ -266,11 +314,11 @@ __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a
     // lane), with inline buffer loads: a compiler-visible load in front of the stores would make every use wait for vmcnt(0)
     // (loads and stores retire out of order with each other), i.e. for the store just issued.  Descriptor built by hand for the asm.
     const u32x4_t rrs = {(unsigned)(reinterpret_cast<uintptr_t>(a.res) & 0xffffffffu), (unsigned)(reinterpret_cast<uintptr_t>(a.res) >> 32) & 0xffffu,
-                         RES ? ((unsigned)(a.M - 1) * (unsigned)a.ldr + (unsigned)a.N) * 2u : 0u, 0x00020000u};
+                         RESV ? ((unsigned)(a.M - 1) * (unsigned)a.ldr + (unsigned)a.N) * 2u : 0u, 0x00020000u};
     const unsigned rvo = ((unsigned)(wr * (16 * MT) + fr) * (unsigned)a.ldr + (unsigned)ycol) * 2u;
-    u32x4_t ra[RES ? MT : 1], rb[RES ? 3 * MT : 1];   // residual pieces of quadrant 0 / of quadrants 1, 2, 3
+    u32x4_t ra[RESV ? MT : 1], rb[RESV ? 3 * MT : 1];   // residual pieces of quadrant 0 / of quadrants 1, 2, 3
     auto res_load_q = [&](u32x4_t *dst, int q, int mm, int nn) {
-        if constexpr (RES) {
+        if constexpr (RESV) {
             const int qi = q >> 1, qj = q & 1;
             const unsigned vo = nn + qj * 128 + ycol + 8 <= a.N ? rvo : 0x80000000u;
 #pragma unroll
@@ -298,6 +346,30 @@ __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a
             dst[t][1] = *reinterpret_cast<const bf16x8_t *>(half + (woff[t] ^ 64));
         }
     };
+    // RING: a residual slot read as A fragments (read_x's rows), only the k step that holds this wave's 32 columns; and the
+    // identity fragment of n tile i in the W operand's lane mapping (woff: lane row kq holds k = 8 kq .. 8 kq + 7 of feature fr):
+    // bf16 1.0 where k == 16 i + fr, so that D[n][m] += res[m][16 i + n].
+    const int rks = (wc & 1) << 6;
+    auto read_r = [&](const char *slot) {
+#pragma unroll
+        for (int t = 0; t < MT; ++t) xf[t][0] = *reinterpret_cast<const bf16x8_t *>(slot + (xoff[t] ^ rks));
+    };
+    bf16x8_t idf[RING ? 2 : 1];
+    if constexpr (RING) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) idf[i][e] = (kq * 8 + e == i * 16 + fr) ? (short)0x3f80 : (short)0;
+    }
+#define P_RMMA(Q)                                                                                               \
+    do {                                                                                                        \
+        __builtin_amdgcn_s_setprio(1);                                                                          \
+        _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                           \
+            _Pragma("unroll") for (int j = 0; j < MT; ++j)                                                      \
+                acc[Q][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(idf[i], xf[j][0], acc[Q][i][j], 0, 0, 0); \
+        __builtin_amdgcn_s_setprio(0);                                                                          \
+        __builtin_amdgcn_sched_barrier(0);                                                                      \
+    } while (0)
     // (FIRST: K tile 0 of a tile starts its accumulators from the instruction's constant zero -- no 128 moves per tile)
 #define P_MMA(Q, WF, FIRST)                                                                                     \
     do {                                                                                                        \
@@ -353,35 +425,65 @@ __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a
         // and group 0 through group 1's: the two epilogues ran one after the other (phase clock: the first two K tiles of a
         // tile took 16.8 K ticks instead of 5.2 K).
         if (wr == 1) P_BARRIER();
-        auto k_tile = [&](int t, auto first_tag) {
+        auto k_tile = [&](int t, auto first_tag, auto lean_tag) {
             constexpr bool FIRST = decltype(first_tag)::value;
+            constexpr bool LEAN = decltype(lean_tag)::value;
             const int s = (t + par) & 1;
             const char *st = smem + s * P_STAGE;
             // phase 1: quadrant (A0,B0); refill B0 of the OTHER stage with K tile t+1
             read_x(st + P_A0); read_w_into(st + P_B0, wf);
-            issue_B(0, s ^ 1, t + 1);
+            if constexpr (LEAN) issue_B_cur(0, s ^ 1, t + 1); else issue_B(0, s ^ 1, t + 1);
             P_WAIT_LGKM0(); P_BARRIER();
             P_MMA(0, wf, FIRST);
             P_BARRIER();
             // phase 2: quadrant (A0,B1); refill A0 (this stage) with K tile t+2
             read_w_into(st + P_B1, wg);
-            issue_A(0, s, t + 2);
+            if constexpr (LEAN) issue_A_cur(0, s, t + 2); else issue_A(0, s, t + 2);
             P_WAIT_LGKM0(); P_BARRIER();
             P_MMA(1, wg, FIRST);
             P_BARRIER();
             // phase 3: quadrant (A1,B1); refill B1 with K tile t+2
             read_x(st + P_A1);
-            issue_B(1, s, t + 2);
+            if constexpr (LEAN) issue_B_cur(1, s, t + 2); else issue_B(1, s, t + 2);
             P_WAIT_LGKM0(); P_BARRIER();
             P_MMA(3, wg, FIRST);
             P_BARRIER();
             // phase 4: quadrant (A1,B0); refill A1 with K tile t+2; retire everything but the last 3 half-tiles
-            issue_A(1, s, t + 2);
+            if constexpr (LEAN) issue_A_cur(1, s, t + 2); else issue_A(1, s, t + 2);
             asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
             P_WAIT_LGKM0(); P_BARRIER();
             P_MMA(2, wf, FIRST);
             P_BARRIER();
             if (a.prof && t < 4) t_k[t] = (unsigned)__builtin_amdgcn_s_memtime();   // (clock: the first K tiles of a tile, one by one)
+        };
+        // RING: virtual K tile V (ring position nk + V) adds the residual columns of B half V to quadrants V and 2 + V.  Waves
+        // wc = 0, 1 own columns from the first 64 (the A slots), wc = 2, 3 from the second 64 (the B slots): a wave-uniform slot
+        // OFFSET, no branch.  The four refills go out in a normal K tile's phases and order (it is the next tile's K tiles 0 / 1
+        // they fetch), behind the same barriers: A0 is read in phase 1 and refilled in phase 2, B1 read in 2 and refilled in 3, A1
+        // read in 2 and refilled in 4, B0 read in 1 and refilled in the next K tile's phase 1 -- never closer than in k_tile.
+        // Phases 3 and 4 have no MFMA section; their barriers stay, so the two wave groups keep their stagger.
+        auto v_tile = [&](auto v_tag) {
+            constexpr int V = decltype(v_tag)::value;
+            const int t = nk + V;
+            const int s = (t + par) & 1;
+            const char *st = smem + s * P_STAGE + (wc >> 1) * (2 * P_HALF);
+            read_r(st);                      // row half 0
+            issue_B(0, s ^ 1, t + 1);
+            P_WAIT_LGKM0(); P_BARRIER();
+            P_RMMA(V);
+            P_BARRIER();
+            read_r(st + P_HALF);             // row half 1
+            issue_A(0, s, t + 2);
+            P_WAIT_LGKM0(); P_BARRIER();
+            P_RMMA(2 + V);
+            P_BARRIER();
+            issue_B(1, s, t + 2);
+            P_BARRIER();
+            P_BARRIER();
+            issue_A(1, s, t + 2);
+            asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            P_BARRIER();
+            P_BARRIER();
         };
         // a HALF tile's K tile: quadrants (A0,B0), (A0,B1) only.  Phases 1 and 2 are the full tile's (same refills: B0 of the other stage
         // with K tile t + 1, A0 of this stage with t + 2); the third phase has no MFMA section: it refills B1 (read for the last time in
@@ -422,23 +524,34 @@ __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a
 #pragma unroll
                     for (int j = 0; j < MT; ++j) acc[q][i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
         } else {
-        k_tile(0, std::true_type{});
-        if constexpr (RES) {
+        k_tile(0, std::true_type{}, std::false_type{});
+        if constexpr (RESV) {
             // the residual pieces of quadrant 0 are requested in front of the last K tile (more than one quadrant's worth does
             // not fit beside the fragments: the compiler would spill the in-flight registers).  That K tile's counted wait is
             // exact for the refills only (nothing is assumed about the order in which register loads and LDS-DMA retire relative
             // to each other): the epilogue waits for the pieces with vmcnt(0).
 #pragma unroll 1
-            for (int t = 1; t < nk - 1; ++t) k_tile(t, std::false_type{});
+            for (int t = 1; t < nk - 1; ++t) k_tile(t, std::false_type{}, std::false_type{});
             res_load_q(ra, 0, m0, n0);
-            k_tile(nk - 1, std::false_type{});
+            k_tile(nk - 1, std::false_type{}, std::false_type{});
         } else {
+            if constexpr (RING) {
+                // K tiles 1 .. nk - 3 request real K tiles of this tile only; the last two request the residual's
+                const int t_res = nk - 2 > 1 ? nk - 2 : 1;
 #pragma unroll 1
-            for (int t = 1; t < nk; ++t) k_tile(t, std::false_type{});
+                for (int t = 1; t < t_res; ++t) k_tile(t, std::false_type{}, std::true_type{});
+#pragma unroll 1
+                for (int t = t_res; t < nk; ++t) k_tile(t, std::false_type{}, std::false_type{});
+                v_tile(std::integral_constant<int, 0>{});
+                v_tile(std::integral_constant<int, 1>{});
+            } else {
+#pragma unroll 1
+                for (int t = 1; t < nk; ++t) k_tile(t, std::false_type{}, std::false_type{});
+            }
         }
         }
         if (wr == 0) P_BARRIER();   // level again
-        par = (par + nk) & 1;
+        par = (par + nkt) & 1;
         const unsigned t_b = a.prof ? (unsigned)__builtin_amdgcn_s_memtime() : 0u;
 
         // ---- between two tiles: the ring already holds the next tile's K tile 0 (its K tile 1 is in flight) ----
@@ -493,7 +606,68 @@ __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a
             P_WAIT_LGKM0(); P_BARRIER();
             }
         }
-        if constexpr (RES) {
+        // folded norm, producer side (the residual epilogues, both routes): statistics of the bf16 values a lane has just packed
+        const bool rms_ = STATS == 2 ? true : (a.ln_rms != 0);   // (wide statistics exist for RMSNorm only: a constant there)
+        float st_m[STATS ? MT : 1], st_q[STATS ? MT : 1];   // a lane's {mean, M2} of the qj = 0 pieces, until their qj = 1 partners
+        auto stats_piece = [&](const u32x4_t &o, int qi, int qj, int j, bool dropped) {
+                                if constexpr (STATS) {
+                                    // folded norm, producer side: {mean, M2} ({sum of squares, -} for RMSNorm) of the bf16 values just packed,
+                                    // per output row and 256-column tile -- 8 values here, the row's other 8 of this lane when qj = 1, then
+                                    // the 4 lane rows, then (through LDS) the 4 waves that share the row
+                                    const unsigned u[4] = {o.x, o.y, o.z, o.w};
+                                    float x_[8];
+            #pragma unroll
+                                    for (int k2 = 0; k2 < 4; ++k2) { x_[2 * k2] = bf16lo_to_f32(u[k2]); x_[2 * k2 + 1] = bf16hi_to_f32(u[k2]); }
+                                    float pm, pq = 0.f;
+                                    if (rms_) {
+                                        pm = 0.f;
+            #pragma unroll
+                                        for (int k2 = 0; k2 < 8; ++k2) pm = fmaf(x_[k2], x_[k2], pm);
+                                        if constexpr (STATS == 2) { if (dropped) pm = 0.f; }   // (ragged last column tile: columns beyond N do not exist)
+                                    } else {
+                                        pm = ((x_[0] + x_[1]) + (x_[2] + x_[3])) + ((x_[4] + x_[5]) + (x_[6] + x_[7]));
+                                        pm *= 0.125f;
+            #pragma unroll
+                                        for (int k2 = 0; k2 < 8; ++k2) { const float d = x_[k2] - pm; pq = fmaf(d, d, pq); }
+                                    }
+                                    if (qj == 0) { st_m[j] = pm; st_q[j] = pq; }
+                                    else {
+                                        float mean = st_m[j], m2 = st_q[j];
+                                        if (rms_) mean += pm;
+                                        else { const float d = pm - mean; mean = fmaf(0.5f, d, mean); m2 = fmaf(d * d, 4.f, m2 + pq); }
+                                        pair_combine<16>(mean, m2, 8.f, rms_);
+                                        pair_combine<32>(mean, m2, 16.f, rms_);
+                                        if (kq == 0) reinterpret_cast<float2_t *>(smem + P_RAW)[(qi * HM + wr * (16 * MT) + j * 16 + fr) * 4 + wc] = (float2_t){mean, m2};
+                                    }
+                                }
+        };
+        auto stats_finish = [&]() {
+            if constexpr (STATS) {
+                P_WAIT_LGKM0(); P_BARRIER();
+                if (tid < BM) {   // the four waves' partials (64 values each) of row tid, in a fixed order
+                    float2_t pp[4];
+                    {
+                        const unsigned addr = (unsigned)(size_t)(smem + P_RAW + tid * 32);   // (inline: see the folded-norm consumer)
+                        asm volatile("ds_read_b64 %0, %4\n\tds_read_b64 %1, %4 offset:8\n\tds_read_b64 %2, %4 offset:16\n\tds_read_b64 %3, %4 offset:24\n\ts_waitcnt lgkmcnt(0)"
+                                     : "=&v"(pp[0]), "=&v"(pp[1]), "=&v"(pp[2]), "=&v"(pp[3]) : "v"(addr) : "memory");
+                    }
+                    float2_t r_;
+                    if (rms_) r_ = (float2_t){(pp[0].x + pp[1].x) + (pp[2].x + pp[3].x), 0.f};
+                    else {
+                        const float d0 = pp[1].x - pp[0].x, d1 = pp[3].x - pp[2].x;
+                        const float m0_ = fmaf(0.5f, d0, pp[0].x), m1_ = fmaf(0.5f, d1, pp[2].x);
+                        const float q0_ = fmaf(d0 * d0, 32.f, pp[0].y + pp[1].y), q1_ = fmaf(d1 * d1, 32.f, pp[2].y + pp[3].y);
+                        const float d = m1_ - m0_;
+                        r_ = (float2_t){fmaf(0.5f, d, m0_), fmaf(d * d, 64.f, q0_ + q1_)};
+                    }
+                    const int m = m0 + tid;
+                    if constexpr (STATS == 2) {   // (slots >= nt of a row are never written: the orchestrator clears the buffer once per call)
+                        if (m < a.M) a.ln_out[(size_t)m * 16 + (n0 >> 8)] = r_.x;
+                    } else if (m < a.M) *reinterpret_cast<float2_t *>(a.ln_out + ((size_t)m * a.nt + (n0 >> 8)) * 2) = r_;
+                }
+            }
+        };
+        if constexpr (RESV) {
             // ---- residual epilogue: y = res + (acc + bias) * LayerScale, one rounding.  The lane-row exchange is done on the fp32
             // values (four exchanges per piece), the residual added in the exchanged layout.  Quadrant 0's residual pieces were
             // requested a K tile ago (waited for here); those of quadrants 1-3 are requested now (the fragment registers are
@@ -506,8 +680,6 @@ __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a
             u32x4_t o_prev = {0u, 0u, 0u, 0u};
             unsigned so_prev = 0u, yv_prev = 0u;
             unsigned yv[2];
-            const bool rms_ = STATS == 2 ? true : (a.ln_rms != 0);   // (wide statistics exist for RMSNorm only: a constant there)
-            float st_m[STATS ? MT : 1], st_q[STATS ? MT : 1];   // a lane's {mean, M2} of the qj = 0 pieces, until their qj = 1 partners
 #pragma unroll
             for (int qj = 0; qj < 2; ++qj) yv[qj] = n0 + qj * 128 + ycol + 8 <= a.N ? yvo : 0x80000000u;
 #pragma unroll
@@ -546,65 +718,13 @@ __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a
                     y[4] += bf16lo_to_f32(rr.z); y[5] += bf16hi_to_f32(rr.z); y[6] += bf16lo_to_f32(rr.w); y[7] += bf16hi_to_f32(rr.w);
                     if (q + j > 0 && !(a.prof & 2)) store_piece(o_prev, yrs, yv_prev, so_prev);
                     o_prev = (u32x4_t){pack_bf16x2(y[0], y[1]), pack_bf16x2(y[2], y[3]), pack_bf16x2(y[4], y[5]), pack_bf16x2(y[6], y[7])};
-                    if constexpr (STATS) {
-                        // folded norm, producer side: {mean, M2} ({sum of squares, -} for RMSNorm) of the bf16 values just packed,
-                        // per output row and 256-column tile -- 8 values here, the row's other 8 of this lane when qj = 1, then
-                        // the 4 lane rows, then (through LDS) the 4 waves that share the row
-                        const unsigned u[4] = {o_prev.x, o_prev.y, o_prev.z, o_prev.w};
-                        float x_[8];
-#pragma unroll
-                        for (int k2 = 0; k2 < 4; ++k2) { x_[2 * k2] = bf16lo_to_f32(u[k2]); x_[2 * k2 + 1] = bf16hi_to_f32(u[k2]); }
-                        float pm, pq = 0.f;
-                        if (rms_) {
-                            pm = 0.f;
-#pragma unroll
-                            for (int k2 = 0; k2 < 8; ++k2) pm = fmaf(x_[k2], x_[k2], pm);
-                            if constexpr (STATS == 2) { if (yv[qj] == 0x80000000u) pm = 0.f; }   // (ragged last column tile: columns beyond N do not exist)
-                        } else {
-                            pm = ((x_[0] + x_[1]) + (x_[2] + x_[3])) + ((x_[4] + x_[5]) + (x_[6] + x_[7]));
-                            pm *= 0.125f;
-#pragma unroll
-                            for (int k2 = 0; k2 < 8; ++k2) { const float d = x_[k2] - pm; pq = fmaf(d, d, pq); }
-                        }
-                        if (qj == 0) { st_m[j] = pm; st_q[j] = pq; }
-                        else {
-                            float mean = st_m[j], m2 = st_q[j];
-                            if (rms_) mean += pm;
-                            else { const float d = pm - mean; mean = fmaf(0.5f, d, mean); m2 = fmaf(d * d, 4.f, m2 + pq); }
-                            pair_combine<16>(mean, m2, 8.f, rms_);
-                            pair_combine<32>(mean, m2, 16.f, rms_);
-                            if (kq == 0) reinterpret_cast<float2_t *>(smem + P_RAW)[(qi * HM + wr * (16 * MT) + j * 16 + fr) * 4 + wc] = (float2_t){mean, m2};
-                        }
-                    }
+                    stats_piece(o_prev, qi, qj, j, yv[qj] == 0x80000000u);
                     yv_prev = yv[qj];
                     so_prev = ((unsigned)(m0 + qi * HM + j * 16) * (unsigned)a.ldy + (unsigned)(n0 + qj * 128)) * 2u;
                 }
             }
             if (!(a.prof & 2)) store_piece(o_prev, yrs, yv_prev, so_prev);
-            if constexpr (STATS) {
-                P_WAIT_LGKM0(); P_BARRIER();
-                if (tid < BM) {   // the four waves' partials (64 values each) of row tid, in a fixed order
-                    float2_t pp[4];
-                    {
-                        const unsigned addr = (unsigned)(size_t)(smem + P_RAW + tid * 32);   // (inline: see the folded-norm consumer)
-                        asm volatile("ds_read_b64 %0, %4\n\tds_read_b64 %1, %4 offset:8\n\tds_read_b64 %2, %4 offset:16\n\tds_read_b64 %3, %4 offset:24\n\ts_waitcnt lgkmcnt(0)"
-                                     : "=&v"(pp[0]), "=&v"(pp[1]), "=&v"(pp[2]), "=&v"(pp[3]) : "v"(addr) : "memory");
-                    }
-                    float2_t r_;
-                    if (rms_) r_ = (float2_t){(pp[0].x + pp[1].x) + (pp[2].x + pp[3].x), 0.f};
-                    else {
-                        const float d0 = pp[1].x - pp[0].x, d1 = pp[3].x - pp[2].x;
-                        const float m0_ = fmaf(0.5f, d0, pp[0].x), m1_ = fmaf(0.5f, d1, pp[2].x);
-                        const float q0_ = fmaf(d0 * d0, 32.f, pp[0].y + pp[1].y), q1_ = fmaf(d1 * d1, 32.f, pp[2].y + pp[3].y);
-                        const float d = m1_ - m0_;
-                        r_ = (float2_t){fmaf(0.5f, d, m0_), fmaf(d * d, 64.f, q0_ + q1_)};
-                    }
-                    const int m = m0 + tid;
-                    if constexpr (STATS == 2) {   // (slots >= nt of a row are never written: the orchestrator clears the buffer once per call)
-                        if (m < a.M) a.ln_out[(size_t)m * 16 + (n0 >> 8)] = r_.x;
-                    } else if (m < a.M) *reinterpret_cast<float2_t *>(a.ln_out + ((size_t)m * a.nt + (n0 >> 8)) * 2) = r_;
-                }
-            }
+            stats_finish();
         } else
         // ---- epilogue: straight from the accumulators, nothing waits for the stores ----
         // A lane holds 4 features (8 bytes packed) of row fr in each of the wave's two 16-column n tiles; v_permlane16_swap
@@ -653,7 +773,7 @@ __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a
                     for (int i = 0; i < 2; ++i) {
                         float v[4];
                         if constexpr (LNC) epi_value_folded<EPI>(acc[q][i][j], rn[qi][j].x, rn[qi][j].y, csum[i], cols[i], v);
-                        else epi_value<EPI>(a, 0, 0, acc[q][i][j], cols[i], v);
+                        else epi_value<RING ? EPI_BIAS : EPI>(a, 0, 0, acc[q][i][j], cols[i], v);   // (RING: the residual is in the accumulators)
                         pk[i][0] = pack_bf16x2(v[0], v[1]); pk[i][1] = pack_bf16x2(v[2], v[3]);
                     }
                     lane_row_swap(pk[0][0], pk[1][0]);
@@ -663,12 +783,14 @@ __global__ __launch_bounds__(P_THREADS, 1) void gemm256p_kernel(const GemmArgs a
                     // run-to-run different)
                     if (q + j > 0 && !(a.prof & 2)) store_piece(o_prev, yrs, yv_prev, so_prev);   // (prof bit 1: ablation, no stores)
                     o_prev = (u32x4_t){pk[0][0], pk[0][1], pk[1][0], pk[1][1]};
+                    stats_piece(o_prev, qi, qj, j, yv[qj] == 0x80000000u);
                     yv_prev = yv[qj];
                     so_prev = ((unsigned)(m0 + qi * HM + j * 16) * (unsigned)a.ldy + (unsigned)(n0 + qj * 128)) * 2u;
                 }
             }
             asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");   // (the same distance for the last piece)
             if (!(a.prof & 2)) store_piece(o_prev, yrs, yv_prev, so_prev);
+            stats_finish();
         }
         if (a.prof) {   // (summed per block, written once at its end: an atomic per tile would sit in front of the next tile's refills)
             const unsigned t_c = (unsigned)__builtin_amdgcn_s_memtime();
@@ -728,6 +850,18 @@ int gemm_half_tail()
     return g_half_tail;
 }
 int gemm_half_tail_set(int v) { const int old = gemm_half_tail(); g_half_tail = v != 0; return old; }
+// The residual epilogue without LayerScale takes its residual through the operand ring (kernel comment, RING) unless switched off:
+// VLLM_GEMM_RES_RING=0 / vllm_set_option("gemm_res_ring", 0) keep the epilogue's own loads (same-process A/B, tests of both routes).
+static int g_res_ring = -1;
+int gemm_res_ring()
+{
+    if (g_res_ring < 0) {
+        const char *e = getenv("VLLM_GEMM_RES_RING");
+        g_res_ring = e ? atoi(e) != 0 : 1;
+    }
+    return g_res_ring;
+}
+int gemm_res_ring_set(int v) { const int old = gemm_res_ring(); g_res_ring = v != 0; return old; }
 static long g_p_launches = 0;   // (vllm_gemm_persistent_launches: tests assert the path they mean to cover ran)
 long gemm256p_launches() { return g_p_launches; }
 
@@ -763,6 +897,10 @@ int gemm256p_launch(int epi, int MT, const GemmArgs &a_, int cus, hipStream_t st
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256p_kernel<EPI_RESIDUAL, 3, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256p_kernel<EPI_RESIDUAL, 4, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256p_kernel<EPI_RESIDUAL, 3, false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS);
+#define SETRING(S) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256p_kernel<EPI_RESIDUAL_RING, 4, false, S>), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS); \
+                   (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256p_kernel<EPI_RESIDUAL_RING, 3, false, S>), hipFuncAttributeMaxDynamicSharedMemorySize, P_LDS);
+        SETRING(0); SETRING(1); SETRING(2);
+#undef SETRING
 #undef SETATTR
     }
 #define LAUNCH_H(E, H) do { if (a.ln_in) { if (MT == 4) VLLM_LAUNCH((gemm256p_kernel<E, 4, true, 0, H>), grid, block, P_LDS, st, a); \
@@ -770,18 +908,23 @@ int gemm256p_launch(int epi, int MT, const GemmArgs &a_, int cus, hipStream_t st
                             else { if (MT == 4) VLLM_LAUNCH((gemm256p_kernel<E, 4, false, 0, H>), grid, block, P_LDS, st, a); \
                                    else VLLM_LAUNCH((gemm256p_kernel<E, 3, false, 0, H>), grid, block, P_LDS, st, a); } } while (0)
 #define LAUNCH(E) do { if (a.half_tail) LAUNCH_H(E, true); else LAUNCH_H(E, false); } while (0)
+#define LAUNCH_RES(S) do { if (ring) { if (MT == 4) VLLM_LAUNCH((gemm256p_kernel<EPI_RESIDUAL_RING, 4, false, S>), grid, block, P_LDS, st, a); \
+                                       else VLLM_LAUNCH((gemm256p_kernel<EPI_RESIDUAL_RING, 3, false, S>), grid, block, P_LDS, st, a); } \
+                           else { if (MT == 4) VLLM_LAUNCH((gemm256p_kernel<EPI_RESIDUAL, 4, false, S>), grid, block, P_LDS, st, a); \
+                                  else VLLM_LAUNCH((gemm256p_kernel<EPI_RESIDUAL, 3, false, S>), grid, block, P_LDS, st, a); } } while (0)
+    // (with LayerScale res / ls is not exact in bf16: the epilogue route.  The ring reads the residual by LDS-DMA in 16-byte pieces,
+    //  like X and W: 16-byte aligned rows, ldr a multiple of 8; gemm256p_takes admits multiples of 4 for the epilogue's register loads)
+    const bool ring = epi == EPI_RESIDUAL && !a.scale && (a.ldr & 7) == 0 && gemm_res_ring();
     if (epi == EPI_RESIDUAL && a.ln_out && a.ln_wide) {
-        if (MT == 4) VLLM_LAUNCH((gemm256p_kernel<EPI_RESIDUAL, 4, false, 2>), grid, block, P_LDS, st, a);
-        else VLLM_LAUNCH((gemm256p_kernel<EPI_RESIDUAL, 3, false, 2>), grid, block, P_LDS, st, a);
+        LAUNCH_RES(2);
     } else if (epi == EPI_RESIDUAL && a.ln_out) {
-        if (MT == 4) VLLM_LAUNCH((gemm256p_kernel<EPI_RESIDUAL, 4, false, 1>), grid, block, P_LDS, st, a);
-        else VLLM_LAUNCH((gemm256p_kernel<EPI_RESIDUAL, 3, false, 1>), grid, block, P_LDS, st, a);
+        LAUNCH_RES(1);
     } else if (epi == EPI_RESIDUAL) {
-        if (MT == 4) VLLM_LAUNCH((gemm256p_kernel<EPI_RESIDUAL, 4, false>), grid, block, P_LDS, st, a);
-        else VLLM_LAUNCH((gemm256p_kernel<EPI_RESIDUAL, 3, false>), grid, block, P_LDS, st, a);
+        LAUNCH_RES(0);
     } else if (epi == EPI_BIAS) LAUNCH(EPI_BIAS); else if (epi == EPI_GELU) LAUNCH(EPI_GELU); else LAUNCH(EPI_QUICK_GELU);
 #undef LAUNCH
 #undef LAUNCH_H
+#undef LAUNCH_RES
     VLLM_CHECK_LAUNCH("gemm256p_kernel");
     return VLLM_OK;
 }

