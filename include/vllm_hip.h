@@ -705,6 +705,42 @@ int vllm_gemm_bf16_residual_save(const uint16_t *X, const uint16_t *W, const uin
                                  int K, int ldx, int ldw, int ldy, int epilogue, const uint16_t *scale, const uint16_t *res, int ldr,
                                  vllm_stream_t stream);
 
+/* Training the embeddings of the vision tower (InternVisionEmbeddings.forward, modeling_intern_vit.py:82-90; HF CLIPVisionEmbeddings
+ * with patch_b = NULL): patch Conv2d (kernel = stride = patch) as im2col + GEMM, class embedding in row 0, + position table.  The
+ * struct and the calls are additions: VllmVitDesc / VllmVitLayer and vllm_abi_version are unchanged.
+ * Forward: the embedding step of vllm_vit_forward with the same kernels -- `out` is bit for bit hidden_states[0] of the InternViT
+ * inference encoder for the same parameters and pixels.  The caller passes the Conv2d weight as the module stores it; the K-padded
+ * copy the GEMM reads is built in the workspace on every call (nothing to go stale between optimizer steps).
+ * Backward, with G = grad_out [n, 1+P, C] and col the im2col matrix of the forward ([n P, 3 patch^2], recomputed from `pixels`, not
+ * kept by the forward):
+ *     grad_pos[s, c]     = sum_n G[n, s, c]
+ *     grad_cls[c]        = sum_n G[n, 0, c]                (the same fp32 sum in the same order: equals grad_pos[0] bit for bit)
+ *     grad_patch_b[c]    = sum_n sum_{s >= 1} G[n, s, c]
+ *     grad_patch_w[c, k] = sum_n sum_p G[n, 1+p, c] col[n P + p, k]
+ * Every gradient is bf16 in the parameter's shape, accumulated in fp32 and rounded once, overwritten (the caller accumulates).  A NULL
+ * gradient pointer skips that work and everything only it needed (no im2col and no weight-gradient GEMM without grad_patch_w; no
+ * reduction pass when grad_patch_b, grad_cls and grad_pos are all NULL).  No atomics: run-to-run identical.  Pixel gradients are not
+ * produced.  n_tiles == 0 zero-fills the requested gradients.  A refused call (VLLM_EINVAL, message in vllm_last_error) writes nothing.
+ * workspace: vllm_vit_embed_workspace_bytes(desc, n_tiles) bytes serve both calls (< 0 for a refused descriptor; host-only
+ * arithmetic).  Nothing is allocated, nothing synchronised; one stream. */
+/* Alignment: out, grad_out, the parameters, the gradients and the workspace 16 bytes.  pixels: element alignment only. */
+typedef struct VllmVitEmbed {
+    int hidden;          /* C, % 64 == 0, <= 8192 */
+    int patch, image;    /* image % patch == 0; P = (image/patch)^2 patches, S = 1 + P rows per tile */
+    int pixel_is_f32;    /* 0 bf16, 1 fp32 */
+    const uint16_t *patch_w;   /* the Conv2d weight as the module stores it: [C, 3*patch*patch] contiguous (no padding) */
+    const uint16_t *patch_b;   /* [C] or NULL (CLIP's conv has no bias) */
+    const uint16_t *cls;       /* [C] */
+    const uint16_t *pos;       /* [1+P, C] */
+} VllmVitEmbed;
+int vllm_vit_embed_sizeof(void);
+long vllm_vit_embed_workspace_bytes(const VllmVitEmbed *desc, int n_tiles);
+int vllm_vit_embed_forward(const VllmVitEmbed *desc, const void *pixels, int n_tiles, uint16_t *out, void *workspace,
+                           long workspace_bytes, vllm_stream_t stream);
+int vllm_vit_embed_backward(const VllmVitEmbed *desc, const void *pixels, int n_tiles, const uint16_t *grad_out,
+                            uint16_t *grad_patch_w, uint16_t *grad_patch_b, uint16_t *grad_cls, uint16_t *grad_pos, void *workspace,
+                            long workspace_bytes, vllm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,6 +170,11 @@ class VllmVitLayerGrads(ctypes.Structure):
                                   "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2")]
 
 
+class VllmVitEmbed(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("hidden", "patch", "image", "pixel_is_f32")] + \
+               [(n, _P) for n in ("patch_w", "patch_b", "cls", "pos")]
+
+
 def check_struct_layouts():
     L = lib()
     assert ctypes.sizeof(VllmMsdaLayerDesc) == L.vllm_msda_layer_desc_sizeof(), "VllmMsdaLayerDesc layout mismatch"
@@ -179,6 +184,7 @@ def check_struct_layouts():
     assert ctypes.sizeof(VllmVitLayerTrain) == L.vllm_vit_layer_train_sizeof(), "VllmVitLayerTrain layout mismatch"
     assert ctypes.sizeof(VllmVitLayerSaved) == L.vllm_vit_layer_saved_sizeof(), "VllmVitLayerSaved layout mismatch"
     assert ctypes.sizeof(VllmVitLayerGrads) == L.vllm_vit_layer_grads_sizeof(), "VllmVitLayerGrads layout mismatch"
+    assert ctypes.sizeof(VllmVitEmbed) == L.vllm_vit_embed_sizeof(), "VllmVitEmbed layout mismatch"
 
 
 EPI_BIAS, EPI_GELU, EPI_QUICK_GELU, EPI_RESIDUAL, EPI_EMBED, EPI_F32 = 0, 1, 2, 3, 4, 5

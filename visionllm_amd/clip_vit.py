@@ -14,8 +14,8 @@ import torch
 from torch import nn
 
 from . import _lib
-from .vit_common import (EncoderPlan, _require_bf16_cuda, fold_norm_into_linear, kpad_for, model_output, norm_folding_applies, plan_ptr,
-                         padded_patch_weight, run_encoder)
+from .vit_common import (EncoderPlan, _require_bf16_cuda, embed_pixels, fold_norm_into_linear, kpad_for, model_output, norm_folding_applies,
+                         plan_ptr, padded_patch_weight, run_encoder)
 
 try:
     from transformers import CLIPVisionConfig  # noqa: F401  (the reference passes this very config class)
@@ -36,6 +36,12 @@ class _CLIPVisionEmbeddings(nn.Module):
         self.num_positions = self.num_patches + 1
         self.position_embedding = nn.Embedding(self.num_positions, self.embed_dim)
         self.register_buffer("position_ids", torch.arange(self.num_positions).expand((1, -1)), persistent=False)
+
+    def forward(self, pixel_values):
+        """HF CLIPVisionEmbeddings.forward (conv without bias, class embedding, the whole position table) through the entry the InternViT
+        embeddings use: vllm_vit_embed_forward, one autograd node (vllm_vit_embed_backward) when a parameter requires grad.  Only this
+        module is differentiable here: the CLIP encoder layers stay inference-only."""
+        return embed_pixels(pixel_values, self.patch_embedding, self.class_embedding, self.position_embedding.weight)
 
 
 class _CLIPAttention(nn.Module):

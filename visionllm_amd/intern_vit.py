@@ -7,15 +7,16 @@ VisionLLMv2/visionllmv2/model/internvit/modeling_intern_vit.py (:61-90 embedding
 ``encoder.layers.{i}.{attn.qkv.weight, attn.q_norm.weight, attn.k_norm.weight, attn.proj.*, mlp.fc1/fc2.*,
 norm1/norm2.weight, ls1, ls2}``).
 
-Inference: ``InternVisionModel.forward`` hands every parameter's device pointer to ``vllm_vit_forward`` (one C call for the whole
-encoder under ``torch.no_grad()``, as the reference runs the frozen tower, modeling_visionllmv2.py:560).
+Inference (the default): ``InternVisionModel.forward`` hands every parameter's device pointer to ``vllm_vit_forward`` (one C call for
+the whole encoder under ``torch.no_grad()``, as the reference runs the frozen tower, modeling_visionllmv2.py:560).
 
 Training (``freeze_vis_encoder=False``, train/train.py:163, 534): ``InternVisionEncoder.forward(inputs_embeds)`` runs the layers as the
 reference does (:232-276, each under ``torch.utils.checkpoint`` when ``gradient_checkpointing and self.training``), and
 ``InternVisionEncoderLayer.forward`` is ONE autograd node around ``vllm_vit_layer_forward_train`` / ``vllm_vit_layer_backward``
 (hand-written HIP underneath; dropout and drop-path are not implemented and raise in training mode).  ``InternRMSNorm.forward`` has
-its own node (``vllm_rmsnorm_backward_bf16``).  Gradients do not reach the embeddings: ``InternVisionModel.forward`` stays
-inference-only.
+its own node (``vllm_rmsnorm_backward_bf16``).  ``InternVisionEmbeddings.forward`` is one node around ``vllm_vit_embed_forward`` /
+``vllm_vit_embed_backward``, and ``InternVisionModel.forward`` with ``native_training = True`` chains the two as the reference's forward
+does (:320-343), so the tower trains from pixels: patch-embedding weight and bias, class embedding and position table included.
 """
 import ctypes
 
@@ -23,8 +24,8 @@ import torch
 from torch import nn
 
 from . import _lib
-from .vit_common import (EncoderPlan, _require_bf16_cuda, fold_norm_into_linear, kpad_for, model_output, norm_folding_applies, plan_ptr,
-                         padded_patch_weight, run_encoder)
+from .vit_common import (EncoderPlan, _require_bf16_cuda, embed_pixels, fold_norm_into_linear, kpad_for, model_output, norm_folding_applies,
+                         plan_ptr, padded_patch_weight, run_encoder)
 
 try:
     from transformers.configuration_utils import PretrainedConfig as _ConfigBase
@@ -135,6 +136,12 @@ class InternVisionEmbeddings(nn.Module):
         self.num_patches = (self.image_size // self.patch_size) ** 2
         self.num_positions = self.num_patches + 1
         self.position_embedding = nn.Parameter(torch.randn(1, self.num_positions, self.embed_dim))
+
+    def forward(self, pixel_values):
+        """modeling_intern_vit.py:82-90 on a CUDA tensor [n, 3, image, image] (the tile size is the position table's):
+        vllm_vit_embed_forward, as one autograd node (vllm_vit_embed_backward) when a parameter requires grad -- the same output bits
+        either way, and those of hidden_states[0] of the inference encoder.  There is no CPU path and no pixel gradient."""
+        return embed_pixels(pixel_values, self.patch_embedding, self.class_embedding, self.position_embedding)
 
 
 class InternAttention(nn.Module):
@@ -343,6 +350,9 @@ class InternVisionModel(nn.Module):
         self._plan = EncoderPlan()
         #: None = materialise every hidden state (reference behaviour); or indices to keep, e.g. (-1, -2, -3)
         self.keep_hidden_states = None
+        #: False = ``forward(pixel_values)`` is the fused inference encoder under no_grad, whatever the grad mode (the default);
+        #: True = with grad enabled and a parameter that requires grad, ``forward`` is differentiable: embeddings -> layer modules
+        self.native_training = False
 
     # -- reference API ------------------------------------------------------------------------------------
     def resize_pos_embeddings(self, old_size, new_size, patch_size):
@@ -408,21 +418,29 @@ class InternVisionModel(nn.Module):
         plan.key, plan.desc, plan.layers = key, desc, layers
         return desc
 
-    @torch.no_grad()
     def forward(self, pixel_values=None, output_hidden_states=None, return_dict=None, pixel_embeds=None):
+        """modeling_intern_vit.py:305-343.  ``pixel_values`` takes the fused inference encoder under ``torch.no_grad()`` unless
+        ``native_training`` is set, grad is enabled and a parameter requires grad: then ``self.embeddings`` and ``self.encoder`` run as
+        autograd nodes (the reference's own route), every hidden state is an autograd tensor and ``keep_hidden_states`` does not apply
+        (all of them are returned with ``output_hidden_states``).  ``pixel_embeds`` always runs the layer modules, under grad or not."""
         cfg = self.config
         output_hidden_states = (output_hidden_states if output_hidden_states is not None
                                 else getattr(cfg, "output_hidden_states", False))
         return_dict = return_dict if return_dict is not None else getattr(cfg, "use_return_dict", True)
         if pixel_values is None and pixel_embeds is None:
             raise ValueError("You have to specify pixel_values or pixel_embeds")
-        if pixel_embeds is not None:
-            raise NotImplementedError("pixel_embeds input is not wired to the native encoder (unused by VisionLLMv2)")
-        if len(pixel_values.shape) != 4:
+        if pixel_embeds is None and len(pixel_values.shape) != 4:
             raise ValueError(f"wrong pixel_values size: {pixel_values.shape}")
-        desc = self._build_plan()
-        keep = self.keep_hidden_states if output_hidden_states else (-1,)
-        states = run_encoder(desc, pixel_values, desc.num_layers, cfg.hidden_size, keep)
-        last = states[-1]
-        hs = tuple(states) if output_hidden_states else None
-        return model_output(last, last[:, 0, :], hs, return_dict)
+        train = self.native_training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if pixel_embeds is not None or train:
+            hidden_states = pixel_embeds if pixel_embeds is not None else self.embeddings(pixel_values)
+            enc = self.encoder(inputs_embeds=hidden_states, output_hidden_states=output_hidden_states, return_dict=True)
+            last = enc.last_hidden_state
+            return model_output(last, last[:, 0, :], enc.hidden_states, return_dict)
+        with torch.no_grad():
+            desc = self._build_plan()
+            keep = self.keep_hidden_states if output_hidden_states else (-1,)
+            states = run_encoder(desc, pixel_values, desc.num_layers, cfg.hidden_size, keep)
+            last = states[-1]
+            hs = tuple(states) if output_hidden_states else None
+            return model_output(last, last[:, 0, :], hs, return_dict)

@@ -86,6 +86,95 @@ def kpad_for(patch):
     return (k + 63) // 64 * 64
 
 
+def _embed_desc(pix, w, b, cls, pos, keep):
+    """VllmVitEmbed for the parameters as the modules store them: conv weight [C, 3, ps, ps], bias [C] or None, class embedding
+    (C elements), position table ([1 + P, C] elements).  The tile size is the position table's (resize_pos_embeddings may have
+    changed it, as in _build_plan)."""
+    C, ps = w.shape[0], w.shape[-1]
+    S = pos.numel() // C
+    g = int(round((S - 1) ** 0.5))
+    if g * g != S - 1:
+        raise ValueError(f"position table of {S} rows is not 1 + a square grid")
+    fields = {}
+    for name, t in (("patch_w", w), ("patch_b", b), ("cls", cls), ("pos", pos)):
+        if t is None:
+            fields[name] = None
+            continue
+        _require_bf16_cuda(name, t)
+        a = _lib.aligned(t.detach())
+        keep.append(a)
+        fields[name] = a.data_ptr()
+    return _lib.VllmVitEmbed(hidden=C, patch=ps, image=g * ps, pixel_is_f32=1 if pix.dtype == torch.float32 else 0, **fields), S
+
+
+def _embed_workspace(L, d, n, dev):
+    wsb = L.vllm_vit_embed_workspace_bytes(ctypes.byref(d), n)
+    _lib.check(0 if wsb >= 0 else -1, "vllm_vit_embed_workspace_bytes")
+    return _lib.workspace(dev, max(wsb, 1)), wsb
+
+
+def _embed_forward(pix, w, b, cls, pos):
+    keep = []
+    d, S = _embed_desc(pix, w, b, cls, pos, keep)
+    if pix.dim() != 4 or pix.shape[1] != 3 or pix.shape[2] != d.image or pix.shape[3] != d.image:
+        raise ValueError(f"pixel_values must be [n, 3, {d.image}, {d.image}], got {tuple(pix.shape)}")
+    L = _lib.lib()
+    _lib.check_struct_layouts()
+    n, dev = pix.shape[0], pix.device
+    out = torch.empty((n, S, d.hidden), dtype=torch.bfloat16, device=dev)
+    with torch.cuda.device(dev):
+        ws, wsb = _embed_workspace(L, d, n, dev)
+        _lib.check(L.vllm_vit_embed_forward(ctypes.byref(d), _lib.ptr(pix), n, _lib.ptr(out), _lib.ptr(ws), wsb, _lib.current_stream(dev)),
+                   "vllm_vit_embed_forward")
+    return out
+
+
+class _EmbedTrain(torch.autograd.Function):
+    """The embeddings of a vision tower as one autograd node: vllm_vit_embed_forward (the no-grad call's bits) /
+    vllm_vit_embed_backward.  Pixels and parameters go through save_for_backward, so an in-place update between forward and backward
+    fails autograd's version check; a parameter that does not need its gradient is a NULL pointer (that work is skipped)."""
+
+    @staticmethod
+    def forward(ctx, pix, w, b, cls, pos):
+        ctx.save_for_backward(pix, w, b, cls, pos)
+        return _embed_forward(pix, w, b, cls, pos)
+
+    @staticmethod
+    def backward(ctx, gout):
+        pix, w, b, cls, pos = ctx.saved_tensors
+        keep = []
+        d, _ = _embed_desc(pix, w, b, cls, pos, keep)
+        n, dev = pix.shape[0], pix.device
+        g = _lib.aligned(gout.to(torch.bfloat16))
+        need = ctx.needs_input_grad
+        grads = [torch.empty(p.shape, dtype=torch.bfloat16, device=dev) if (k and p is not None) else None
+                 for k, p in zip(need[1:], (w, b, cls, pos))]
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            ws, wsb = _embed_workspace(L, d, n, dev)
+            _lib.check(L.vllm_vit_embed_backward(ctypes.byref(d), _lib.ptr(pix), n, _lib.ptr(g), *[_lib.ptr(t) for t in grads], _lib.ptr(ws), wsb,
+                                                 _lib.current_stream(dev)), "vllm_vit_embed_backward")
+        return (None,) + tuple(grads)
+
+
+def embed_pixels(pixel_values, conv, class_embedding, position_table):
+    """InternVisionEmbeddings.forward (modeling_intern_vit.py:82-90) / HF CLIPVisionEmbeddings.forward on a CUDA tensor
+    [n, 3, image, image] (bf16 or fp32; other floating dtypes are cast to bf16 as run_encoder does) -> [n, 1 + P, C] bf16.  One
+    autograd node when grad is enabled and a parameter requires grad, a plain call otherwise: the same bits."""
+    if not pixel_values.is_cuda:
+        raise RuntimeError("pixel_values must be a CUDA tensor: the native vision encoder has no CPU path")
+    if pixel_values.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("gradients with respect to pixel_values are not implemented (nothing in the model asks for them); "
+                                  "detach pixel_values")
+    if pixel_values.dtype not in (torch.bfloat16, torch.float32):
+        pixel_values = pixel_values.to(torch.bfloat16)
+    pix = pixel_values.detach().contiguous()
+    params = (conv.weight, conv.bias, class_embedding, position_table)
+    if torch.is_grad_enabled() and any(p is not None and p.requires_grad for p in params):
+        return _EmbedTrain.apply(pix, *params)
+    return _embed_forward(pix, *[p.detach() if p is not None else None for p in params])
+
+
 def run_encoder(desc, pixel_values, num_layers, hidden_size, keep=None):
     """Allocate hidden states and call vllm_vit_forward.  ``keep``: None = materialise all L+1 states (what the
     reference does with output_hidden_states=True), or an iterable of indices (negative allowed) to keep."""
