@@ -14,7 +14,11 @@ rounded as operands -- in IEEE half times 2^14 / 2^4, an exact scale that keeps 
 where rounding stops being relative and the eps form of the bounds stops describing it -- one final rounding):
 test_attn_train_cpu.py keeps it inside the bounds on every case, so the bounds are ones a faithful implementation meets.
 Nothing here touches torch.cuda at import."""
+import functools
+
 import torch
+
+import bounds
 
 CASES = ("random", "spiked_key", "key0_dominant", "key0_far_below", "near_one_hot")
 
@@ -145,5 +149,4 @@ def worst_factor(got, ref, bound):
     return float(r.flatten()[i]), i
 
 
-def rel_rms(got, ref):
-    return float(((got.double() - ref) ** 2).mean().sqrt() / (ref ** 2).mean().sqrt().clamp_min(1e-300))
+rel_rms = functools.partial(bounds.rel_rms, clamp=True)

@@ -21,7 +21,7 @@ import math
 import torch
 import torch.nn.functional as F
 
-from vit_layer_train_inputs import bf16_ulp, excess_ulp, rel_rms  # noqa: F401  (the project's bound, re-exported)
+from bounds import bf16_ulp, excess_ulp, rel_rms  # noqa: F401  (the project's bound, re-exported)
 
 # (n, image, patch, C, bias, pixel dtype)
 CASES = [(3, 70, 14, 128, True, torch.bfloat16),     # S = 26, ragged everywhere, 78 rows: less than one wgrad tile

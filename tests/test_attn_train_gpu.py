@@ -9,6 +9,7 @@ import torch
 from torch import nn
 
 import attn_train_inputs as ati
+from bounds import P, stream
 from visionllm_amd import _lib
 from visionllm_amd.flash_attention import FlashAttention
 
@@ -22,14 +23,6 @@ DTYPES = [torch.bfloat16, torch.float16]
 # that, so at S = 1 it stops at fp32 accumulation's own resolution, 2^-20 of the tensor's rms -- 2^-12 of a bf16 spacing.
 RMS_FLOOR_S1 = 2.0 ** -20
 B, H = 3, 3          # 9 (batch, head) pairs: one full group of 8 on the XCDs and a group with one live member
-
-
-def stream():
-    return _lib.current_stream(torch.device(DEV))
-
-
-def P(t):
-    return _lib.ptr(t)
 
 
 def entry(name, dtype):

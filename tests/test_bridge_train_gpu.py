@@ -11,20 +11,13 @@ import pytest
 import torch
 from torch import nn
 
+from bounds import P, assert_bound, stream
 from visionllm_amd import _lib
 from visionllm_amd.bridge import build_vl_bridge
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 KINDS = ["linear", "mlp2x_gelu", "mlp3x_gelu", "internvl_mlp"]
-
-
-def P(t):
-    return _lib.ptr(t)
-
-
-def stream():
-    return _lib.current_stream(torch.device(DEV))
 
 
 def make_bridge(kind, cin, cout, bias=True, seed=0):
@@ -166,18 +159,6 @@ def test_project_hidden_state_still_refuses_under_grad():
 
 
 # ---- 6: building blocks against fp64 -----------------------------------------------------------------------------------------------
-def bf16_ulp(x):
-    e = torch.floor(torch.log2(x.abs().double().clamp_min(2.0 ** -126)))
-    return torch.pow(2.0, e - 7)
-
-
-def assert_bound(out, ref, mag, what, rel_mag=2.0 ** -17):
-    """|out - ref| <= 1 bf16 ulp(ref) + rel_mag * sum|terms| (the GEMM tests' bound)"""
-    err = (out.double() - ref).abs()
-    u = (err - rel_mag * mag).clamp_min(0) / bf16_ulp(ref)
-    assert u.max().item() <= 1.0, f"{what}: {u.max().item():.2f} bf16 ulp at {int(u.argmax())}"
-
-
 @pytest.mark.parametrize("M,N,K,pad", [(1000, 256, 128, 0), (77, 64, 640, 8), (4096, 1024, 256, 16), (2304, 512, 512, 24), (0, 128, 64, 0)])
 @pytest.mark.parametrize("with_db", [False, True])
 def test_wgrad_against_fp64(M, N, K, pad, with_db):

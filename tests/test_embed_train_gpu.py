@@ -12,6 +12,7 @@ import torch
 
 import embed_train_inputs as E
 import vit_layer_train_inputs as VI
+from bounds import P, stream
 from visionllm_amd import _lib
 from visionllm_amd.clip_vit import CLIPVisionModel, _CLIPVisionEmbeddings
 from visionllm_amd.intern_vit import InternVisionConfig, InternVisionEmbeddings, InternVisionModel
@@ -21,14 +22,6 @@ DEV = "cuda:0"
 NAN = float("nan")
 NAMES = ("w", "b", "cls", "pos")
 PAD = 24   # NaN elements in front of and behind every gradient view (48 bytes: the views stay 16-byte aligned)
-
-
-def P(t):
-    return _lib.ptr(t)
-
-
-def stream():
-    return _lib.current_stream(torch.device(DEV))
 
 
 def desc_of(c, image, patch):

@@ -11,11 +11,11 @@ import math
 import pytest
 import torch
 
+from bounds import P, assert_bound, stream
 from visionllm_amd import _lib
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-P = _lib.ptr
 CANARY = 7.0
 
 #        M      N     K   tile   pad
@@ -32,25 +32,8 @@ def bf(t):
     return t.to(torch.bfloat16)
 
 
-def stream():
-    return _lib.current_stream(torch.device(DEV))
-
-
 def bits(t):
     return t.contiguous().view(torch.int16)
-
-
-def bf16_ulp(x):
-    e = torch.floor(torch.log2(x.abs().double().clamp_min(2.0 ** -126)))
-    return torch.pow(2.0, e - 7)
-
-
-def assert_bound(out, ref, mag, what, rel_mag=2.0 ** -17):
-    """|out - ref| <= 1 bf16 ulp(ref) + 2^-17 sum|terms|: the bound of test_gemm256_persistent_residual."""
-    err = (out.double() - ref).abs()
-    u = (err - rel_mag * mag).clamp_min(0) / bf16_ulp(ref)
-    print(f"{what}: max excess {u.max().item():.3f} bf16 ulp")
-    assert u.max().item() <= 1.0, f"{what}: {u.max().item():.2f} bf16 ulp at {int(u.argmax())}"
 
 
 def gemm(c, x, w, b, res, ring, y=None, ldr=None):

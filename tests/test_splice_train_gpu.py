@@ -9,16 +9,13 @@ import pytest
 import torch
 
 import splice_train_inputs as SI
+from bounds import bf16_ulp, stream
 from splice_train_inputs import IMP
 from visionllm_amd import _lib
 from visionllm_amd.splice import splice_status_ok, splice_visual_tokens
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-
-
-def stream():
-    return _lib.current_stream(torch.device(DEV))
 
 
 def native_grads(c, need=(True, True), emb=None, feats=None, grad_out=None, **kw):
@@ -81,12 +78,6 @@ def test_pure_moves_are_exact_at_the_benchmark_shape():
 
 
 # ---- 2: the repeat rule: k terms added in fp32 in ascending slot order, rounded to bf16 once ---------------------------------------
-def bf16_ulp(x):
-    """Spacing of bf16 at the magnitude of the fp64 values ``x`` (8 significant bits; the smallest normal's below it)."""
-    _, e = torch.frexp(x.abs().clamp_min(2.0 ** -126))       # |x| = m 2^e, 0.5 <= m < 1
-    return torch.ldexp(torch.ones_like(x), e - 8)
-
-
 @pytest.mark.parametrize("name", ["repeat2", "repeat3"])
 @pytest.mark.parametrize("C", [64, 2056])
 def test_repeat_rule_against_fp64(name, C):

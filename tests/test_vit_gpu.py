@@ -16,6 +16,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from bounds import P, bf16_ulp, stream
 from conftest import golden_sd, load_golden
 from oracle import vit as V
 from visionllm_amd import _lib
@@ -31,25 +32,11 @@ def bf(t):
     return t.to(torch.bfloat16)
 
 
-def P(t):
-    return _lib.ptr(t)
-
-
-def stream():
-    return _lib.current_stream(torch.device(DEV))
-
-
 def close(out, ref, tol=1e-2, what=""):
     out, ref = out.float().cpu(), ref.float().cpu()
     scale = ref.abs().max().item() + 1e-6
     err = (out - ref).abs().max().item()
     assert err <= tol * scale, f"{what}: max err {err:.4g} vs scale {scale:.4g}"
-
-
-def bf16_ulp(x):
-    """Spacing of bf16 numbers at |x| (8 significand bits): 2^(floor(log2 |x|) - 7); the smallest normal's for |x| -> 0."""
-    e = torch.floor(torch.log2(x.abs().double().clamp_min(2.0 ** -126)))
-    return torch.pow(2.0, e - 7)
 
 
 _ULP_LOG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "ulp_table.jsonl")

@@ -12,20 +12,13 @@ import pytest
 import torch
 
 import vit_layer_train_inputs as I
+from bounds import P, stream
 from visionllm_amd import _lib
 from visionllm_amd.intern_vit import (InternRMSNorm, InternVisionConfig, InternVisionEncoder, InternVisionEncoderLayer, InternVisionModel)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 NAN = float("nan")
-
-
-def P(t):
-    return _lib.ptr(t)
-
-
-def stream():
-    return _lib.current_stream(torch.device(DEV))
 
 
 def nan_like(rows, cols):

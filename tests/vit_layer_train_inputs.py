@@ -23,6 +23,8 @@ import math
 
 import torch
 
+from bounds import bf16_ulp, excess_ulp, rel_rms  # noqa: F401  (the project's bound, re-exported)
+
 EPS = 1e-6
 NORM_SHAPES = [(300, 128), (77, 1024), (64, 3200), (33, 200)]          # (rows, C) of the row-wise kernels' tests
 # (hidden, heads, inter, B, S, qk_normalization, qkv_bias)
@@ -30,22 +32,6 @@ LAYER_CONFIGS = [(128, 2, 256, 2, 37, True, False),
                  (256, 2, 512, 3, 65, False, True),                     # head_dim 128
                  (1024, 16, 4096, 2, 577, True, False),                 # the 8-phase GEMM and split-wgrad routes
                  (3200, 25, 12800, 1, 130, True, False)]                # InternViT-6B widths
-
-
-def bf16_ulp(x):
-    e = torch.floor(torch.log2(x.abs().double().clamp_min(2.0 ** -126)))
-    return torch.pow(2.0, e - 7)
-
-
-def excess_ulp(out, ref, mag, rel_mag=2.0 ** -17):
-    """max over elements of (|out - ref| - rel_mag * mag) / ulp(ref): the bound holds when this is <= 1."""
-    err = (out.double() - ref.double()).abs()
-    return ((err - rel_mag * mag).clamp_min(0) / bf16_ulp(ref)).max().item()
-
-
-def rel_rms(a, ref):
-    ref = ref.double()
-    return (a.double() - ref).pow(2).mean().sqrt().item() / (ref.pow(2).mean().sqrt().item() + 1e-300)
 
 
 # ---- the reference's statements -------------------------------------------------------------------------------------------------------

@@ -208,3 +208,10 @@ def workspace(device, nbytes, slot=0):
         buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
         _workspaces[key] = buf
     return buf
+
+
+def sized_workspace(device, nbytes, what, slot=0):
+    """``workspace()`` for the answer ``nbytes`` of the size query named ``what`` -> (buffer, byte count to pass to C).  A negative
+    answer is the query refusing its arguments: raised with the library's error text."""
+    check(0 if nbytes >= 0 else -1, what)
+    return workspace(device, nbytes, slot), nbytes

@@ -74,8 +74,7 @@ def _run(desc, hidden, n, T, C):
     T_out = T // 4 if desc.pixel_shuffle else T
     out = torch.empty((n, T_out, desc.out_features), dtype=torch.bfloat16, device=hidden.device)
     with torch.cuda.device(hidden.device):
-        wsb = lib.vllm_bridge_workspace_bytes(ctypes.byref(desc), n, T)
-        ws = _lib.workspace(hidden.device, max(wsb, 1))
+        ws, wsb = _lib.sized_workspace(hidden.device, lib.vllm_bridge_workspace_bytes(ctypes.byref(desc), n, T), "vllm_bridge_workspace_bytes")
         _lib.check(lib.vllm_bridge_forward(ctypes.byref(desc), _lib.ptr(hidden), n, T, C, _lib.ptr(out), _lib.ptr(ws),
                                            wsb, _lib.current_stream(hidden.device)), "vllm_bridge_forward")
     return out
@@ -183,9 +182,8 @@ class _BridgeTrain(torch.autograd.Function):
         act = [torch.empty((rows, cout), dtype=torch.bfloat16, device=dev) for _ in range(depth - 1)]
         ln = torch.empty((rows, d.in_features), dtype=torch.bfloat16, device=dev) if d.kind == _lib.BRIDGE_INTERNVL_MLP else None
         with torch.cuda.device(dev):
-            wsb = L.vllm_bridge_backward_workspace_bytes(ctypes.byref(d), rows, 0)
-            _lib.check(0 if wsb >= 0 else -1, "vllm_bridge_backward_workspace_bytes")
-            ws = _lib.workspace(dev, max(wsb, 1))
+            ws, wsb = _lib.sized_workspace(dev, L.vllm_bridge_backward_workspace_bytes(ctypes.byref(d), rows, 0),
+                                           "vllm_bridge_backward_workspace_bytes")
             _lib.check(L.vllm_bridge_forward_train(ctypes.byref(d), _lib.ptr(x), rows, _lib.ptr(out), _ptr_array(pre), _ptr_array(act),
                                                    _lib.ptr(ln), _lib.ptr(ws), wsb, _lib.current_stream(dev)), "vllm_bridge_forward_train")
         ctx.meta = (kind, depth, eps)
@@ -212,9 +210,8 @@ class _BridgeTrain(torch.autograd.Function):
         gx = torch.empty((rows, d.in_features), dtype=torch.bfloat16, device=dev) if need_x else None
         L = _lib.lib()
         with torch.cuda.device(dev):
-            wsb = L.vllm_bridge_backward_workspace_bytes(ctypes.byref(d), rows, int(need_x))
-            _lib.check(0 if wsb >= 0 else -1, "vllm_bridge_backward_workspace_bytes")
-            ws = _lib.workspace(dev, max(wsb, 1))
+            ws, wsb = _lib.sized_workspace(dev, L.vllm_bridge_backward_workspace_bytes(ctypes.byref(d), rows, int(need_x)),
+                                           "vllm_bridge_backward_workspace_bytes")
             _lib.check(L.vllm_bridge_backward(ctypes.byref(d), _lib.ptr(x), rows, _lib.ptr(g), _ptr_array(pre), _ptr_array(act), _lib.ptr(ln),
                                               _lib.ptr(gx), _ptr_array(gw), _ptr_array(gb), _lib.ptr(gln[0]), _lib.ptr(gln[1]),
                                               _lib.ptr(ws), wsb, _lib.current_stream(dev)), "vllm_bridge_backward")

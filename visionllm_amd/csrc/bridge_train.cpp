@@ -8,15 +8,11 @@
 //     first Linear: dX = dY_0 W_0 (bf16), or for internvl_mlp dZ in fp32 (VLLM_EPI_F32) into the LayerNorm backward (bridge_bwd.hip).
 // No allocation, no synchronisation, one stream; the workspace is the caller's.
 #include <algorithm>
-#include "kernels.hpp"
+#include "orchestrate.hpp"
 
 using namespace vllm;
 
-#define TRY(x) do { int rc__ = (x); if (rc__ != VLLM_OK) return rc__; } while (0)
-
 namespace {
-inline long al256(long x) { return (x + 255) & ~255L; }
-
 int check_train_desc(const VllmBridgeDesc *d, const char *who)
 {
     VLLM_REQUIRE(d && d->depth >= 1 && d->depth <= 4, "%s: bad descriptor", who);
@@ -40,34 +36,20 @@ TrainWs train_ws_layout(const VllmBridgeDesc *d, long rows, bool need_gx)
     const long Cin = d->in_features, Cout = d->out_features;
     const bool ivl = d->kind == VLLM_BRIDGE_INTERNVL_MLP;
     TrainWs w;
-    long off = 0;
-    auto take = [&](long b) { long o = off; off += al256(b); return o; };
+    Carver cv;
     // (the sk slot first: the training forward uses only it, from the workspace's start)
     w.sk_bytes = rows >= 1024 ? SK_SCRATCH_BYTES : 0;   // stream-K tail of the 8-phase GEMM, as vllm_bridge_forward sizes it
-    w.sk = take(w.sk_bytes);
-    w.wt = take(Cout * std::max(d->depth > 1 ? Cout : 0L, (ivl || need_gx) ? Cin : 0L) * 2);   // W_i^T
-    w.dy0 = take(d->depth > 1 ? rows * Cout * 2 : 0);   // dY of the hidden Linears, ping-pong
-    w.dy1 = take(d->depth > 2 ? rows * Cout * 2 : 0);
-    w.dz = take(ivl ? rows * Cin * 4 : 0);              // LayerNorm output gradient, fp32
+    w.sk = cv.take(w.sk_bytes);
+    w.wt = cv.take(Cout * std::max(d->depth > 1 ? Cout : 0L, (ivl || need_gx) ? Cin : 0L) * 2);   // W_i^T
+    w.dy0 = cv.take(d->depth > 1 ? rows * Cout * 2 : 0);   // dY of the hidden Linears, ping-pong
+    w.dy1 = cv.take(d->depth > 2 ? rows * Cout * 2 : 0);
+    w.dz = cv.take(ivl ? rows * Cin * 4 : 0);              // LayerNorm output gradient, fp32
     long wg = 0;
     for (int i = 0; i < d->depth; ++i) wg = std::max(wg, gemm_wgrad_workspace_bytes((int)rows, (int)Cout, (int)(i == 0 ? Cin : Cout)));
-    w.wg = take(wg);
-    w.lnp = take(ivl ? ln_bwd_workspace_bytes(rows, (int)Cin) : 0);
-    w.total = off;
+    w.wg = cv.take(wg);
+    w.lnp = cv.take(ivl ? ln_bwd_workspace_bytes(rows, (int)Cin) : 0);
+    w.total = cv.off;
     return w;
-}
-
-// the GEMM call of vllm_bridge_forward (kernels.hpp gemm()), with the pre-activation output of EPI_GELU_SAVE
-int gemm_t(hipStream_t st, int epi, const uint16_t *X, int ldx, const uint16_t *W, int ldw, const uint16_t *bias, uint16_t *Y, int ldy,
-           long M, int N, int K, const uint16_t *res, int ldr, uint16_t *pre, void *sk, long sk_bytes)
-{
-    GemmArgs a;
-    gemm_set_scratch(a, sk, sk_bytes);
-    a.X = X; a.W = W; a.Y = Y; a.bias = bias; a.scale = nullptr; a.res = res;
-    a.M = (int)M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldr = ldr; a.P = 0; a.mt = a.nt = 0; a.xP = 0;
-    a.variant = gemm_variant_override(); a.variant256 = 0; a.direct_store = gemm_direct_store();
-    a.pre = pre;
-    return gemm_bf16_launch(epi, a, st);
 }
 }  // namespace
 
@@ -95,7 +77,7 @@ extern "C" int vllm_bridge_forward_train(const VllmBridgeDesc *d, const uint16_t
                  "bridge_forward_train: workspace too small (%ld < %ld bytes) or misaligned", ws_bytes, sk_bytes);
     hipStream_t st = (hipStream_t)stream;
     void *sk = sk_bytes ? workspace : nullptr;
-    if (sk) VLLM_REQUIRE(hipMemsetAsync(sk, 0, SK_FLAG_BYTES, st) == hipSuccess, "bridge_forward_train: flag reset failed");
+    TRY(sk_scratch_reset(sk, st, "bridge_forward_train"));
     const uint16_t *in = x;
     if (ivl) {
         TRY(norm_bf16_launch(false, x, Cin, d->ln_w, d->ln_b, saved_ln, Cin, rows, Cin, d->ln_eps, st));
@@ -104,8 +86,11 @@ extern "C" int vllm_bridge_forward_train(const VllmBridgeDesc *d, const uint16_t
     int K = Cin;
     for (int i = 0; i < d->depth; ++i) {
         const bool last = i == d->depth - 1;
-        if (last) TRY(gemm_t(st, EPI_BIAS, in, K, d->w[i], K, d->b[i], out, Cout, rows, Cout, K, nullptr, 0, nullptr, sk, sk_bytes));
-        else TRY(gemm_t(st, EPI_GELU_SAVE, in, K, d->w[i], K, d->b[i], saved_act[i], Cout, rows, Cout, K, nullptr, 0, saved_pre[i], sk, sk_bytes));
+        // the GEMM call of vllm_bridge_forward; a hidden Linear's epilogue also leaves its pre-activation for the backward
+        GemmArgs a = gemm_args(in, K, d->w[i], K, d->b[i], last ? out : saved_act[i], Cout, rows, Cout, K);
+        if (!last) a.pre = saved_pre[i];
+        gemm_set_scratch(a, sk, sk_bytes);
+        TRY(gemm_bf16_launch(last ? EPI_BIAS : EPI_GELU_SAVE, a, st));
         if (!last) in = saved_act[i];
         K = Cout;
     }
@@ -129,13 +114,9 @@ extern "C" int vllm_bridge_backward(const VllmBridgeDesc *d, const uint16_t *x, 
                  "bridge_backward: gradients must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     if (rows == 0) {   // no rows: every parameter gradient is an empty sum
-        for (int i = 0; i < D; ++i) {
-            VLLM_REQUIRE(hipMemsetAsync(grad_w[i], 0, (size_t)Cout * (i == 0 ? Cin : Cout) * 2, st) == hipSuccess, "bridge_backward: memset failed");
-            if (grad_b && grad_b[i]) VLLM_REQUIRE(hipMemsetAsync(grad_b[i], 0, (size_t)Cout * 2, st) == hipSuccess, "bridge_backward: memset failed");
-        }
-        if (grad_ln_w) VLLM_REQUIRE(hipMemsetAsync(grad_ln_w, 0, (size_t)Cin * 2, st) == hipSuccess, "bridge_backward: memset failed");
-        if (grad_ln_b) VLLM_REQUIRE(hipMemsetAsync(grad_ln_b, 0, (size_t)Cin * 2, st) == hipSuccess, "bridge_backward: memset failed");
-        return VLLM_OK;
+        for (int i = 0; i < D; ++i)
+            TRY(zero_bf16(st, "bridge_backward", {{grad_w[i], (long)Cout * (i == 0 ? Cin : Cout)}, {grad_b ? grad_b[i] : nullptr, Cout}}));
+        return zero_bf16(st, "bridge_backward", {{grad_ln_w, Cin}, {grad_ln_b, Cin}});
     }
     VLLM_REQUIRE(x && grad_out && aligned16(x) && aligned16(grad_out), "bridge_backward: x and grad_out must be 16-byte aligned device pointers");
     VLLM_REQUIRE(!ivl || (saved_ln && aligned16(saved_ln)), "bridge_backward: internvl_mlp needs saved_ln");
@@ -148,7 +129,7 @@ extern "C" int vllm_bridge_backward(const VllmBridgeDesc *d, const uint16_t *x, 
                  ws_bytes, w.total);
     char *ws = (char *)workspace;
     void *sk = w.sk_bytes ? ws + w.sk : nullptr;
-    if (sk) VLLM_REQUIRE(hipMemsetAsync(sk, 0, SK_FLAG_BYTES, st) == hipSuccess, "bridge_backward: flag reset failed");
+    TRY(sk_scratch_reset(sk, st, "bridge_backward"));
     uint16_t *wt = (uint16_t *)(ws + w.wt);
     uint16_t *bufs[2] = {(uint16_t *)(ws + w.dy0), (uint16_t *)(ws + w.dy1)};
     const bool dx0 = need_gx || (ivl && (grad_ln_w || grad_ln_b));   // the first Linear's input gradient is needed
@@ -160,18 +141,16 @@ extern "C" int vllm_bridge_backward(const VllmBridgeDesc *d, const uint16_t *x, 
                               w.total - w.wg, st));
         if (i > 0) {
             uint16_t *nxt = bufs[(D - 1 - i) & 1];
-            TRY(transpose_bf16_launch(d->w[i], Cout, wt, Cout, Cout, Cout, st));
-            TRY(gemm_t(st, EPI_GELU_BWD, dy, Cout, wt, Cout, nullptr, nxt, Cout, rows, Cout, Cout, saved_pre[i - 1], Cout, nullptr, sk, w.sk_bytes));
+            TRY(linear_dgrad(st, EPI_GELU_BWD, dy, d->w[i], Cout, Cout, rows, wt, nxt, saved_pre[i - 1], sk, w.sk_bytes));
             dy = nxt;
         } else if (dx0) {
-            TRY(transpose_bf16_launch(d->w[0], Cin, wt, Cout, Cout, Cin, st));   // W_0 [Cout, Cin] -> [Cin, Cout]
             if (ivl) {
                 float *dz = (float *)(ws + w.dz);
-                TRY(gemm_t(st, EPI_F32, dy, Cout, wt, Cout, nullptr, (uint16_t *)dz, Cin, rows, Cin, Cout, nullptr, 0, nullptr, sk, w.sk_bytes));
+                TRY(linear_dgrad(st, EPI_F32, dy, d->w[0], Cout, Cin, rows, wt, dz, nullptr, sk, w.sk_bytes));
                 TRY(ln_bwd_launch(x, Cin, dz, Cin, d->ln_w, d->ln_eps, rows, Cin, grad_x, Cin, grad_ln_w, grad_ln_b, ws + w.lnp,
                                   w.total - w.lnp, st));
             } else {
-                TRY(gemm_t(st, EPI_BIAS, dy, Cout, wt, Cout, nullptr, grad_x, Cin, rows, Cin, Cout, nullptr, 0, nullptr, sk, w.sk_bytes));
+                TRY(linear_dgrad(st, EPI_BIAS, dy, d->w[0], Cout, Cin, rows, wt, grad_x, nullptr, sk, w.sk_bytes));
             }
         }
     }

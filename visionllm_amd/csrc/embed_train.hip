@@ -17,7 +17,7 @@
 // The backward keeps nothing from the forward: the im2col matrix is rebuilt from the pixels.  No allocation, no synchronisation, one stream.
 #include <algorithm>
 #include "common.hpp"
-#include "kernels.hpp"
+#include "orchestrate.hpp"
 
 namespace vllm {
 namespace {
@@ -164,8 +164,6 @@ inline unsigned grid_for(long n)
     return (unsigned)b;
 }
 
-inline long al256(long x) { return (x + 255) & ~255L; }
-
 struct Dims { int C, ps, img, g, P, S, K, kpad; };
 
 int check_embed(const VllmVitEmbed *d, int n, Dims *o, const char *who)
@@ -190,16 +188,15 @@ struct Ws { long sk, wp, col, wg, wg_bytes, bp, nb, total; };
 Ws ws_layout(const Dims &q, int n)
 {
     Ws w;
-    long off = 0;
-    auto take = [&](long b) { long o = off; off += al256(b); return o; };
-    w.sk = take(SK_SCRATCH_BYTES);
-    w.wp = take((long)q.C * q.kpad * 2);
-    w.col = take((long)n * q.S * q.kpad * 2);
+    Carver cv;
+    w.sk = cv.take(SK_SCRATCH_BYTES);
+    w.wp = cv.take((long)q.C * q.kpad * 2);
+    w.col = cv.take((long)n * q.S * q.kpad * 2);
     w.wg_bytes = std::max(0L, gemm_wgrad_workspace_bytes((int)((long)n * q.S), q.C, q.kpad));
-    w.wg = take(w.wg_bytes);
+    w.wg = cv.take(w.wg_bytes);
     w.nb = (q.S + TS_ROWS - 1) / TS_ROWS;
-    w.bp = take(w.nb * q.C * 4);
-    w.total = off;
+    w.bp = cv.take(w.nb * q.C * 4);
+    w.total = cv.off;
     return w;
 }
 
@@ -207,8 +204,6 @@ Ws ws_layout(const Dims &q, int n)
 }  // namespace vllm
 
 using namespace vllm;
-
-#define TRY(x) do { int rc__ = (x); if (rc__ != VLLM_OK) return rc__; } while (0)
 
 extern "C" int vllm_vit_embed_sizeof(void) { return (int)sizeof(VllmVitEmbed); }
 
@@ -235,7 +230,7 @@ extern "C" int vllm_vit_embed_forward(const VllmVitEmbed *d, const void *pixels,
     void *sk = ws + w.sk;
     uint16_t *wp = (uint16_t *)(ws + w.wp), *col = (uint16_t *)(ws + w.col);
     const int C = q.C;
-    VLLM_REQUIRE(hipMemsetAsync(sk, 0, SK_FLAG_BYTES, st) == hipSuccess, "vit_embed_forward: flag reset failed");
+    TRY(sk_scratch_reset(sk, st, "vit_embed_forward"));
     if (q.K % 2 == 0) VLLM_LAUNCH((embed_pad_weight_kernel<2>), dim3(grid_for((long)C * q.kpad / 2)), dim3(256), 0, st, d->patch_w, wp, C, q.K, q.kpad);
     else VLLM_LAUNCH((embed_pad_weight_kernel<1>), dim3(grid_for((long)C * q.kpad)), dim3(256), 0, st, d->patch_w, wp, C, q.K, q.kpad);
     VLLM_CHECK_LAUNCH("embed_pad_weight_kernel");
@@ -258,10 +253,7 @@ extern "C" int vllm_vit_embed_backward(const VllmVitEmbed *d, const void *pixels
     hipStream_t st = (hipStream_t)stream;
     const int C = q.C, S = q.S;
     if (n == 0) {   // no tiles: every gradient is an empty sum
-        struct { uint16_t *p; long n; } z[] = {{grad_patch_w, (long)C * q.K}, {grad_patch_b, C}, {grad_cls, C}, {grad_pos, (long)S * C}};
-        for (auto &e : z)
-            if (e.p) VLLM_REQUIRE(hipMemsetAsync(e.p, 0, (size_t)e.n * 2, st) == hipSuccess, "vit_embed_backward: memset failed");
-        return VLLM_OK;
+        return zero_bf16(st, "vit_embed_backward", {{grad_patch_w, (long)C * q.K}, {grad_patch_b, C}, {grad_cls, C}, {grad_pos, (long)S * C}});
     }
     const bool sums = grad_patch_b || grad_cls || grad_pos;
     if (!sums && !grad_patch_w) return VLLM_OK;

@@ -319,19 +319,27 @@ int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
 
 using namespace vllm;
 
+// The VLLM_GEMM_FORCE_* requests OR-ed into an entry point's `epilogue` word (tests / tuning), decoded in one place.  `accept` is the
+// mask of bits the entry reads; the others are ignored there.  FORCE_128 / _256 / _192 are the values 1 / 2 / 3 of one two-bit field.
+constexpr int FORCE_TILE = VLLM_GEMM_FORCE_192;
+static void gemm_force_bits(GemmArgs &a, int epilogue, int accept)
+{
+    const int e = epilogue & accept, tile = e & FORCE_TILE;
+    if (tile) a.variant = tile >> 8;
+    if (e & VLLM_GEMM_FORCE_MF32) a.variant = 4;
+    if (e & VLLM_GEMM_FORCE_TILEWISE) a.no_persist = 1;
+    if (tile == VLLM_GEMM_FORCE_192) { a.variant = 2; a.variant256 = 3; }
+    else if (tile == VLLM_GEMM_FORCE_256) a.variant256 = 4;
+}
+
 extern "C" int vllm_gemm_bf16(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, int M, int N,
                               int K, int ldx, int ldw, int ldy, int epilogue, const uint16_t *scale,
                               const uint16_t *res, int ldr, int P, vllm_stream_t stream)
 {
     VLLM_REQUIRE(X && W && Y, "vllm_gemm_bf16: null pointer");
-    GemmArgs a;
-    a.X = X; a.W = W; a.Y = Y; a.bias = bias; a.scale = scale; a.res = res;
-    a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldr = ldr; a.P = P; a.mt = a.nt = 0; a.xP = 0; a.variant = gemm_variant_override(); a.variant256 = 0; a.direct_store = gemm_direct_store();
-    if ((epilogue >> 8) & 3) a.variant = (epilogue >> 8) & 3;   // VLLM_GEMM_FORCE_* (tests / tuning)
-    if (epilogue & 0x800) a.variant = 4;                         // VLLM_GEMM_FORCE_MF32
-    if (epilogue & 0x1000) a.no_persist = 1;                     // VLLM_GEMM_FORCE_TILEWISE
-    if (((epilogue >> 8) & 3) == 3) { a.variant = 2; a.variant256 = 3; }   // VLLM_GEMM_FORCE_192
-    else if (((epilogue >> 8) & 3) == 2) a.variant256 = 4;
+    GemmArgs a = gemm_args(X, ldx, W, ldw, bias, Y, ldy, M, N, K);
+    a.scale = scale; a.res = res; a.ldr = ldr; a.P = P;
+    gemm_force_bits(a, epilogue, FORCE_TILE | VLLM_GEMM_FORCE_MF32 | VLLM_GEMM_FORCE_TILEWISE);
     return gemm_bf16_launch(epilogue & 0xff, a, (hipStream_t)stream);
 }
 
@@ -341,13 +349,9 @@ extern "C" int vllm_gemm_bf16_residual_save(const uint16_t *X, const uint16_t *W
 {
     VLLM_REQUIRE(X && W && Y && pre && res, "vllm_gemm_bf16_residual_save: null pointer");
     VLLM_REQUIRE((epilogue & 0xff) == EPI_RESIDUAL, "vllm_gemm_bf16_residual_save: the epilogue is VLLM_EPI_RESIDUAL (plus VLLM_GEMM_FORCE_* bits)");
-    GemmArgs a;
-    a.X = X; a.W = W; a.Y = Y; a.bias = bias; a.scale = scale; a.res = res; a.pre = pre;
-    a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldr = ldr; a.P = 0; a.mt = a.nt = 0; a.xP = 0; a.variant = gemm_variant_override(); a.variant256 = 0; a.direct_store = gemm_direct_store();
-    if ((epilogue >> 8) & 3) a.variant = (epilogue >> 8) & 3;   // VLLM_GEMM_FORCE_* as vllm_gemm_bf16 reads them
-    if (epilogue & 0x800) a.variant = 4;
-    if (((epilogue >> 8) & 3) == 3) { a.variant = 2; a.variant256 = 3; }
-    else if (((epilogue >> 8) & 3) == 2) a.variant256 = 4;
+    GemmArgs a = gemm_args(X, ldx, W, ldw, bias, Y, ldy, M, N, K);
+    a.scale = scale; a.res = res; a.ldr = ldr; a.pre = pre;
+    gemm_force_bits(a, epilogue, FORCE_TILE | VLLM_GEMM_FORCE_MF32);   // (VLLM_GEMM_FORCE_TILEWISE is not read here)
     return gemm_bf16_launch(EPI_RESIDUAL_SAVE, a, (hipStream_t)stream);
 }
 
@@ -357,12 +361,11 @@ extern "C" int vllm_gemm_bf16_ln(const uint16_t *X, const uint16_t *W, const uin
                                  const float *ln_bias, vllm_stream_t stream)
 {
     VLLM_REQUIRE(X && W && Y, "vllm_gemm_bf16_ln: null pointer");
-    GemmArgs a;
-    a.X = X; a.W = W; a.Y = Y; a.bias = bias; a.scale = scale; a.res = res;
-    a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldr = ldr; a.P = 0; a.mt = a.nt = 0; a.xP = 0; a.variant = 0; a.variant256 = 0; a.direct_store = gemm_direct_store();
-    if (((epilogue >> 8) & 3) == 3) { a.variant = 2; a.variant256 = 3; }
-    else if (((epilogue >> 8) & 3) == 2) { a.variant = 2; a.variant256 = 4; }
-    if (epilogue & 0x1000) a.no_persist = 1;
+    GemmArgs a = gemm_args(X, ldx, W, ldw, bias, Y, ldy, M, N, K);
+    a.scale = scale; a.res = res; a.ldr = ldr;
+    a.variant = 0;   // only the 8-phase kernel folds a norm: the process-wide variant override does not apply ...
+    if ((epilogue & FORCE_TILE) == VLLM_GEMM_FORCE_128) epilogue &= ~FORCE_TILE;   // ... and neither does a forced 128x128 kernel
+    gemm_force_bits(a, epilogue, FORCE_TILE | VLLM_GEMM_FORCE_TILEWISE);
     a.ln_out = ln_out; a.ln_in = ln_in; a.ln_slots = ln_slots; a.ln_cols = K; a.ln_rms = ln_rms; a.ln_eps = ln_eps;
     a.ln_colsum = ln_colsum; a.ln_bias = ln_bias;
     // round 5: RMSNorm rows of a hidden size other than four column tiles use the WIDE statistics layout ([M][16] floats, header)
@@ -383,17 +386,12 @@ extern "C" int vllm_gemm_bf16_sk(const uint16_t *X, const uint16_t *W, const uin
 {
     VLLM_REQUIRE(X && W && Y, "vllm_gemm_bf16_sk: null pointer");
     VLLM_REQUIRE(!scratch || (scratch_bytes >= SK_FLAG_BYTES + SK_SLOT_BYTES && aligned16(scratch)), "vllm_gemm_bf16_sk: scratch too small or misaligned");
-    GemmArgs a;
-    gemm_set_scratch(a, scratch, scratch_bytes);
     // the flags are reset in front of every call of THIS entry (a memset node of 4 KB: a call that died half way, or a caller that
     // never zeroed its scratch, must not hand a stale "slot ready" to the next one); the orchestrators reset theirs once per forward
     if (scratch) VLLM_REQUIRE(hipMemsetAsync(scratch, 0, SK_FLAG_BYTES, (hipStream_t)stream) == hipSuccess, "vllm_gemm_bf16_sk: flag reset failed");
-    a.X = X; a.W = W; a.Y = Y; a.bias = bias; a.scale = scale; a.res = res;
-    a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldr = ldr; a.P = P; a.mt = a.nt = 0; a.xP = 0; a.variant = gemm_variant_override(); a.variant256 = 0; a.direct_store = gemm_direct_store();
-    if ((epilogue >> 8) & 3) a.variant = (epilogue >> 8) & 3;
-    if (epilogue & 0x800) a.variant = 4;
-    if (epilogue & 0x1000) a.no_persist = 1;
-    if (((epilogue >> 8) & 3) == 3) { a.variant = 2; a.variant256 = 3; }
-    else if (((epilogue >> 8) & 3) == 2) a.variant256 = 4;
+    GemmArgs a = gemm_args(X, ldx, W, ldw, bias, Y, ldy, M, N, K);
+    a.scale = scale; a.res = res; a.ldr = ldr; a.P = P;
+    gemm_set_scratch(a, scratch, scratch_bytes);
+    gemm_force_bits(a, epilogue, FORCE_TILE | VLLM_GEMM_FORCE_MF32 | VLLM_GEMM_FORCE_TILEWISE);
     return gemm_bf16_launch(epilogue & 0xff, a, (hipStream_t)stream);
 }

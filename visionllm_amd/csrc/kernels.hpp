@@ -24,22 +24,24 @@ enum GemmEpilogue : int {
 // the residual epilogue and its training form share every schedule decision and the arithmetic of Y
 constexpr bool epi_is_residual(int epi) { return epi == EPI_RESIDUAL || epi == EPI_RESIDUAL_SAVE; }
 
+// Every member has a default (null / zero), so a fill site names only what it uses; gemm_args() below sets the core operands and the
+// process-wide schedule options.  A kernel argument: defaults may be added, members are neither reordered nor resized.
 struct GemmArgs {
-    const uint16_t *X;      // [M, K] row stride ldx
-    const uint16_t *W;      // [N, K] row stride ldw
-    uint16_t *Y;            // [M', N] row stride ldy
-    const uint16_t *bias;   // [N] or null
-    const uint16_t *scale;  // [N] layer-scale (EPI_RESIDUAL) or null
-    const uint16_t *res;    // [M, N] residual, row stride ldr (EPI_RESIDUAL); [P+1, N] position table (EPI_EMBED)
-    int M, N, K;
-    int ldx, ldw, ldy, ldr;
-    int P;                  // patches per image (EPI_EMBED)
-    int mt, nt;             // tile counts (filled by the launcher)
-    int xP;                 // >0: X is [n, 1+xP, K] and row m reads X row m + m/xP + 1 (CLS rows skipped)
-    int variant;            // 0 auto, 1 force 128x128 kernel, 2 force 256x256 8-phase kernel (tuning / tests)
-    int variant256;         // 8-phase kernel block rows: 0 auto, 3 -> 192, 4 -> 256
+    const uint16_t *X = nullptr;      // [M, K] row stride ldx
+    const uint16_t *W = nullptr;      // [N, K] row stride ldw
+    uint16_t *Y = nullptr;            // [M', N] row stride ldy
+    const uint16_t *bias = nullptr;   // [N] or null
+    const uint16_t *scale = nullptr;  // [N] layer-scale (EPI_RESIDUAL) or null
+    const uint16_t *res = nullptr;    // [M, N] residual, row stride ldr (EPI_RESIDUAL); [P+1, N] position table (EPI_EMBED)
+    int M = 0, N = 0, K = 0;
+    int ldx = 0, ldw = 0, ldy = 0, ldr = 0;
+    int P = 0;              // patches per image (EPI_EMBED)
+    int mt = 0, nt = 0;     // tile counts (filled by the launcher)
+    int xP = 0;             // >0: X is [n, 1+xP, K] and row m reads X row m + m/xP + 1 (CLS rows skipped)
+    int variant = 0;        // 0 auto, 1 force 128x128 kernel, 2 force 256x256 8-phase kernel (tuning / tests)
+    int variant256 = 0;     // 8-phase kernel block rows: 0 auto, 3 -> 192, 4 -> 256
     int half_tail = 0;      // persistent schedule (launcher): 1 = the tiles of the last, incomplete round run as two half-height tiles each
-    int direct_store;       // 8-phase epilogue: 0 through LDS, 1 straight from the accumulator layout, 2 automatic
+    int direct_store = 0;   // 8-phase epilogue: 0 through LDS, 1 straight from the accumulator layout, 2 automatic
     // EPI_MSDA only: output features [0, nsplit) come from W / bias and become sampling locations in Y (fp32, ldy),
     // features [nsplit, N) come from W2 / bias2 and become the per-head softmax over L*P == 16 logits in Y2 (fp32, ldy2)
     const uint16_t *W2 = nullptr, *bias2 = nullptr;
@@ -156,14 +158,28 @@ inline void gemm_set_scratch(GemmArgs &a, void *scratch, long bytes)
     a.sk_ws_bytes = bytes - SK_FLAG_BYTES;
 }
 
+// The one place a GemmArgs gets its core operands: Y[M, N] = epilogue(X[M, K] W[N, K]^T + bias) under the process-wide schedule options.
+// Whatever else a call uses (scale, res / ldr, P, xP, pre, the ln_* block, the MSDA block, the scratch) it assigns by name behind this.
+// (M is the orchestrators' long row count, which they have checked against 2^31.)
+inline GemmArgs gemm_args(const uint16_t *X, int ldx, const uint16_t *W, int ldw, const uint16_t *bias, uint16_t *Y, int ldy, long M, int N,
+                          int K)
+{
+    GemmArgs a;
+    a.X = X; a.W = W; a.Y = Y; a.bias = bias;
+    a.M = (int)M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldy = ldy;
+    a.variant = gemm_variant_override();
+    a.direct_store = gemm_direct_store();
+    return a;
+}
+
+// the common case in one call
 inline int gemm(hipStream_t st, int epi, const uint16_t *X, int ldx, const uint16_t *W, int ldw, const uint16_t *bias,
                 uint16_t *Y, int ldy, int M, int N, int K, const uint16_t *scale = nullptr, const uint16_t *res = nullptr,
                 int ldr = 0, int P = 0, int xP = 0, void *scratch = nullptr, long scratch_bytes = 0)
 {
-    GemmArgs a;
+    GemmArgs a = gemm_args(X, ldx, W, ldw, bias, Y, ldy, M, N, K);
+    a.scale = scale; a.res = res; a.ldr = ldr; a.P = P; a.xP = xP;
     gemm_set_scratch(a, scratch, scratch_bytes);
-    a.X = X; a.W = W; a.Y = Y; a.bias = bias; a.scale = scale; a.res = res;
-    a.M = M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldr = ldr; a.P = P; a.mt = a.nt = 0; a.xP = xP; a.variant = gemm_variant_override(); a.variant256 = 0; a.direct_store = gemm_direct_store();
     return gemm_bf16_launch(epi, a, st);
 }
 

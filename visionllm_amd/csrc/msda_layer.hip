@@ -15,7 +15,7 @@
 // bf16 itself.  The layer is then 4 launches: value GEMM, query GEMM, operator, output GEMM.
 #include "common.hpp"
 #include <stdlib.h>
-#include "kernels.hpp"
+#include "orchestrate.hpp"
 #include "msda_sample.hpp"
 
 namespace vllm {
@@ -129,8 +129,6 @@ inline bool msda_layer_value_bf16()
     return g_layer_value_bf16 != 0;
 }
 
-inline long align256(long x) { return (x + 255) & ~255L; }
-
 struct LayerWs {
     long value, off, logit, opout, opout_bf16, total;
 };
@@ -138,13 +136,13 @@ LayerWs layer_ws(const VllmMsdaLayerDesc *d, long B, long Lq, long S)
 {
     const long C = d->d_model, MLP = (long)d->n_heads * d->n_levels * d->n_points;
     LayerWs w;
-    long p = 0;
-    w.value = p; p += align256(B * S * C * 4);
-    w.off = p; p += align256(B * Lq * MLP * 2 * 4);
-    w.logit = p; p += align256(B * Lq * MLP * 4);
-    w.opout = p; p += align256(B * Lq * C * 4);
-    w.opout_bf16 = p; p += align256(B * Lq * C * 2);
-    w.total = p;
+    Carver cv;
+    w.value = cv.take(B * S * C * 4);
+    w.off = cv.take(B * Lq * MLP * 2 * 4);
+    w.logit = cv.take(B * Lq * MLP * 4);
+    w.opout = cv.take(B * Lq * C * 4);
+    w.opout_bf16 = cv.take(B * Lq * C * 2);
+    w.total = cv.off;
     return w;
 }
 
@@ -186,12 +184,6 @@ int msda_layer_value_bf16_set(int v) { const int old = msda_layer_value_bf16() ?
 }  // namespace vllm
 
 using namespace vllm;
-
-#define TRY(x)                      \
-    do {                            \
-        const int rc__ = (x);       \
-        if (rc__ != VLLM_OK) return rc__; \
-    } while (0)
 
 extern "C" unsigned long vllm_msda_layer_desc_sizeof(void) { return sizeof(VllmMsdaLayerDesc); }
 
@@ -257,12 +249,9 @@ extern "C" int vllm_msda_layer_forward(const VllmMsdaLayerDesc *d, const uint16_
     // dtype, and that one reads bf16 natively: the value is then stored in bf16 -- what the reference's own bf16 module computes
     // (...mask_dn.py:764-766 rounds it to bf16 before the upcast) at half the value GEMM's write and half the operator's read.
     uint16_t *value16 = (uint16_t *)value;
-    GemmArgs va;
-    {
-        va.X = input_flatten; va.W = d->value_proj_w; va.Y = value16; va.bias = d->value_proj_b; va.scale = nullptr; va.res = nullptr;
-        va.M = B * S; va.N = C; va.K = C; va.ldx = C; va.ldw = C; va.ldy = C; va.ldr = 0; va.P = 0; va.mt = va.nt = 0; va.xP = 0;
-        va.variant = 0; va.variant256 = 0; va.direct_store = 0; va.row_mask = padding_mask;
-    }
+    GemmArgs va = gemm_args(input_flatten, C, d->value_proj_w, C, d->value_proj_b, value16, C, B * S, C, C);
+    va.variant = 0; va.direct_store = 0;   // built for the streaming kernel (gemm_skinny_takes below), which a forced variant would bypass
+    va.row_mask = padding_mask;
     // (the bf16-value operator needs 8 channels per lane: D / 8 a power of two, 8 <= D <= 512 -- vllm_msda_forward_bf16's own
     //  precondition; a d_model-256 layer with 64 heads (D = 4) keeps the fp32 value path instead of failing there.  ADVICE r4)
     const bool d_bf16_ok = D >= 8 && D <= 512 && D % 8 == 0 && ((D / 8) & (D / 8 - 1)) == 0;
@@ -274,14 +263,10 @@ extern "C" int vllm_msda_layer_forward(const VllmMsdaLayerDesc *d, const uint16_
     // offsets and logits of the queries (:110-111) in one GEMM; softmax + location arithmetic (:112-129) in its epilogue: the tile
     // kernel's form needs L * P == 16; the streaming kernel's (gemm_skinny.hip: d_model 256, 8 heads, 4 points, >= 4096 query
     // rows) also takes 1 ... 3 levels -- the 3-level pixel decoder (msdeformattn_pixel_decoder.py:57-58)
-    GemmArgs a;
-    {
-        a.X = query; a.W = d->sampling_offsets_w; a.Y = (uint16_t *)off; a.bias = d->sampling_offsets_b; a.scale = nullptr;
-        a.res = nullptr; a.M = B * Lq; a.N = MLP * 3; a.K = C; a.ldx = C; a.ldw = C; a.ldy = MLP * 2; a.ldr = 0; a.P = 0;
-        a.mt = a.nt = 0; a.xP = 0; a.variant = 0; a.variant256 = 0; a.direct_store = 0;
-        a.W2 = d->attention_weights_w; a.bias2 = d->attention_weights_b; a.Y2 = lg; a.ldy2 = MLP; a.nsplit = MLP * 2;
-        a.ref = ref; a.shapes = shapes; a.mL = L; a.mP = P; a.ref_dim = d->ref_dim; a.four_d = d->use_4d_normalizer;
-    }
+    GemmArgs a = gemm_args(query, C, d->sampling_offsets_w, C, d->sampling_offsets_b, (uint16_t *)off, MLP * 2, B * Lq, MLP * 3, C);
+    a.variant = 0; a.direct_store = 0;   // as for the value GEMM: the EPI_MSDA launch picks streaming or tile kernel by shape, not by override
+    a.W2 = d->attention_weights_w; a.bias2 = d->attention_weights_b; a.Y2 = lg; a.ldy2 = MLP; a.nsplit = MLP * 2;
+    a.ref = ref; a.shapes = shapes; a.mL = L; a.mP = P; a.ref_dim = d->ref_dim; a.four_d = d->use_4d_normalizer;
     const bool tile_form = L * P == 16 && P % 2 == 0 && (MLP * 2) % 128 == 0;
     if (!layer_unfused() && (tile_form || gemm_skinny_takes(EPI_MSDA, a))) {
         TRY(gemm_bf16_launch(EPI_MSDA, a, st));

@@ -6,13 +6,11 @@
 // vllm_bridge_forward replaces select + pixel_shuffle + vl_bridge (visionllmv2/model/modeling_visionllmv2.py:569-579).
 #include <stdlib.h>
 #include <algorithm>
-#include "kernels.hpp"
+#include "orchestrate.hpp"
 
 using namespace vllm;
 
 namespace {
-inline long align256(long x) { return (x + 255) & ~255L; }
-
 struct VitWs {
     long xn, qkv, ao, hmid, mid, col, h0, h1, sk, ln, total;
 };
@@ -21,19 +19,18 @@ VitWs vit_ws_layout(const VllmVitDesc *d, int n)
 {
     const long g = d->image / d->patch, P = g * g, S = P + 1, M = (long)n * S;
     VitWs w;
-    long off = 0;
-    auto take = [&](long bytes) { long o = off; off += align256(bytes); return o; };
-    w.xn = take(M * d->hidden * 2);
-    w.qkv = take(M * 3L * d->hidden * 2);
-    w.ao = take(M * d->hidden * 2);
-    w.hmid = take(M * d->hidden * 2);
-    w.mid = take(M * (long)d->inter * 2);
-    w.col = take((long)n * P * d->kpad * 2);
-    w.h0 = take(M * d->hidden * 2);   // ping-pong hidden states for entries the caller does not want
-    w.h1 = take(M * d->hidden * 2);
-    w.sk = take(SK_SCRATCH_BYTES);    // stream-K tail of the GEMMs (kernels.hpp)
-    w.ln = take(2 * M * std::max((d->hidden + 255) / 256 * 2, 16) * 4);   // folded norms: {mean, M2} per (row, 256-column tile) or the wide layout's 16 floats per row; two buffers
-    w.total = off;
+    Carver cv;
+    w.xn = cv.take(M * d->hidden * 2);
+    w.qkv = cv.take(M * 3L * d->hidden * 2);
+    w.ao = cv.take(M * d->hidden * 2);
+    w.hmid = cv.take(M * d->hidden * 2);
+    w.mid = cv.take(M * (long)d->inter * 2);
+    w.col = cv.take((long)n * P * d->kpad * 2);
+    w.h0 = cv.take(M * d->hidden * 2);   // ping-pong hidden states for entries the caller does not want
+    w.h1 = cv.take(M * d->hidden * 2);
+    w.sk = cv.take(SK_SCRATCH_BYTES);    // stream-K tail of the GEMMs (kernels.hpp)
+    w.ln = cv.take(2 * M * std::max((d->hidden + 255) / 256 * 2, 16) * 4);   // folded norms: {mean, M2} per (row, 256-column tile) or the wide layout's 16 floats per row; two buffers
+    w.total = cv.off;
     return w;
 }
 
@@ -64,8 +61,6 @@ extern "C" long vllm_vit_workspace_bytes(const VllmVitDesc *d, int n_tiles)
     return vit_ws_layout(d, n_tiles).total;
 }
 
-#define TRY(x) do { int rc__ = (x); if (rc__ != VLLM_OK) return rc__; } while (0)
-
 static long g_folded_gemms = 0;   // GEMM launches with a norm folded in (tests assert the path they mean to cover ran)
 extern "C" long vllm_vit_folded_gemm_launches(void) { return __atomic_load_n(&g_folded_gemms, __ATOMIC_RELAXED); }
 
@@ -94,7 +89,7 @@ extern "C" int vllm_vit_forward(const VllmVitDesc *d, const void *pixels, int n,
     auto state = [&](int i) -> uint16_t * { return hs[i] ? hs[i] : pp[i & 1]; };
 
     void *sk = ws + w.sk;
-    VLLM_REQUIRE(hipMemsetAsync(sk, 0, SK_FLAG_BYTES, st) == hipSuccess, "vit: flag reset failed");
+    TRY(sk_scratch_reset(sk, st, "vit"));
 
     // ---- embeddings: im2col gather -> GEMM (+bias +pos, rows scattered past CLS) ; CLS rows ----
     uint16_t *emb = clip ? hmid : state(0);   // CLIP: pre_layrnorm produces hidden_states[0]
@@ -127,11 +122,9 @@ extern "C" int vllm_vit_forward(const VllmVitDesc *d, const void *pixels, int n,
     auto gemm_ln = [&](int epi, const uint16_t *X, int ldx, const uint16_t *W, int ldw, const uint16_t *bias, uint16_t *Y, int ldy, int N,
                        int K, const uint16_t *scale, const uint16_t *res, int ldr, float *ln_out, const float *ln_in,
                        const float *colsum, const float *bias_ln) {
-        GemmArgs a;
+        GemmArgs a = gemm_args(X, ldx, W, ldw, bias, Y, ldy, M, N, K);
+        a.scale = scale; a.res = res; a.ldr = ldr;
         gemm_set_scratch(a, sk, SK_SCRATCH_BYTES);
-        a.X = X; a.W = W; a.Y = Y; a.bias = bias; a.scale = scale; a.res = res;
-        a.M = (int)M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldr = ldr; a.P = 0; a.mt = a.nt = 0; a.xP = 0;
-        a.variant = gemm_variant_override(); a.variant256 = 0; a.direct_store = gemm_direct_store();
         if (a.variant == 1 || a.variant == 4) a.variant = 0;   // (a forced 128x128 kernel / the 32x32x16 variant cannot fold)
         a.ln_out = ln_out; a.ln_in = ln_in; a.ln_slots = ntC; a.ln_cols = C; a.ln_rms = clip ? 0 : 1; a.ln_eps = d->eps;
         a.ln_colsum = colsum; a.ln_bias = bias_ln; a.ln_wide = wide ? 1 : 0; a.dry_run = dry;
@@ -235,14 +228,13 @@ BridgeWs bridge_ws_layout(const VllmBridgeDesc *d, int n, int T_in)
     const long T = d->pixel_shuffle ? T_in / 4 : T_in;
     const long rows = (long)n * T;
     BridgeWs w;
-    long off = 0;
-    auto take = [&](long bytes) { long o = off; off += align256(bytes); return o; };
-    w.a = take(d->pixel_shuffle ? rows * d->in_features * 2 : 0);                       // shuffled features
-    w.b = take(d->kind == VLLM_BRIDGE_INTERNVL_MLP ? rows * d->in_features * 2 : 0);   // LayerNorm output
-    w.c = take(d->depth > 1 ? 2 * align256(rows * (long)d->out_features * 2) : 0);     // MLP intermediates
+    Carver cv;
+    w.a = cv.take(d->pixel_shuffle ? rows * d->in_features * 2 : 0);                       // shuffled features
+    w.b = cv.take(d->kind == VLLM_BRIDGE_INTERNVL_MLP ? rows * d->in_features * 2 : 0);   // LayerNorm output
+    w.c = cv.take(d->depth > 1 ? 2 * align256(rows * (long)d->out_features * 2) : 0);     // MLP intermediates
     w.sk_bytes = rows >= 1024 ? SK_SCRATCH_BYTES : 0;                                   // stream-K tail of the 8-phase GEMM (kernels.hpp)
-    w.sk = take(w.sk_bytes);
-    w.total = off;
+    w.sk = cv.take(w.sk_bytes);
+    w.total = cv.off;
     return w;
 }
 }  // namespace
@@ -309,7 +301,7 @@ extern "C" int vllm_bridge_forward(const VllmBridgeDesc *d, const uint16_t *hidd
     }
     uint16_t *tmp[2] = {(uint16_t *)(ws + w.c), (uint16_t *)(ws + w.c + align256(rows * (long)Cout * 2))};
     void *sk = w.sk_bytes ? ws + w.sk : nullptr;
-    if (sk) VLLM_REQUIRE(hipMemsetAsync(sk, 0, SK_FLAG_BYTES, st) == hipSuccess, "bridge: flag reset failed");
+    TRY(sk_scratch_reset(sk, st, "bridge"));
     int K = Cin;
     for (int i = 0; i < d->depth; ++i) {
         VLLM_REQUIRE(d->w[i], "bridge: weight %d missing", i);

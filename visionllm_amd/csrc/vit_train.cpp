@@ -20,15 +20,11 @@
 // No allocation, no synchronisation, one stream; the workspace is the caller's.
 #include <algorithm>
 #include <math.h>
-#include "kernels.hpp"
+#include "orchestrate.hpp"
 
 using namespace vllm;
 
-#define TRY(x) do { int rc__ = (x); if (rc__ != VLLM_OK) return rc__; } while (0)
-
 namespace {
-inline long al256(long x) { return (x + 255) & ~255L; }
-
 struct Dims { int C, H, D, I, B, S; long M; bool qkn; };
 
 int check_layer(const VllmVitLayerTrain *d, int B, int S, Dims *o, const char *who)
@@ -64,40 +60,27 @@ Ws ws_layout(const Dims &q)
 {
     const long M = q.M, C = q.C, I = q.I;
     Ws w;
-    long off = 0;
-    auto take = [&](long b) { long o = off; off += al256(b); return o; };
+    Carver cv;
     w.sk_bytes = M >= 1024 ? SK_SCRATCH_BYTES : 0;   // stream-K tail of the 8-phase GEMM, as the other orchestrators size it
-    w.sk = take(w.sk_bytes);
-    w.xn = take(M * C * 2);                            // norm1(x) / norm2(x1)
-    w.qkn = take(q.qkn ? M * 3 * C * 2 : 0);           // post-norm q, k (forward) + v copied beside them (backward)
-    w.fwd_total = off;
-    w.ga = take(M * C * 2);                            // gy2, then gy1
-    w.gb = take(M * C * 2);                            // dxn2 -> g1 (in place), kept until norm1's backward
-    w.gi = take(M * I * 2);                            // dh1
-    w.gq = take(M * 3 * C * 2);                        // dqkv; its first M x C elements carry dctx / dxn1 around it
-    w.wt = take(std::max(3 * C * C, C * I) * 2);       // W^T of the input-gradient GEMM at hand
+    w.sk = cv.take(w.sk_bytes);
+    w.xn = cv.take(M * C * 2);                            // norm1(x) / norm2(x1)
+    w.qkn = cv.take(q.qkn ? M * 3 * C * 2 : 0);           // post-norm q, k (forward) + v copied beside them (backward)
+    w.fwd_total = cv.off;
+    w.ga = cv.take(M * C * 2);                            // gy2, then gy1
+    w.gb = cv.take(M * C * 2);                            // dxn2 -> g1 (in place), kept until norm1's backward
+    w.gi = cv.take(M * I * 2);                            // dh1
+    w.gq = cv.take(M * 3 * C * 2);                        // dqkv; its first M x C elements carry dctx / dxn1 around it
+    w.wt = cv.take(std::max(3 * C * C, C * I) * 2);       // W^T of the input-gradient GEMM at hand
     const long wg = std::max({gemm_wgrad_workspace_bytes((int)M, (int)C, (int)I), gemm_wgrad_workspace_bytes((int)M, (int)I, (int)C),
                    gemm_wgrad_workspace_bytes((int)M, (int)C, (int)C), gemm_wgrad_workspace_bytes((int)M, (int)(3 * C), (int)C)});
     w.wg_bytes = std::max(0L, wg);
-    w.wg = take(w.wg_bytes);
+    w.wg = cv.take(w.wg_bytes);
     w.np_bytes = std::max(0L, rms_bwd_workspace_bytes(M, (int)C, 2));   // column-sum partials (G = 2 is the largest user)
-    w.np = take(w.np_bytes);
+    w.np = cv.take(w.np_bytes);
     w.ad_bytes = std::max(0L, vllm_attn_bwd_workspace_bytes(q.B, q.S, q.H, q.D));
-    w.ad = take(w.ad_bytes);
-    w.total = off;
+    w.ad = cv.take(w.ad_bytes);
+    w.total = cv.off;
     return w;
-}
-
-int gemm_t(hipStream_t st, int epi, const uint16_t *X, int ldx, const uint16_t *W, int ldw, const uint16_t *bias, uint16_t *Y, int ldy,
-           long M, int N, int K, const uint16_t *scale, const uint16_t *res, int ldr, uint16_t *pre, void *sk, long sk_bytes)
-{
-    GemmArgs a;
-    gemm_set_scratch(a, sk, sk_bytes);
-    a.X = X; a.W = W; a.Y = Y; a.bias = bias; a.scale = scale; a.res = res;
-    a.M = (int)M; a.N = N; a.K = K; a.ldx = ldx; a.ldw = ldw; a.ldy = ldy; a.ldr = ldr; a.P = 0; a.mt = a.nt = 0; a.xP = 0;
-    a.variant = gemm_variant_override(); a.variant256 = 0; a.direct_store = gemm_direct_store();
-    a.pre = pre;
-    return gemm_bf16_launch(epi, a, st);
 }
 }  // namespace
 
@@ -128,12 +111,12 @@ extern "C" int vllm_vit_layer_forward_train(const VllmVitLayerTrain *d, const ui
     const int C = q.C, I = q.I;
     const long M = q.M;
     void *sk = w.sk_bytes ? ws + w.sk : nullptr;
-    if (sk) VLLM_REQUIRE(hipMemsetAsync(sk, 0, SK_FLAG_BYTES, st) == hipSuccess, "vit_layer_forward_train: flag reset failed");
+    TRY(sk_scratch_reset(sk, st, "vit_layer_forward_train"));
     uint16_t *xn = (uint16_t *)(ws + w.xn), *qkn = (uint16_t *)(ws + w.qkn);
     const VllmVitLayerSaved &s = *saved;
 
     TRY(norm_bf16_launch(true, x, C, d->norm1_w, nullptr, xn, C, M, C, d->eps, st));
-    TRY(gemm_t(st, EPI_BIAS, xn, C, d->qkv_w, C, d->qkv_b, s.qkv, 3 * C, M, 3 * C, C, nullptr, nullptr, 0, nullptr, sk, w.sk_bytes));
+    TRY(gemm(st, EPI_BIAS, xn, C, d->qkv_w, C, d->qkv_b, s.qkv, 3 * C, (int)M, 3 * C, C, nullptr, nullptr, 0, 0, 0, sk, w.sk_bytes));
     const uint16_t *qk = s.qkv;
     if (q.qkn) {   // out of place: the backward normalises the pre-norm q / k again
         TRY(norm_bf16_launch(true, s.qkv, 3 * C, d->q_norm_w, nullptr, qkn, 3 * C, M, C, d->eps, st, d->k_norm_w, 2));
@@ -150,10 +133,20 @@ extern "C" int vllm_vit_layer_forward_train(const VllmVitLayerTrain *d, const ui
         a.lse = s.lse;
         TRY(attn_fwd_launch(a, q.D, st));
     }
-    TRY(gemm_t(st, EPI_RESIDUAL_SAVE, s.ctx, C, d->proj_w, C, d->proj_b, s.x1, C, M, C, C, d->ls1, x, C, s.y1, sk, w.sk_bytes));
+    // the three GEMMs whose epilogue also leaves its pre-activation / pre-LayerScale output for the backward
+    auto gemm_save = [&](int epi, GemmArgs a, uint16_t *pre) {
+        a.pre = pre;
+        gemm_set_scratch(a, sk, w.sk_bytes);
+        return gemm_bf16_launch(epi, a, st);
+    };
+    GemmArgs proj = gemm_args(s.ctx, C, d->proj_w, C, d->proj_b, s.x1, C, M, C, C);
+    proj.scale = d->ls1; proj.res = x; proj.ldr = C;
+    TRY(gemm_save(EPI_RESIDUAL_SAVE, proj, s.y1));
     TRY(norm_bf16_launch(true, s.x1, C, d->norm2_w, nullptr, xn, C, M, C, d->eps, st));
-    TRY(gemm_t(st, EPI_GELU_SAVE, xn, C, d->fc1_w, C, d->fc1_b, s.a1, I, M, I, C, nullptr, nullptr, 0, s.h1, sk, w.sk_bytes));
-    TRY(gemm_t(st, EPI_RESIDUAL_SAVE, s.a1, I, d->fc2_w, I, d->fc2_b, out, C, M, C, I, d->ls2, s.x1, C, s.y2, sk, w.sk_bytes));
+    TRY(gemm_save(EPI_GELU_SAVE, gemm_args(xn, C, d->fc1_w, C, d->fc1_b, s.a1, I, M, I, C), s.h1));
+    GemmArgs fc2 = gemm_args(s.a1, I, d->fc2_w, I, d->fc2_b, out, C, M, C, I);
+    fc2.scale = d->ls2; fc2.res = s.x1; fc2.ldr = C;
+    TRY(gemm_save(EPI_RESIDUAL_SAVE, fc2, s.y2));
     return VLLM_OK;
 }
 
@@ -175,12 +168,9 @@ extern "C" int vllm_vit_layer_backward(const VllmVitLayerTrain *d, const uint16_
     const int C = q.C, I = q.I;
     const long M = q.M;
     if (M == 0) {   // no rows: every parameter gradient is an empty sum
-        struct { uint16_t *p; long n; } z[] = {{g.norm1_w, C}, {g.qkv_w, 3L * C * C}, {g.qkv_b, 3L * C}, {g.q_norm_w, C}, {g.k_norm_w, C}, {g.proj_w, (long)C * C},
-                                               {g.proj_b, C}, {g.ls1, C}, {g.norm2_w, C}, {g.fc1_w, (long)I * C}, {g.fc1_b, I}, {g.fc2_w, (long)C * I},
-                                               {g.fc2_b, C}, {g.ls2, C}};
-        for (auto &e : z)
-            if (e.p) VLLM_REQUIRE(hipMemsetAsync(e.p, 0, (size_t)e.n * 2, st) == hipSuccess, "vit_layer_backward: memset failed");
-        return VLLM_OK;
+        return zero_bf16(st, "vit_layer_backward", {{g.norm1_w, C}, {g.qkv_w, 3L * C * C}, {g.qkv_b, 3L * C}, {g.q_norm_w, C}, {g.k_norm_w, C},
+                                                    {g.proj_w, (long)C * C}, {g.proj_b, C}, {g.ls1, C}, {g.norm2_w, C}, {g.fc1_w, (long)I * C},
+                                                    {g.fc1_b, I}, {g.fc2_w, (long)C * I}, {g.fc2_b, C}, {g.ls2, C}});
     }
     TRY(check_saved(saved, "vit_layer_backward"));
     VLLM_REQUIRE(x && grad_out && aligned16(x) && aligned16(grad_out), "vit_layer_backward: x and grad_out must be 16-byte aligned device pointers");
@@ -189,7 +179,7 @@ extern "C" int vllm_vit_layer_backward(const VllmVitLayerTrain *d, const uint16_
                  ws_bytes, w.total);
     char *ws = (char *)workspace;
     void *sk = w.sk_bytes ? ws + w.sk : nullptr;
-    if (sk) VLLM_REQUIRE(hipMemsetAsync(sk, 0, SK_FLAG_BYTES, st) == hipSuccess, "vit_layer_backward: flag reset failed");
+    TRY(sk_scratch_reset(sk, st, "vit_layer_backward"));
     uint16_t *xn = (uint16_t *)(ws + w.xn), *qkn = (uint16_t *)(ws + w.qkn), *ga = (uint16_t *)(ws + w.ga), *gb = (uint16_t *)(ws + w.gb);
     uint16_t *gi = (uint16_t *)(ws + w.gi), *gq = (uint16_t *)(ws + w.gq), *wt = (uint16_t *)(ws + w.wt);
     void *wg = ws + w.wg, *np = ws + w.np;
@@ -207,16 +197,12 @@ extern "C" int vllm_vit_layer_backward(const VllmVitLayerTrain *d, const uint16_
     // ---- MLP block ----
     if (y2 || g.ls2) TRY(ls_bwd_launch(grad_out, C, s.y2, C, d->ls2, M, C, y2 ? ga : nullptr, C, g.ls2, np, w.np_bytes, st));
     if (g.fc2_w) TRY(gemm_wgrad_launch(ga, C, s.a1, I, (int)M, C, I, g.fc2_w, I, g.fc2_b, wg, w.wg_bytes, st));
-    if (h1) {
-        TRY(transpose_bf16_launch(d->fc2_w, I, wt, C, C, I, st));   // [C, I] -> [I, C]
-        TRY(gemm_t(st, EPI_GELU_BWD, ga, C, wt, C, nullptr, gi, I, M, I, C, nullptr, s.h1, I, nullptr, sk, w.sk_bytes));
-    }
+    if (h1) TRY(linear_dgrad(st, EPI_GELU_BWD, ga, d->fc2_w, C, I, M, wt, gi, s.h1, sk, w.sk_bytes));
     if (g.fc1_w || n2) TRY(norm_bf16_launch(true, s.x1, C, d->norm2_w, nullptr, xn, C, M, C, d->eps, st));
     if (g.fc1_w) TRY(gemm_wgrad_launch(gi, I, xn, C, (int)M, I, C, g.fc1_w, C, g.fc1_b, wg, w.wg_bytes, st));
     const uint16_t *g1 = grad_out;
     if (n2) {
-        TRY(transpose_bf16_launch(d->fc1_w, C, wt, I, I, C, st));   // [I, C] -> [C, I]
-        TRY(gemm_t(st, EPI_BIAS, gi, I, wt, I, nullptr, gb, C, M, C, I, nullptr, nullptr, 0, nullptr, sk, w.sk_bytes));
+        TRY(linear_dgrad(st, EPI_BIAS, gi, d->fc1_w, I, C, M, wt, gb, nullptr, sk, w.sk_bytes));
         TRY(rms_bwd_launch(s.x1, C, gb, C, d->norm2_w, nullptr, 1, d->eps, M, C, x1 ? gb : nullptr, C, x1 ? grad_out : nullptr, C, g.norm2_w,
                            nullptr, np, w.np_bytes, st));
         g1 = gb;
@@ -227,8 +213,7 @@ extern "C" int vllm_vit_layer_backward(const VllmVitLayerTrain *d, const uint16_
     if (g.proj_w) TRY(gemm_wgrad_launch(ga, C, s.ctx, C, (int)M, C, C, g.proj_w, C, g.proj_b, wg, w.wg_bytes, st));
     if (!dq) return VLLM_OK;
     uint16_t *dctx = xn;   // (norm2(x1) has been consumed)
-    TRY(transpose_bf16_launch(d->proj_w, C, wt, C, C, C, st));
-    TRY(gemm_t(st, EPI_BIAS, ga, C, wt, C, nullptr, dctx, C, M, C, C, nullptr, nullptr, 0, nullptr, sk, w.sk_bytes));
+    TRY(linear_dgrad(st, EPI_BIAS, ga, d->proj_w, C, C, M, wt, dctx, nullptr, sk, w.sk_bytes));
     const uint16_t *qkv_n = s.qkv;
     if (q.qkn) {
         TRY(norm_bf16_launch(true, s.qkv, 3 * C, d->q_norm_w, nullptr, qkn, 3 * C, M, C, d->eps, st, d->k_norm_w, 2));
@@ -243,8 +228,7 @@ extern "C" int vllm_vit_layer_backward(const VllmVitLayerTrain *d, const uint16_
     if (g.qkv_w || n1) TRY(norm_bf16_launch(true, x, C, d->norm1_w, nullptr, xn, C, M, C, d->eps, st));
     if (g.qkv_w) TRY(gemm_wgrad_launch(gq, 3 * C, xn, C, (int)M, 3 * C, C, g.qkv_w, C, g.qkv_b, wg, w.wg_bytes, st));
     if (!n1) return VLLM_OK;
-    TRY(transpose_bf16_launch(d->qkv_w, C, wt, 3 * C, 3 * C, C, st));   // [3C, C] -> [C, 3C]
-    TRY(gemm_t(st, EPI_BIAS, gq, 3 * C, wt, 3 * C, nullptr, ga, C, M, C, 3 * C, nullptr, nullptr, 0, nullptr, sk, w.sk_bytes));
+    TRY(linear_dgrad(st, EPI_BIAS, gq, d->qkv_w, 3 * C, C, M, wt, ga, nullptr, sk, w.sk_bytes));
     TRY(rms_bwd_launch(x, C, ga, C, d->norm1_w, nullptr, 1, d->eps, M, C, grad_x, C, grad_x ? g1 : nullptr, C, g.norm1_w, nullptr, np, w.np_bytes, st));
     return VLLM_OK;
 }

@@ -48,7 +48,7 @@ class _FlashAttnQKVPacked(torch.autograd.Function):
             need = L.vllm_attn_bwd_workspace_bytes(B, S, H, D)
             if need < 0:
                 raise RuntimeError(f"native FlashAttention backward: head_dim {D} not supported (64 or 128)")
-            ws = _lib.workspace(qkv.device, max(need, 16))
+            ws, need = _lib.sized_workspace(qkv.device, need, "vllm_attn_bwd_workspace_bytes")
             _lib.check(_entry("vllm_attn_bwd_qkvpacked", qkv.dtype)(
                 _lib.ptr(qkv), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(grad_out), B, S, H, D, ctx.scale, _lib.ptr(grad_qkv),
                 _lib.ptr(ws), need, _lib.current_stream(qkv.device)), "vllm_attn_bwd_qkvpacked")

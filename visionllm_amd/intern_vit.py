@@ -115,9 +115,7 @@ class _RMSNormTrain(torch.autograd.Function):
         gw = torch.empty_like(w) if need_w else None
         L = _lib.lib()
         with torch.cuda.device(x.device):
-            wsb = L.vllm_rmsnorm_backward_workspace_bytes(rows, C, 1)
-            _lib.check(0 if wsb >= 0 else -1, "vllm_rmsnorm_backward_workspace_bytes")
-            ws = _lib.workspace(x.device, max(wsb, 1))
+            ws, wsb = _lib.sized_workspace(x.device, L.vllm_rmsnorm_backward_workspace_bytes(rows, C, 1), "vllm_rmsnorm_backward_workspace_bytes")
             _lib.check(L.vllm_rmsnorm_backward_bf16(_lib.ptr(x), C, _lib.ptr(g), C, _lib.ptr(w), None, 1, ctx.eps, rows, C, _lib.ptr(gx), C,
                                                     None, 0, _lib.ptr(gw), None, _lib.ptr(ws), wsb, _lib.current_stream(x.device)),
                        "vllm_rmsnorm_backward_bf16")
@@ -204,9 +202,7 @@ def _layer_forward(meta, x, params, want_saved):
              torch.empty((M, C), **bf)]
     sv = _lib.VllmVitLayerSaved(**{n: t.data_ptr() for n, t in zip(_SAVED, saved)})
     with torch.cuda.device(dev):
-        wsb = L.vllm_vit_layer_backward_workspace_bytes(ctypes.byref(d), B, S)
-        _lib.check(0 if wsb >= 0 else -1, "vllm_vit_layer_backward_workspace_bytes")
-        ws = _lib.workspace(dev, max(wsb, 1))
+        ws, wsb = _lib.sized_workspace(dev, L.vllm_vit_layer_backward_workspace_bytes(ctypes.byref(d), B, S), "vllm_vit_layer_backward_workspace_bytes")
         _lib.check(L.vllm_vit_layer_forward_train(ctypes.byref(d), _lib.ptr(x), B, S, _lib.ptr(out), ctypes.byref(sv), _lib.ptr(ws), wsb,
                                                   _lib.current_stream(dev)), "vllm_vit_layer_forward_train")
     return out, (saved if want_saved else None)
@@ -246,9 +242,8 @@ class _VitLayerTrain(torch.autograd.Function):
         sv = _lib.VllmVitLayerSaved(**{n: t_.data_ptr() for n, t_ in zip(_SAVED, saved)})
         L = _lib.lib()
         with torch.cuda.device(dev):
-            wsb = L.vllm_vit_layer_backward_workspace_bytes(ctypes.byref(d), B, S)
-            _lib.check(0 if wsb >= 0 else -1, "vllm_vit_layer_backward_workspace_bytes")
-            ws = _lib.workspace(dev, max(wsb, 1))
+            ws, wsb = _lib.sized_workspace(dev, L.vllm_vit_layer_backward_workspace_bytes(ctypes.byref(d), B, S),
+                                           "vllm_vit_layer_backward_workspace_bytes")
             _lib.check(L.vllm_vit_layer_backward(ctypes.byref(d), _lib.ptr(x), B, S, _lib.ptr(g), ctypes.byref(sv), _lib.ptr(gx),
                                                  ctypes.byref(gs), _lib.ptr(ws), wsb, _lib.current_stream(dev)), "vllm_vit_layer_backward")
         out = [t_ if n else None for t_, n in zip(grads, ctx.needs_input_grad[2:])]   # (a weight gradient computed only for its bias is dropped)

@@ -386,10 +386,7 @@ def msda_layer_prepare(query, reference_points, input_flatten, spatial_shapes, l
     shapes = spatial_shapes.to(device=q.device, dtype=torch.int64).contiguous()
     lsi = level_start_index.to(device=q.device, dtype=torch.int64).contiguous()
     mask = None if padding_mask is None else padding_mask.to(torch.uint8).contiguous()
-    nbytes = L.vllm_msda_layer_workspace_bytes(ctypes.byref(desc), B, Lq, S)
-    if nbytes < 0:
-        _lib.check(-1, "vllm_msda_layer_workspace_bytes")
-    ws = _lib.workspace(q.device, nbytes)
+    ws, wsb = _lib.sized_workspace(q.device, L.vllm_msda_layer_workspace_bytes(ctypes.byref(desc), B, Lq, S), "vllm_msda_layer_workspace_bytes")
     out = torch.empty_like(q)
 
     def launch():
@@ -399,7 +396,7 @@ def msda_layer_prepare(query, reference_points, input_flatten, spatial_shapes, l
         with torch.cuda.device(q.device):
             _lib.check(L.vllm_msda_layer_forward(ctypes.byref(desc), _lib.ptr(q), _lib.ptr(ref), _lib.ptr(x), _lib.ptr(mask),
                                                  _lib.ptr(shapes), _lib.ptr(lsi), B, Lq, S, _lib.ptr(out), _lib.ptr(ws),
-                                                 ws.numel(), _lib.current_stream(q.device)), "vllm_msda_layer_forward")
+                                                 wsb, _lib.current_stream(q.device)), "vllm_msda_layer_forward")
         launch.keep = keep   # (parameters referenced by the descriptor stay alive until the call has been enqueued)
         return out
     return launch

@@ -79,9 +79,8 @@ class _PointSampleMaskedMean(torch.autograd.Function):
         grad_in = torch.empty(ctx.map_shape, dtype=ctx.map_dtype, device=g.device)
         name = "vllm_point_sample_mean_backward_bf16" if ctx.map_dtype == torch.bfloat16 else "vllm_point_sample_mean_backward_f32"
         with torch.cuda.device(g.device):
-            nbytes = _lib.lib().vllm_point_sample_backward_workspace_bytes(N, C, H, W, P)
-            _lib.check(min(nbytes, 0), "vllm_point_sample_backward_workspace_bytes")
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=g.device) if nbytes else None   # (allocations are 512-byte aligned)
+            ws, nbytes = _lib.sized_workspace(g.device, _lib.lib().vllm_point_sample_backward_workspace_bytes(N, C, H, W, P),
+                                              "vllm_point_sample_backward_workspace_bytes")
             _lib.check(getattr(_lib.lib(), name)(_lib.ptr(pts), _lib.ptr(v), _lib.ptr(g), N, C, H, W, P, _lib.ptr(grad_in),
                                                  _lib.ptr(ws), nbytes, _lib.current_stream(g.device)), name)
         return grad_in, None, None

@@ -108,9 +108,7 @@ def _embed_desc(pix, w, b, cls, pos, keep):
 
 
 def _embed_workspace(L, d, n, dev):
-    wsb = L.vllm_vit_embed_workspace_bytes(ctypes.byref(d), n)
-    _lib.check(0 if wsb >= 0 else -1, "vllm_vit_embed_workspace_bytes")
-    return _lib.workspace(dev, max(wsb, 1)), wsb
+    return _lib.sized_workspace(dev, L.vllm_vit_embed_workspace_bytes(ctypes.byref(d), n), "vllm_vit_embed_workspace_bytes")
 
 
 def _embed_forward(pix, w, b, cls, pos):
@@ -216,10 +214,7 @@ def run_encoder(desc, pixel_values, num_layers, hidden_size, keep=None):
             if nc == 0:
                 continue
             ptrs = (ctypes.c_void_p * (L + 1))(*[s.data_ptr() + lo * row_bytes if s is not None else None for s in states])
-            ws_bytes = lib.vllm_vit_workspace_bytes(ctypes.byref(desc), nc)
-            if ws_bytes < 0:
-                raise RuntimeError("vllm_vit_workspace_bytes: " + lib.vllm_last_error().decode())
-            ws = _lib.workspace(dev, ws_bytes, slot=c)
+            ws, ws_bytes = _lib.sized_workspace(dev, lib.vllm_vit_workspace_bytes(ctypes.byref(desc), nc), "vllm_vit_workspace_bytes", slot=c)
             stream = main if c == 0 else _side_stream(dev, c)
             if c > 0:
                 stream.wait_stream(main)   # inputs (and the workspace's previous users) are ordered on the caller's stream
