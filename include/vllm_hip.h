@@ -349,8 +349,10 @@ int vllm_gemm_bf16(const uint16_t *X, const uint16_t *W, const uint16_t *bias, u
  * fill a whole number of rounds on the device's CUs, the K iterations of the last round's tiles are spread evenly over all CUs
  * (fp32 partial tiles meet in `scratch`, summed in a fixed order: results are run-to-run identical).  `scratch` is
  * vllm_gemm_scratch_bytes() bytes, 16-byte aligned; the call resets its first 4096 bytes (flags) with a memset node in front of
- * the kernel; calls sharing a scratch must be ordered on one stream.  NULL scratch = vllm_gemm_bf16.  vllm_vit_forward /
- * vllm_bridge_forward reserve theirs inside their workspace. */
+ * the kernel; calls sharing a scratch must be ordered on one stream.  NULL scratch = vllm_gemm_bf16.  A shorter scratch is legal
+ * down to the flags and one 262144-byte slot (less, or a misaligned pointer: VLLM_EINVAL): the tail is then planned only if the
+ * slots of every compute unit fit, and never reaches past `scratch_bytes`.  vllm_vit_forward / vllm_bridge_forward reserve theirs
+ * inside their workspace. */
 long vllm_gemm_scratch_bytes(void);
 long vllm_gemm_sk_launches(void);   /* GEMM launches of this process that took the stream-K tail (tests / tuning) */
 long vllm_gemm_half_tail_launches(void);   /* ... of the persistent schedule whose last round ran as half-height tiles (round 4) */
@@ -639,7 +641,10 @@ int vllm_bridge_forward(const VllmBridgeDesc *desc, const uint16_t *hidden, int 
  * NULL, grad_ln_w / grad_ln_b (internvl_mlp; either may be NULL), grad_x [rows, in_features] when not NULL.  All gradients bf16 (fp32
  * accumulation inside, fp32 LayerNorm input gradient), overwritten (the caller accumulates).  Run-to-run identical.
  * workspace: vllm_bridge_backward_workspace_bytes(desc, rows, need_grad_x) bytes for the backward; the same size (with need_grad_x 0)
- * also serves the training forward.  Nothing is allocated, nothing synchronised; one stream. */
+ * also serves the training forward (which uses only the stream-K scratch at its head, present from 1024 rows on).  Where the query
+ * answers 0 (a Linear projector below the split and stream-K sizes with grad_x NULL) a NULL workspace / 0 bytes is accepted; otherwise a
+ * NULL, short or misaligned workspace is refused (VLLM_EINVAL) before anything is enqueued.  Nothing is allocated, nothing synchronised;
+ * one stream. */
 /* Alignment: x, out, grad_out, grad_x, every saved tensor and gradient, the descriptor's parameters and the workspace 16 bytes. */
 long vllm_bridge_backward_workspace_bytes(const VllmBridgeDesc *desc, long rows, int need_grad_x);
 int vllm_bridge_forward_train(const VllmBridgeDesc *desc, const uint16_t *x, long rows, uint16_t *out, uint16_t *const *saved_pre,

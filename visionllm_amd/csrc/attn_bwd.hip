@@ -367,7 +367,7 @@ int attn_bwd_launch(const uint16_t *qkv, const uint16_t *out, const float *lse, 
     if (B == 0) return VLLM_OK;
     const long need = attn_bwd_workspace(B, S, H, D);
     VLLM_REQUIRE((long)H * D < (1l << 22), "attn_bwd: H * D too large for 32-bit tile offsets");
-    VLLM_REQUIRE(qkv && out && lse && grad_out && grad_qkv && workspace, "attn_bwd: null pointer");
+    VLLM_REQUIRE(qkv && out && lse && grad_out && grad_qkv && workspace, "attn_bwd: null pointer (an operand or the workspace)");
     VLLM_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(grad_out) && aligned16(grad_qkv) && aligned16(workspace) &&
                      (reinterpret_cast<uintptr_t>(lse) & 3u) == 0,
                  "attn_bwd: qkv, out, grad_out, grad_qkv and workspace must be 16-byte aligned, lse 4-byte aligned");

@@ -125,8 +125,9 @@ extern "C" int vllm_bridge_backward(const VllmBridgeDesc *d, const uint16_t *x, 
                      "bridge_backward: saved_pre[%d] / saved_act[%d] missing or not 16-byte aligned", i, i);
     const bool need_gx = grad_x != nullptr;
     const TrainWs w = train_ws_layout(d, rows, need_gx);
-    VLLM_REQUIRE(workspace && aligned16(workspace) && ws_bytes >= w.total, "bridge_backward: workspace too small (%ld < %ld bytes) or misaligned",
-                 ws_bytes, w.total);
+    // (a Linear bridge below the split and stream-K sizes with no grad_x needs none: NULL / 0 is accepted where the query answers 0)
+    VLLM_REQUIRE(w.total == 0 || (workspace && aligned16(workspace) && ws_bytes >= w.total),
+                 "bridge_backward: workspace too small (%ld < %ld bytes) or misaligned", ws_bytes, w.total);
     char *ws = (char *)workspace;
     void *sk = w.sk_bytes ? ws + w.sk : nullptr;
     TRY(sk_scratch_reset(sk, st, "bridge_backward"));

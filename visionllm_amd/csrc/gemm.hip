@@ -385,7 +385,7 @@ extern "C" int vllm_gemm_bf16_sk(const uint16_t *X, const uint16_t *W, const uin
                                  const uint16_t *res, int ldr, int P, void *scratch, long scratch_bytes, vllm_stream_t stream)
 {
     VLLM_REQUIRE(X && W && Y, "vllm_gemm_bf16_sk: null pointer");
-    VLLM_REQUIRE(!scratch || (scratch_bytes >= SK_FLAG_BYTES + SK_SLOT_BYTES && aligned16(scratch)), "vllm_gemm_bf16_sk: scratch too small or misaligned");
+    VLLM_REQUIRE(!scratch || (scratch_bytes >= SK_FLAG_BYTES + SK_SLOT_BYTES && aligned16(scratch)), "vllm_gemm_bf16_sk: scratch workspace too small (%ld < %ld bytes) or misaligned", scratch_bytes, SK_FLAG_BYTES + SK_SLOT_BYTES);
     // the flags are reset in front of every call of THIS entry (a memset node of 4 KB: a call that died half way, or a caller that
     // never zeroed its scratch, must not hand a stale "slot ready" to the next one); the orchestrators reset theirs once per forward
     if (scratch) VLLM_REQUIRE(hipMemsetAsync(scratch, 0, SK_FLAG_BYTES, (hipStream_t)stream) == hipSuccess, "vllm_gemm_bf16_sk: flag reset failed");

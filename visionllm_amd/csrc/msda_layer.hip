@@ -234,7 +234,8 @@ extern "C" int vllm_msda_layer_forward(const VllmMsdaLayerDesc *d, const uint16_
     VLLM_REQUIRE(S > 0, "msda_layer: empty value");
     VLLM_REQUIRE(query && ref && input_flatten && shapes && lsi && out, "msda_layer: null pointer");
     const LayerWs w = layer_ws(d, B, Lq, S);
-    VLLM_REQUIRE(workspace && ws_bytes >= w.total, "msda_layer: workspace too small (%ld < %ld)", ws_bytes, w.total);
+    VLLM_REQUIRE(workspace && aligned16(workspace) && ws_bytes >= w.total, "msda_layer: workspace too small (%ld < %ld bytes) or misaligned", ws_bytes,
+                 w.total);
     VLLM_REQUIRE((long)B * S < (1L << 31) && (long)B * Lq < (1L << 31), "msda_layer: too many rows for one launch");
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;

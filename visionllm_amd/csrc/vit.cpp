@@ -70,9 +70,9 @@ extern "C" int vllm_vit_forward(const VllmVitDesc *d, const void *pixels, int n,
     TRY(check_desc(d));
     VLLM_REQUIRE(n >= 0, "vit: negative tile count");
     if (n == 0) return VLLM_OK;
-    VLLM_REQUIRE(pixels && hs && workspace, "vit: null pointer");
+    VLLM_REQUIRE(pixels && hs, "vit: null pointer");
     const VitWs w = vit_ws_layout(d, n);
-    VLLM_REQUIRE(ws_bytes >= w.total, "vit: workspace too small (%ld < %ld)", ws_bytes, w.total);
+    VLLM_REQUIRE(workspace && aligned16(workspace) && ws_bytes >= w.total, "vit: workspace too small (%ld < %ld bytes) or misaligned", ws_bytes, w.total);
     VLLM_REQUIRE(hs[d->num_layers], "vit: the last hidden state must be provided");
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
@@ -252,7 +252,8 @@ extern "C" int vllm_bridge_forward(const VllmBridgeDesc *d, const uint16_t *hidd
     if (n == 0) return VLLM_OK;
     VLLM_REQUIRE(hidden && out, "bridge: null pointer");
     const BridgeWs w = bridge_ws_layout(d, n, T_in);
-    VLLM_REQUIRE(w.total == 0 || (workspace && ws_bytes >= w.total), "bridge: workspace too small");
+    VLLM_REQUIRE(w.total == 0 || (workspace && aligned16(workspace) && ws_bytes >= w.total), "bridge: workspace too small (%ld < %ld bytes) or misaligned",
+                 ws_bytes, w.total);
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
     const int S = T_in + (d->skip_cls ? 1 : 0);
