@@ -330,7 +330,7 @@ int vllm_point_sample_backward_f32(const float *coords, const float *grad_out /*
 #define VLLM_GEMM_FORCE_128 0x100
 #define VLLM_GEMM_FORCE_256 0x200   /* 8-phase schedule, 256-row block tile */
 #define VLLM_GEMM_FORCE_192 0x300   /* 8-phase schedule, 192-row block tile */
-#define VLLM_GEMM_FORCE_4W 0x400    /* 4-wave schedule: 256x256x32 block tile, 128x128 per wave */
+#define VLLM_GEMM_FORCE_4W 0x400    /* 4-wave schedule: 256x256x32 block tile, 128x128 per wave (not built: VLLM_EINVAL) */
 #define VLLM_GEMM_FORCE_MF32 0x800  /* 8-phase schedule, 256-row block tile, v_mfma_f32_32x32x16_bf16 */
 #define VLLM_GEMM_FORCE_TILEWISE 0x1000 /* 8-phase schedule with one workgroup per tile, where the persistent walk over the tiles
                                         * (qkv / fc1 shapes: bias / GELU / quick-GELU epilogue, N % 256 == 0) would be taken */
@@ -340,7 +340,8 @@ int vllm_point_sample_backward_f32(const float *coords, const float *grad_out /*
  * K % 64 == 0, N % 4 == 0, 16-byte aligned operands.  bias/scale may be NULL.  For VLLM_EPI_EMBED `res` is the
  * position table [P+1, N] (row stride ldr) and P the patches per image; output row of input row m is
  * (m / P) * (P + 1) + 1 + m % P. */
-/* Alignment (every vllm_gemm_bf16*): X and W 16 bytes, Y 8 bytes (16 with VLLM_EPI_F32), scratch 16 bytes. */
+/* Alignment (every vllm_gemm_bf16*): X and W 16 bytes, Y 8 bytes (16 with VLLM_EPI_F32), scratch 16 bytes; bias, scale, the bf16 `res`
+ * (residual, position table, saved pre-activation) and `pre` 8 bytes.  Row strides: ldx, ldw multiples of 8, ldy and ldr of 4. */
 int vllm_gemm_bf16(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y,
                    int M, int N, int K, int ldx, int ldw, int ldy, int epilogue,
                    const uint16_t *scale, const uint16_t *res, int ldr, int P, vllm_stream_t stream);

@@ -249,17 +249,25 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(const GemmAr
 
 int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st);   // gemm256.hip
 
+static inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }   // (NULL passes: optional operands)
+
 int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
 {
     VLLM_REQUIRE(a.M >= 0 && a.N > 0 && a.K > 0, "gemm: bad dims M=%d N=%d K=%d", a.M, a.N, a.K);
     if (a.M == 0) return VLLM_OK;
+    VLLM_REQUIRE((epi >= EPI_BIAS && epi <= EPI_GELU_BWD) || epi == EPI_MSDA || epi == EPI_GELU_SAVE || epi == EPI_RESIDUAL_SAVE,
+                 "gemm: unknown epilogue %d", epi);
     VLLM_REQUIRE(a.K % BK == 0, "gemm: K=%d must be a multiple of %d", a.K, BK);
     VLLM_REQUIRE(a.N % 4 == 0, "gemm: N=%d must be a multiple of 4", a.N);
     VLLM_REQUIRE(a.ldx % 8 == 0 && a.ldw % 8 == 0 && a.ldy % 4 == 0 && aligned16(a.X) && aligned16(a.W) &&
                      (reinterpret_cast<uintptr_t>(a.Y) & (epi == EPI_F32 || epi == EPI_MSDA ? 15u : 7u)) == 0,
                  "gemm: X and W must be 16-byte aligned, Y 8-byte aligned (16-byte for fp32 output), row strides multiples of 8 elements");
-    VLLM_REQUIRE(!epi_is_residual(epi) || (a.res && a.ldr % 4 == 0), "gemm: residual epilogue needs res");
-    VLLM_REQUIRE(epi != EPI_EMBED || (a.res && a.P > 0), "gemm: embed epilogue needs the position table and P");
+    // the epilogues read bias / scale / res as 8-byte pairs (gemm_epilogue.hpp)
+    VLLM_REQUIRE(aligned8(a.bias) && aligned8(a.scale), "gemm: bias and scale must be 8-byte aligned");
+    VLLM_REQUIRE(!epi_is_residual(epi) || (a.res && a.ldr % 4 == 0 && aligned8(a.res)),
+                 "gemm: residual epilogue needs res (8-byte aligned, ldr a multiple of 4)");
+    VLLM_REQUIRE(epi != EPI_EMBED || (a.res && a.P > 0 && a.ldr % 4 == 0 && aligned8(a.res)),
+                 "gemm: embed epilogue needs the position table (8-byte aligned, ldr a multiple of 4) and P");
     VLLM_REQUIRE(epi != EPI_GELU_BWD || (a.res && !a.bias && a.ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(a.res) & 7u) == 0),
                  "gemm: the GELU-backward epilogue needs the saved pre-activation `res` (8-byte aligned, ldr a multiple of 4) and no bias");
     VLLM_REQUIRE((epi != EPI_GELU_SAVE && epi != EPI_RESIDUAL_SAVE) || (a.pre && (reinterpret_cast<uintptr_t>(a.pre) & 7u) == 0),
@@ -330,6 +338,7 @@ static void gemm_force_bits(GemmArgs &a, int epilogue, int accept)
     if (e & VLLM_GEMM_FORCE_TILEWISE) a.no_persist = 1;
     if (tile == VLLM_GEMM_FORCE_192) { a.variant = 2; a.variant256 = 3; }
     else if (tile == VLLM_GEMM_FORCE_256) a.variant256 = 4;
+    if (epilogue & VLLM_GEMM_FORCE_4W) a.variant = 3;   // every entry: the launcher refuses it (not built), no entry ignores it
 }
 
 extern "C" int vllm_gemm_bf16(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, int M, int N,

@@ -776,7 +776,6 @@ static long sk_max_tiles(int cus)
 
 int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
 {
-    const int cus = device_cus();
     a.nt = ceil_div(a.N, G2_BN);
     if (a.ln_in || a.ln_out) {   // folded norm: the row-wise LDS epilogue is where it lives
         VLLM_REQUIRE(epi != EPI_F32 && (a.N & 7) == 0 && (a.ldy & 7) == 0 && aligned16(a.Y) && a.variant256 != 5,
@@ -801,6 +800,7 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
             a.ln_inv_cols = 1.f / cnt;
         }
     }
+    const int cus = device_cus();   // (behind the refusals above: a refused call makes no HIP call)
     a.res_init = (epi_is_residual(epi) && a.variant256 != 5 && !res_init_disabled() && a.N % 8 == 0 && a.N >= 8 &&
                   a.ldr % 8 == 0 && aligned16(a.res)) ? 1 : 0;
     { static const int pf = [] { const char *e = getenv("VLLM_GEMM_PROF"); return e ? atoi(e) : 0; }(); a.prof = pf; }
