@@ -428,6 +428,20 @@ int vllm_rmsnorm_backward_bf16(const uint16_t *x, int ldx, const uint16_t *grad_
                                const uint16_t *weight2, int G, float eps, long rows, int C, uint16_t *grad_x, int ldgx,
                                const uint16_t *grad_res, int ldgr, uint16_t *grad_w, uint16_t *grad_w2, void *workspace,
                                long workspace_bytes, vllm_stream_t stream);
+/* nn.LayerNorm backward inside a layer's chain (the CLIP encoder layer's layer_norm1 / layer_norm2, pre_layrnorm, post_layernorm): the
+ * same function as vllm_layernorm_backward_bf16 with a bf16 grad_y and a residual gradient, on vllm_rmsnorm_backward_bf16's walk.  x,
+ * grad_y, grad_x [rows, C] bf16 with row strides ldx / ldg / ldgx (elements); weight (gamma) [C].  Row mean and variance are recomputed
+ * in fp32:  xhat = (x - mean) r, g = grad_y gamma, grad_x = r (g - mean(g) - xhat mean(g xhat)) [+ grad_res], rounded once;  grad_w =
+ * sum_rows grad_y xhat with the UNROUNDED fp32 xhat;  grad_b = sum_rows grad_y.  grad_res (bf16 [rows, C], row stride ldgr; NULL = none;
+ * needs grad_x) is the gradient of a residual branch that left the normalised tensor, added before the rounding.  grad_x may alias grad_y.
+ * grad_x, grad_w, grad_b may each be NULL (not needed).  Column sums: per-block fp32 partials in `workspace`
+ * (vllm_layernorm_backward_res_workspace_bytes(rows, C); host-only arithmetic, < 0 for unsupported sizes) and a fixed-order reduce -- no
+ * atomics, the same bits on every run.  C % 64 == 0, C <= 8192.  rows == 0 zero-fills the requested sums.  A refused call writes nothing. */
+/* Alignment: x, grad_y, grad_x, grad_res, weight and workspace 16 bytes (row strides multiples of 8); grad_w, grad_b 2 bytes. */
+long vllm_layernorm_backward_res_workspace_bytes(long rows, int C);
+int vllm_layernorm_backward_res_bf16(const uint16_t *x, int ldx, const uint16_t *grad_y, int ldg, const uint16_t *weight, float eps,
+                                     long rows, int C, uint16_t *grad_x, int ldgx, const uint16_t *grad_res, int ldgr, uint16_t *grad_w,
+                                     uint16_t *grad_b, void *workspace, long workspace_bytes, vllm_stream_t stream);
 /* Backward of LayerScale + residual, out = res + y * ls (modeling_intern_vit.py:206-208): grad_y = bf16(grad_out * ls) [rows, C] (row
  * stride ldgy), grad_ls = sum_rows grad_out * y [C] (fp32 partials in `workspace` and a fixed-order reduce, as above); the residual's
  * gradient is grad_out itself.  Either output may be NULL (y is only read for grad_ls, ls only for grad_y).  C % 8 == 0, C <= 8192. */
@@ -710,6 +724,65 @@ int vllm_vit_layer_backward(const VllmVitLayerTrain *desc, const uint16_t *x, in
 int vllm_gemm_bf16_residual_save(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, uint16_t *pre, int M, int N,
                                  int K, int ldx, int ldw, int ldy, int epilogue, const uint16_t *scale, const uint16_t *res, int ldr,
                                  vllm_stream_t stream);
+
+/* Training one CLIP encoder layer (transformers 4.34 CLIPEncoderLayer.forward: layer_norm1 -> CLIPAttention (separate q / k / v
+ * projections, here one fused [3C, C] weight; q * scale, softmax, out_proj) -> residual -> layer_norm2 -> CLIPMLP (fc1, quick-GELU or erf
+ * GELU, fc2) -> residual; the reference builds CLIPVisionModel in the vis_encoder slot, visionllmv2/train/train.py:382-384, and offers
+ * freeze_vis_encoder=False, :163, 534).  No dropout, no attention mask.  x, out, grad_out, grad_x [B, S, hidden] bf16, contiguous.
+ * hidden % 64 == 0 (<= 8192), inter % 64 == 0, head_dim 64 or 128.  These structs are additions: VllmVitLayer / VllmVitDesc /
+ * VllmVitLayerTrain and vllm_abi_version are unchanged. */
+typedef struct VllmClipLayerTrain {
+    int hidden, heads, inter;
+    int act;                                /* VLLM_EPI_QUICK_GELU or VLLM_EPI_GELU */
+    float eps;
+    const uint16_t *norm1_w, *norm1_b;      /* layer_norm1 */
+    const uint16_t *qkv_w, *qkv_b;          /* [3C, C], [3C]: q, k, v projections concatenated */
+    const uint16_t *proj_w, *proj_b;        /* out_proj */
+    const uint16_t *norm2_w, *norm2_b;      /* layer_norm2 */
+    const uint16_t *fc1_w, *fc1_b, *fc2_w, *fc2_b;
+} VllmClipLayerTrain;
+/* What the training forward keeps for the backward (caller buffers, all written by the forward; M = B * S rows):
+ *   qkv [M, 3C];  ctx [M, C] attention output;  lse [B, heads, S] fp32;  x1 [M, C] the hidden state between the two blocks;  h1 / a1
+ *   [M, inter] fc1 output before / after the activation  -- (5 C + 2 inter) M bf16 elements + lse (no LayerScale: no pre-scale outputs).
+ * Recomputed by the backward instead of saved, one norm launch each: layer_norm1(x), layer_norm2(x1). */
+typedef struct VllmClipLayerSaved {
+    uint16_t *qkv, *ctx;
+    float *lse;
+    uint16_t *x1, *h1, *a1;
+} VllmClipLayerSaved;
+/* Parameter gradients (bf16, the parameters' shapes, overwritten -- the caller accumulates), in the layer's parameter order.  NULL = not
+ * needed: that product is skipped, and everything only it needed.  A bias gradient of a Linear comes out of its weight gradient's launch:
+ * it needs the weight's pointer too.  The k block of qkv_b, elements [C, 2C), is written as zero: the k projection's bias shifts every score of
+ * a query row alike, which softmax does not see, so its gradient is identically zero (summing the computed dK would store rounding noise). */
+typedef struct VllmClipLayerGrads {
+    uint16_t *norm1_w, *norm1_b, *qkv_w, *qkv_b, *proj_w, *proj_b, *norm2_w, *norm2_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b;
+} VllmClipLayerGrads;
+int vllm_clip_layer_train_sizeof(void);
+int vllm_clip_layer_saved_sizeof(void);
+int vllm_clip_layer_grads_sizeof(void);
+/* Training forward: the statement order of vllm_vit_forward where it does not fold norms, with the same kernels (where the inference
+ * encoder launches its norms, `out` is bit for bit its next hidden state); fc1 runs the *_SAVE form of `act`, whose Y keeps the
+ * inference bits.  Backward: grad_out -> grad_x (NULL allowed) and the gradients named in `grads`; fp32 accumulation, every gradient
+ * element rounded once, run-to-run identical.  B * S == 0 zero-fills the gradients.
+ * workspace: vllm_clip_layer_backward_workspace_bytes(desc, B, S) bytes serve both calls (< 0 for a refused descriptor; host-only
+ * arithmetic).  Nothing is allocated, nothing synchronised; one stream.  A refused call (VLLM_EINVAL) writes nothing. */
+/* Alignment: x, out, grad_out, grad_x, every saved tensor and gradient, the descriptor's parameters and the workspace 16 bytes. */
+long vllm_clip_layer_backward_workspace_bytes(const VllmClipLayerTrain *desc, int B, int S);
+int vllm_clip_layer_forward_train(const VllmClipLayerTrain *desc, const uint16_t *x, int B, int S, uint16_t *out,
+                                  const VllmClipLayerSaved *saved, void *workspace, long workspace_bytes, vllm_stream_t stream);
+int vllm_clip_layer_backward(const VllmClipLayerTrain *desc, const uint16_t *x, int B, int S, const uint16_t *grad_out,
+                             const VllmClipLayerSaved *saved, uint16_t *grad_x, const VllmClipLayerGrads *grads, void *workspace,
+                             long workspace_bytes, vllm_stream_t stream);
+/* Building blocks of that layer's fc1 / fc2 (tests).  `force_bits` = VLLM_GEMM_FORCE_* bits only (no epilogue number).
+ * quick_gelu_save: vllm_gemm_bf16 with VLLM_EPI_QUICK_GELU -- Y is bit for bit what that call stores (with VLLM_GEMM_FORCE_TILEWISE where
+ *   the persistent schedule would take it) -- which also writes pre [M, N] (row stride ldy) = bf16(x W^T + b), the pre-activation.
+ * quick_gelu_bwd: y = (x W^T) * q'(res[m, n]), q'(h) = s (1 + 1.702 h (1 - s)), s = sigmoid(1.702 h); `res` = the saved pre-activation
+ *   [M, N] (row stride ldr); `bias` must be NULL (VLLM_EINVAL otherwise: dh1 = (g W2) q'(h1) has none). */
+/* Alignment: X, W 16 bytes; Y, pre, res, bias 8 bytes. */
+int vllm_gemm_bf16_quick_gelu_save(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, uint16_t *pre, int M, int N,
+                                   int K, int ldx, int ldw, int ldy, int force_bits, vllm_stream_t stream);
+int vllm_gemm_bf16_quick_gelu_bwd(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, int M, int N, int K, int ldx,
+                                  int ldw, int ldy, int force_bits, const uint16_t *res, int ldr, vllm_stream_t stream);
 
 /* Training the embeddings of the vision tower (InternVisionEmbeddings.forward, modeling_intern_vit.py:82-90; HF CLIPVisionEmbeddings
  * with patch_b = NULL): patch Conv2d (kernel = stride = patch) as im2col + GEMM, class embedding in row 0, + position table.  The

@@ -170,6 +170,21 @@ class VllmVitLayerGrads(ctypes.Structure):
                                   "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2")]
 
 
+class VllmClipLayerTrain(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("hidden", "heads", "inter", "act")] + [("eps", ctypes.c_float)] + \
+               [(n, _P) for n in ("norm1_w", "norm1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "norm2_w", "norm2_b", "fc1_w", "fc1_b",
+                                  "fc2_w", "fc2_b")]
+
+
+class VllmClipLayerSaved(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ("qkv", "ctx", "lse", "x1", "h1", "a1")]
+
+
+class VllmClipLayerGrads(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ("norm1_w", "norm1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "norm2_w", "norm2_b", "fc1_w", "fc1_b",
+                                  "fc2_w", "fc2_b")]
+
+
 class VllmVitEmbed(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("hidden", "patch", "image", "pixel_is_f32")] + \
                [(n, _P) for n in ("patch_w", "patch_b", "cls", "pos")]
@@ -185,6 +200,9 @@ def check_struct_layouts():
     assert ctypes.sizeof(VllmVitLayerSaved) == L.vllm_vit_layer_saved_sizeof(), "VllmVitLayerSaved layout mismatch"
     assert ctypes.sizeof(VllmVitLayerGrads) == L.vllm_vit_layer_grads_sizeof(), "VllmVitLayerGrads layout mismatch"
     assert ctypes.sizeof(VllmVitEmbed) == L.vllm_vit_embed_sizeof(), "VllmVitEmbed layout mismatch"
+    assert ctypes.sizeof(VllmClipLayerTrain) == L.vllm_clip_layer_train_sizeof(), "VllmClipLayerTrain layout mismatch"
+    assert ctypes.sizeof(VllmClipLayerSaved) == L.vllm_clip_layer_saved_sizeof(), "VllmClipLayerSaved layout mismatch"
+    assert ctypes.sizeof(VllmClipLayerGrads) == L.vllm_clip_layer_grads_sizeof(), "VllmClipLayerGrads layout mismatch"
 
 
 EPI_BIAS, EPI_GELU, EPI_QUICK_GELU, EPI_RESIDUAL, EPI_EMBED, EPI_F32 = 0, 1, 2, 3, 4, 5

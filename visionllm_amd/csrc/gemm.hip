@@ -255,7 +255,8 @@ int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
 {
     VLLM_REQUIRE(a.M >= 0 && a.N > 0 && a.K > 0, "gemm: bad dims M=%d N=%d K=%d", a.M, a.N, a.K);
     if (a.M == 0) return VLLM_OK;
-    VLLM_REQUIRE((epi >= EPI_BIAS && epi <= EPI_GELU_BWD) || epi == EPI_MSDA || epi == EPI_GELU_SAVE || epi == EPI_RESIDUAL_SAVE,
+    VLLM_REQUIRE((epi >= EPI_BIAS && epi <= EPI_GELU_BWD) || epi == EPI_MSDA || epi == EPI_GELU_SAVE || epi == EPI_RESIDUAL_SAVE ||
+                     epi == EPI_QUICK_GELU_SAVE || epi == EPI_QUICK_GELU_BWD,
                  "gemm: unknown epilogue %d", epi);
     VLLM_REQUIRE(a.K % BK == 0, "gemm: K=%d must be a multiple of %d", a.K, BK);
     VLLM_REQUIRE(a.N % 4 == 0, "gemm: N=%d must be a multiple of 4", a.N);
@@ -268,9 +269,9 @@ int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
                  "gemm: residual epilogue needs res (8-byte aligned, ldr a multiple of 4)");
     VLLM_REQUIRE(epi != EPI_EMBED || (a.res && a.P > 0 && a.ldr % 4 == 0 && aligned8(a.res)),
                  "gemm: embed epilogue needs the position table (8-byte aligned, ldr a multiple of 4) and P");
-    VLLM_REQUIRE(epi != EPI_GELU_BWD || (a.res && !a.bias && a.ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(a.res) & 7u) == 0),
+    VLLM_REQUIRE((epi != EPI_GELU_BWD && epi != EPI_QUICK_GELU_BWD) || (a.res && !a.bias && a.ldr % 4 == 0 && (reinterpret_cast<uintptr_t>(a.res) & 7u) == 0),
                  "gemm: the GELU-backward epilogue needs the saved pre-activation `res` (8-byte aligned, ldr a multiple of 4) and no bias");
-    VLLM_REQUIRE((epi != EPI_GELU_SAVE && epi != EPI_RESIDUAL_SAVE) || (a.pre && (reinterpret_cast<uintptr_t>(a.pre) & 7u) == 0),
+    VLLM_REQUIRE((epi != EPI_GELU_SAVE && epi != EPI_RESIDUAL_SAVE && epi != EPI_QUICK_GELU_SAVE) || (a.pre && (reinterpret_cast<uintptr_t>(a.pre) & 7u) == 0),
                  "gemm: the training-forward epilogue needs an 8-byte aligned pre-activation output");
     // tall, skinny K = 256 problems (the linears of a deformable-attention layer): weight-stationary streaming kernel, bit-identical
     // to the 128 x 128 kernel below where both serve the shape (its EPI_MSDA form also takes L = 1 ... 3 levels, which the tile
@@ -316,6 +317,8 @@ int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
     case EPI_GELU_BWD: L(EPI_GELU_BWD); break;
     case EPI_GELU_SAVE: L(EPI_GELU_SAVE); break;
     case EPI_RESIDUAL_SAVE: L(EPI_RESIDUAL_SAVE); break;
+    case EPI_QUICK_GELU_SAVE: L(EPI_QUICK_GELU_SAVE); break;
+    case EPI_QUICK_GELU_BWD: L(EPI_QUICK_GELU_BWD); break;
     default: set_error("gemm: unknown epilogue %d", epi); return VLLM_EINVAL;
     }
 #undef L
@@ -362,6 +365,29 @@ extern "C" int vllm_gemm_bf16_residual_save(const uint16_t *X, const uint16_t *W
     a.scale = scale; a.res = res; a.ldr = ldr; a.pre = pre;
     gemm_force_bits(a, epilogue, FORCE_TILE | VLLM_GEMM_FORCE_MF32);   // (VLLM_GEMM_FORCE_TILEWISE is not read here)
     return gemm_bf16_launch(EPI_RESIDUAL_SAVE, a, (hipStream_t)stream);
+}
+
+// The CLIP layer's two training epilogues for the tests: `force_bits` carries VLLM_GEMM_FORCE_* only (its low byte is not an epilogue).
+extern "C" int vllm_gemm_bf16_quick_gelu_save(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, uint16_t *pre, int M,
+                                              int N, int K, int ldx, int ldw, int ldy, int force_bits, vllm_stream_t stream)
+{
+    VLLM_REQUIRE(X && W && Y && pre, "vllm_gemm_bf16_quick_gelu_save: null pointer");
+    VLLM_REQUIRE((force_bits & 0xff) == 0, "vllm_gemm_bf16_quick_gelu_save: force_bits holds VLLM_GEMM_FORCE_* bits only");
+    GemmArgs a = gemm_args(X, ldx, W, ldw, bias, Y, ldy, M, N, K);
+    a.pre = pre;
+    gemm_force_bits(a, force_bits, FORCE_TILE | VLLM_GEMM_FORCE_MF32);   // (never persistent: VLLM_GEMM_FORCE_TILEWISE is not read here)
+    return gemm_bf16_launch(EPI_QUICK_GELU_SAVE, a, (hipStream_t)stream);
+}
+
+extern "C" int vllm_gemm_bf16_quick_gelu_bwd(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, int M, int N, int K,
+                                             int ldx, int ldw, int ldy, int force_bits, const uint16_t *res, int ldr, vllm_stream_t stream)
+{
+    VLLM_REQUIRE(X && W && Y, "vllm_gemm_bf16_quick_gelu_bwd: null pointer");
+    VLLM_REQUIRE((force_bits & 0xff) == 0, "vllm_gemm_bf16_quick_gelu_bwd: force_bits holds VLLM_GEMM_FORCE_* bits only");
+    GemmArgs a = gemm_args(X, ldx, W, ldw, bias, Y, ldy, M, N, K);
+    a.res = res; a.ldr = ldr;
+    gemm_force_bits(a, force_bits, FORCE_TILE | VLLM_GEMM_FORCE_MF32);
+    return gemm_bf16_launch(EPI_QUICK_GELU_BWD, a, (hipStream_t)stream);
 }
 
 extern "C" int vllm_gemm_bf16_ln(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, int M, int N, int K, int ldx,

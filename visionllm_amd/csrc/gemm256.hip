@@ -886,6 +886,7 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
         // schedule takes that one, one workgroup per tile WITHOUT a stream-K tail does (same MFMA sequence per tile, same epilogue
         // arithmetic: test_gemm256_persistent_schedule), and stores the pre-activation as well
         if (epi == EPI_GELU_SAVE && gemm256p_takes(EPI_GELU, b, cus)) a.sk_tiles = 0;
+        if (epi == EPI_QUICK_GELU_SAVE && gemm256p_takes(EPI_QUICK_GELU, b, cus)) a.sk_tiles = 0;   // (the CLIP layer's fc1: the same rule)
     }
     if (a.dry_run) return VLLM_EINVAL;   // (asked only whether the persistent schedule would take this GEMM: no message, no launch)
     VLLM_REQUIRE(!a.ln_wide, "gemm256: wide folded-norm statistics are implemented by the persistent schedule only (at least as many tiles as CUs, "
@@ -914,7 +915,7 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256_bf16_kernel<E, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256_bf16_kernel<E, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
         SETATTR(EPI_BIAS); SETATTR(EPI_GELU); SETATTR(EPI_QUICK_GELU); SETATTR(EPI_RESIDUAL); SETATTR(EPI_EMBED); SETATTR(EPI_F32);
-        SETATTR(EPI_GELU_BWD); SETATTR(EPI_GELU_SAVE); SETATTR(EPI_RESIDUAL_SAVE);
+        SETATTR(EPI_GELU_BWD); SETATTR(EPI_GELU_SAVE); SETATTR(EPI_RESIDUAL_SAVE); SETATTR(EPI_QUICK_GELU_SAVE); SETATTR(EPI_QUICK_GELU_BWD);
 #undef SETATTR
     }
 #define L(E) do { if (mf32) VLLM_LAUNCH((gemm256_bf16_kernel<E, 4, true>), grid, block, lds, st, a); \
@@ -939,6 +940,8 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
     case EPI_GELU_BWD: L(EPI_GELU_BWD); break;
     case EPI_GELU_SAVE: L(EPI_GELU_SAVE); break;
     case EPI_RESIDUAL_SAVE: L(EPI_RESIDUAL_SAVE); break;
+    case EPI_QUICK_GELU_SAVE: L(EPI_QUICK_GELU_SAVE); break;
+    case EPI_QUICK_GELU_BWD: L(EPI_QUICK_GELU_BWD); break;
     default: set_error("gemm256: unknown epilogue %d", epi); return VLLM_EINVAL;
     }
 #undef L

@@ -33,6 +33,13 @@ __device__ __forceinline__ float quick_gelu(float x)
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * x));
 }
 
+// d quick_gelu / dh = s (1 + 1.702 h (1 - s)), s = sigmoid(1.702 h)   (CLIP layer backward, EPI_QUICK_GELU_BWD); |q'| <= 1.0999
+__device__ __forceinline__ float quick_gelu_grad(float h)
+{
+    const float s = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * h));
+    return s * fmaf(1.702f * h, 1.0f - s, 1.0f);
+}
+
 struct EpiCols {   // per-n constants, loaded once per 16-column tile
     float bia[4], scl[4];
 };
@@ -78,7 +85,15 @@ __device__ __forceinline__ void epi_value(const GemmArgs &a, int m, int n, const
         const uint2_t rr = *reinterpret_cast<const uint2_t *>(a.res + (size_t)m * a.ldr + n);
         v[0] *= gelu_erf_grad(bf16lo_to_f32(rr.x)); v[1] *= gelu_erf_grad(bf16hi_to_f32(rr.x));
         v[2] *= gelu_erf_grad(bf16lo_to_f32(rr.y)); v[3] *= gelu_erf_grad(bf16hi_to_f32(rr.y));
-    } else if (EPI == EPI_QUICK_GELU) {
+    } else if (EPI == EPI_QUICK_GELU_BWD) {
+        // y = acc * q'(res[m, n]), res = the saved pre-activation (no bias: the launcher refuses one)
+        const uint2_t rr = *reinterpret_cast<const uint2_t *>(a.res + (size_t)m * a.ldr + n);
+        v[0] *= quick_gelu_grad(bf16lo_to_f32(rr.x)); v[1] *= quick_gelu_grad(bf16hi_to_f32(rr.x));
+        v[2] *= quick_gelu_grad(bf16lo_to_f32(rr.y)); v[3] *= quick_gelu_grad(bf16hi_to_f32(rr.y));
+    } else if (EPI == EPI_QUICK_GELU || EPI == EPI_QUICK_GELU_SAVE) {
+        // training forward: EPI_QUICK_GELU's arithmetic below, and the pre-activation leaves too (bf16, row stride ldy) for the backward's q'
+        if (EPI == EPI_QUICK_GELU_SAVE)
+            *reinterpret_cast<uint2_t *>(a.pre + (size_t)m * a.ldy + n) = (uint2_t){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
         // x * sigmoid(1.702 x), x = acc + bias: the exponent -1.702 log2(e) (acc + bias) is ONE fma of the accumulator (the bias
         // times the constant is per column) instead of add + multiply -- 5.5 instead of 6.5 VALU per element of a tile whose
         // epilogue nothing overlaps

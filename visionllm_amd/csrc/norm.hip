@@ -319,6 +319,123 @@ __global__ __launch_bounds__(RB_THREADS) void rms_bwd_kernel(const uint16_t *__r
     }
 }
 
+// nn.LayerNorm backward inside the CLIP layer's chain (clip_train.cpp): rms_bwd_kernel's walk with a mean.  Per row the mean and the
+// second moment about it are recomputed from x in fp32 (two passes over the registers: no cancellation);  xhat = (x - mean) r,
+// g = grad_y gamma,  grad_x = r (g - mean(g) - xhat mean(g xhat)) [+ grad_res]  (one rounding),  grad_w = sum_rows grad_y xhat  (xhat NOT
+// rounded),  grad_b = sum_rows grad_y.  The partials are [2][nbv][C]: grad_w's, then grad_b's.  A chunk past the row's end (a thread
+// without work at this C) must stay out of the second moment: its x - mean is masked to zero, and everything behind it is zero too.
+template <int MAXCH, int TPR, bool DX>
+__global__ __launch_bounds__(RB_THREADS) void ln_res_bwd_kernel(const uint16_t *__restrict__ x, int ldx, const uint16_t *gy, int ldgy,
+                                                                const uint16_t *__restrict__ w, uint16_t *gx, int ldgx,
+                                                                const uint16_t *__restrict__ gres, int ldgr, float *__restrict__ part,
+                                                                long rows, int C, int rpb, int nbv, float eps)
+{
+    __shared__ float red[2][4];
+    constexpr int RG = RB_THREADS / TPR;
+    const int tl = threadIdx.x % TPR, nchunk = C >> 3;
+    const int vb = blockIdx.x * RG + threadIdx.x / TPR;
+    float wf[MAXCH][8], accw[MAXCH][8], accb[MAXCH][8];
+#pragma unroll
+    for (int i = 0; i < MAXCH; ++i) {
+        const int c = i * TPR + tl;
+        uint4_t wv = {0, 0, 0, 0};
+        if (c < nchunk) wv = *reinterpret_cast<const uint4_t *>(w + c * 8);
+        bf16x8_to_f32(wv, wf[i]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) accw[i][k] = accb[i][k] = 0.f;
+    }
+    const float invC = 1.f / (float)C;
+    const long r0 = (long)vb * rpb, r1 = r0 + rpb < rows ? r0 + rpb : rows;   // (vb >= nbv: an empty range)
+    uint4_t nx[MAXCH], ng[MAXCH], nr[MAXCH];
+    auto request = [&](long r) {
+#pragma unroll
+        for (int i = 0; i < MAXCH; ++i) {
+            const int c = i * TPR + tl;
+            nx[i] = ng[i] = nr[i] = (uint4_t){0, 0, 0, 0};
+            if (c < nchunk && r < r1) {
+                nx[i] = *reinterpret_cast<const uint4_t *>(x + r * ldx + c * 8);
+                ng[i] = *reinterpret_cast<const uint4_t *>(gy + r * ldgy + c * 8);
+                if (DX && gres) nr[i] = *reinterpret_cast<const uint4_t *>(gres + r * ldgr + c * 8);
+            }
+        }
+    };
+    request(r0);
+    int par = 0;
+    for (int it = 0; it < rpb; ++it) {   // (the same trip count in every thread: the row sums are block-wide barriers)
+        const long r = r0 + it;
+        float xv[MAXCH][8], gv[MAXCH][8];
+        uint4_t rv[MAXCH];
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXCH; ++i) {
+            bf16x8_to_f32(nx[i], xv[i]);
+            bf16x8_to_f32(ng[i], gv[i]);
+            rv[i] = nr[i];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s += xv[i][k];
+        }
+        request(r + 1);   // (another row than the one stored below: grad_x may alias grad_y)
+        const float mean = rb_row_sum<TPR>(s, red, par) * invC;
+        par ^= 1;
+        float vs = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXCH; ++i) {
+            const bool own = i * TPR + tl < nchunk;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float dlt = own ? xv[i][k] - mean : 0.f;
+                xv[i][k] = dlt;
+                vs = fmaf(dlt, dlt, vs);
+            }
+        }
+        const float rstd = rsqrtf(rb_row_sum<TPR>(vs, red, par) * invC + eps);
+        par ^= 1;
+        float sg = 0.f, sgx = 0.f;
+#pragma unroll
+        for (int i = 0; i < MAXCH; ++i)
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float xh = xv[i][k] * rstd;
+                xv[i][k] = xh;
+                accw[i][k] = fmaf(gv[i][k], xh, accw[i][k]);   // (a row past the range was requested as zeros)
+                accb[i][k] += gv[i][k];
+                gv[i][k] *= wf[i][k];
+                sg += gv[i][k];
+                sgx = fmaf(gv[i][k], xh, sgx);
+            }
+        if (DX) {
+            const float mg = rb_row_sum<TPR>(sg, red, par) * invC;
+            par ^= 1;
+            const float mgx = rb_row_sum<TPR>(sgx, red, par) * invC;
+            par ^= 1;
+#pragma unroll
+            for (int i = 0; i < MAXCH; ++i) {
+                const int c = i * TPR + tl;
+                if (c < nchunk && r < r1) {
+                    float rf[8], o[8];
+                    bf16x8_to_f32(rv[i], rf);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) o[k] = rstd * (gv[i][k] - mg - xv[i][k] * mgx) + rf[k];
+                    const uint4_t ov = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])};
+                    *reinterpret_cast<uint4_t *>(gx + r * ldgx + c * 8) = ov;
+                }
+            }
+        }
+    }
+    if (vb >= nbv) return;
+    float *pw = part + (size_t)vb * C, *pb = part + ((size_t)nbv + vb) * C;
+#pragma unroll
+    for (int i = 0; i < MAXCH; ++i) {
+        const int c = i * TPR + tl;
+        if (c < nchunk) {
+            *reinterpret_cast<float4_t *>(pw + c * 8) = (float4_t){accw[i][0], accw[i][1], accw[i][2], accw[i][3]};
+            *reinterpret_cast<float4_t *>(pw + c * 8 + 4) = (float4_t){accw[i][4], accw[i][5], accw[i][6], accw[i][7]};
+            *reinterpret_cast<float4_t *>(pb + c * 8) = (float4_t){accb[i][0], accb[i][1], accb[i][2], accb[i][3]};
+            *reinterpret_cast<float4_t *>(pb + c * 8 + 4) = (float4_t){accb[i][4], accb[i][5], accb[i][6], accb[i][7]};
+        }
+    }
+}
+
 template <int MAXCH, int TPR, bool DY>
 __global__ __launch_bounds__(RB_THREADS) void ls_bwd_kernel(const uint16_t *__restrict__ go, int ldgo, const uint16_t *__restrict__ y, int ldy,
                                                             const uint16_t *__restrict__ ls, uint16_t *__restrict__ gy, int ldgy,
@@ -476,6 +593,46 @@ int rms_bwd_launch(const uint16_t *x, int ldx, const uint16_t *gy, int ldgy, con
     return VLLM_OK;
 }
 
+long ln_res_bwd_workspace_bytes(long rows, int C)
+{
+    if (rows < 0 || C <= 0 || C % 64 != 0 || C > RB_MAX_C) return -1;
+    return 2L * rb_plan(rows, C).nbv * C * 4;
+}
+
+int ln_res_bwd_launch(const uint16_t *x, int ldx, const uint16_t *gy, int ldgy, const uint16_t *w, float eps, long rows, int C, uint16_t *gx,
+                      int ldgx, const uint16_t *gres, int ldgr, uint16_t *gw, uint16_t *gb, void *ws, long ws_bytes, hipStream_t st)
+{
+    VLLM_REQUIRE(rows >= 0 && C > 0 && C % 64 == 0 && C <= RB_MAX_C, "layernorm_backward_res: C=%d must be a multiple of 64 and <= %d", C, RB_MAX_C);
+    VLLM_REQUIRE((!gw || (reinterpret_cast<uintptr_t>(gw) & 1u) == 0) && (!gb || (reinterpret_cast<uintptr_t>(gb) & 1u) == 0),
+                 "layernorm_backward_res: misaligned weight / bias gradient");
+    if (rows == 0) {   // no rows: the column sums are empty sums
+        if (gw) VLLM_REQUIRE(hipMemsetAsync(gw, 0, (size_t)C * 2, st) == hipSuccess, "layernorm_backward_res: memset failed");
+        if (gb) VLLM_REQUIRE(hipMemsetAsync(gb, 0, (size_t)C * 2, st) == hipSuccess, "layernorm_backward_res: memset failed");
+        return VLLM_OK;
+    }
+    VLLM_REQUIRE(x && gy && w && aligned16(x) && aligned16(gy) && aligned16(w), "layernorm_backward_res: x, grad_y and weight must be 16-byte aligned device pointers");
+    VLLM_REQUIRE(ldx >= C && ldgy >= C && ldx % 8 == 0 && ldgy % 8 == 0 && (!gx || (aligned16(gx) && ldgx >= C && ldgx % 8 == 0)) &&
+                     (!gres || (gx && aligned16(gres) && ldgr >= C && ldgr % 8 == 0)),
+                 "layernorm_backward_res: row strides must cover the row and be multiples of 8 elements, pointers 16-byte aligned (grad_res needs grad_x)");
+    if (!gx && !gw && !gb) return VLLM_OK;
+    const RbPlan p = rb_plan(rows, C);
+    const long need = 2L * p.nbv * C * 4;
+    VLLM_REQUIRE(ws && aligned16(ws) && ws_bytes >= need, "layernorm_backward_res: workspace too small or misaligned (%ld < %ld bytes)", ws_bytes, need);
+    float *part = reinterpret_cast<float *>(ws);
+    const dim3 grid((unsigned)p.grid), block(RB_THREADS);
+#define L2(M, T, D) VLLM_LAUNCH((ln_res_bwd_kernel<M, T, D>), grid, block, 0, st, x, ldx, gy, ldgy, w, gx, ldgx, gres, ldgr, part, rows, C, p.rpb, p.nbv, eps)
+#define L1(M, T) do { if (gx) L2(M, T, true); else L2(M, T, false); } while (0)
+    if (p.tpr == 64) L1(1, 64); else if (p.tpr == 128) L1(1, 128); else if (p.maxch == 1) L1(1, 256); else if (p.maxch == 2) L1(2, 256); else L1(4, 256);
+#undef L1
+#undef L2
+    VLLM_CHECK_LAUNCH("ln_res_bwd_kernel");
+    if (gw || gb) {
+        VLLM_LAUNCH(colsum_reduce_kernel, dim3((unsigned)ceil_div(C, 32), 2u), dim3(256), 0, st, part, p.nbv, C, gw, gb);
+        VLLM_CHECK_LAUNCH("colsum_reduce_kernel");
+    }
+    return VLLM_OK;
+}
+
 long ls_bwd_workspace_bytes(long rows, int C) { return rms_bwd_workspace_bytes(rows, C, 1); }
 
 int ls_bwd_launch(const uint16_t *go, int ldgo, const uint16_t *y, int ldy, const uint16_t *ls, long rows, int C, uint16_t *gy, int ldgy,
@@ -535,6 +692,16 @@ extern "C" int vllm_rmsnorm_backward_bf16(const uint16_t *x, int ldx, const uint
 {
     return rms_bwd_launch(x, ldx, grad_y, ldg, weight, weight2, G, eps, rows, C, grad_x, ldgx, grad_res, ldgr, grad_w, grad_w2, workspace,
                           workspace_bytes, (hipStream_t)stream);
+}
+
+extern "C" long vllm_layernorm_backward_res_workspace_bytes(long rows, int C) { return ln_res_bwd_workspace_bytes(rows, C); }
+
+extern "C" int vllm_layernorm_backward_res_bf16(const uint16_t *x, int ldx, const uint16_t *grad_y, int ldg, const uint16_t *weight, float eps,
+                                                long rows, int C, uint16_t *grad_x, int ldgx, const uint16_t *grad_res, int ldgr,
+                                                uint16_t *grad_w, uint16_t *grad_b, void *workspace, long workspace_bytes, vllm_stream_t stream)
+{
+    return ln_res_bwd_launch(x, ldx, grad_y, ldg, weight, eps, rows, C, grad_x, ldgx, grad_res, ldgr, grad_w, grad_b, workspace, workspace_bytes,
+                             (hipStream_t)stream);
 }
 
 extern "C" long vllm_layerscale_backward_workspace_bytes(long rows, int C) { return ls_bwd_workspace_bytes(rows, C); }

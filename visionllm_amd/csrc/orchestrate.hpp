@@ -1,4 +1,4 @@
-// Host-side scaffolding shared by the orchestrators (vit.cpp, vit_train.cpp, bridge_train.cpp, embed_train.hip, msda_layer.hip): the
+// Host-side scaffolding shared by the orchestrators (vit.cpp, vit_train.cpp, clip_train.cpp, bridge_train.cpp, embed_train.hip, msda_layer.hip): the
 // pieces every entry point that strings kernels together on the caller's stream used to copy from the one before.  Host code only.
 #pragma once
 #include <initializer_list>
@@ -33,7 +33,7 @@ inline int zero_bf16(hipStream_t st, const char *who, std::initializer_list<Bf16
 }
 
 // Input gradient of a Linear with weight W [out, in] (dense rows): dX [M, in] = epilogue(dY [M, out] W), as the bf16 GEMM on W^T, which is
-// written into wt [in, out] first.  `pre` is the saved pre-activation [M, in] of EPI_GELU_BWD (null otherwise); dX is fp32 for EPI_F32.
+// written into wt [in, out] first.  `pre` is the saved pre-activation [M, in] of EPI_GELU_BWD / EPI_QUICK_GELU_BWD (null otherwise); dX is fp32 for EPI_F32.
 inline int linear_dgrad(hipStream_t st, int epi, const uint16_t *dY, const uint16_t *W, int out, int in, long M, uint16_t *wt, void *dX,
                         const uint16_t *pre, void *sk, long sk_bytes)
 {
