@@ -221,6 +221,63 @@ int vllm_msda_prep_f32(float *offsets_to_locations, float *logits_to_weights, co
 /* Alignment (vllm_f32_to_bf16): src 16 bytes, dst 8 bytes. */
 int vllm_f32_to_bf16(const float *src, uint16_t *dst, long n, vllm_stream_t stream);
 
+/* Training the layer (bf16 modules): the forward pass above with the tensors its backward needs kept in CALLER memory, and the backward
+ * from grad_out to grad_query, grad_input_flatten and the gradients of the eight parameters.  Gradients with respect to
+ * reference_points are not computed.
+ *
+ * vllm_msda_layer_forward_train enqueues exactly the launches of vllm_msda_layer_forward for the same arguments (`out` has the same
+ * bits).  `saved` (vllm_msda_layer_saved_bytes(desc, B, Lq, S) bytes, < 0 for a refused descriptor) receives, each piece rounded up
+ * to 256 bytes: the projected value [B*S, C] (fp32; bf16 in the first half of the same piece on the decoder route, Lq != S), the
+ * sampling locations fp32 [B*Lq, M*L*P*2], the softmax weights fp32 [B*Lq, M*L*P], and the bf16 operator output [B*Lq, C].
+ * *value_is_bf16 (HOST memory, may be NULL) is set to 1 where the value was stored as bf16, else 0, before the call returns -- no
+ * synchronisation; pass it on to the backward.  workspace: vllm_msda_layer_forward_train_workspace_bytes bytes.
+ *
+ * vllm_msda_layer_backward: grad_out [B*Lq, C] bf16; grad_query [B*Lq, C], grad_input_flatten [B*S, C] and the members of
+ * VllmMsdaLayerGrads (shaped like their parameters) are bf16 and may each be NULL (not needed: the product and whatever only it
+ * needed is skipped), except that a bias gradient comes out of its weight gradient's launch (pass both).  Every non-NULL gradient
+ * is written completely; rows of grad_input_flatten under a padded key are exact zeros.  B * Lq == 0 zero-fills the parameter
+ * gradients and grad_input_flatten.  grad_value is accumulated with float atomics, so grad_input_flatten and the value_proj gradients
+ * may differ in the last bits between two runs; every other output is deterministic.  workspace:
+ * vllm_msda_layer_backward_workspace_bytes bytes (< 0 for a refused descriptor).  The three size queries are host-only.
+ * One stream, no allocation, no synchronisation; a refused call (bad descriptor, NULL or misaligned pointer, short or misaligned
+ * saved memory or workspace: VLLM_EINVAL) has enqueued nothing. */
+typedef struct VllmMsdaLayerGrads {
+    uint16_t *value_proj_w, *value_proj_b;
+    uint16_t *sampling_offsets_w, *sampling_offsets_b;
+    uint16_t *attention_weights_w, *attention_weights_b;
+    uint16_t *output_proj_w, *output_proj_b;
+} VllmMsdaLayerGrads;
+int vllm_msda_layer_grads_sizeof(void);
+long vllm_msda_layer_saved_bytes(const VllmMsdaLayerDesc *desc, int B, int Lq, int S);
+long vllm_msda_layer_forward_train_workspace_bytes(const VllmMsdaLayerDesc *desc, int B, int Lq, int S);
+long vllm_msda_layer_backward_workspace_bytes(const VllmMsdaLayerDesc *desc, int B, int Lq, int S);
+/* Alignment: query, input_flatten, out, every weight / bias of the descriptor, saved and workspace 16 bytes; reference_points 8 bytes
+ * (16 with ref_dim 4). */
+int vllm_msda_layer_forward_train(const VllmMsdaLayerDesc *desc, const uint16_t *query, const float *reference_points,
+                                  const uint16_t *input_flatten, const uint8_t *padding_mask, const int64_t *spatial_shapes,
+                                  const int64_t *level_start_index, int B, int Lq, int S, uint16_t *out, void *saved,
+                                  long saved_bytes, int *value_is_bf16, void *workspace, long workspace_bytes,
+                                  vllm_stream_t stream);
+/* Alignment: as vllm_msda_layer_forward_train; grad_out and every gradient 16 bytes. */
+int vllm_msda_layer_backward(const VllmMsdaLayerDesc *desc, const uint16_t *query, const float *reference_points,
+                             const uint16_t *input_flatten, const uint8_t *padding_mask, const int64_t *spatial_shapes,
+                             const int64_t *level_start_index, int B, int Lq, int S, const void *saved, long saved_bytes,
+                             int value_is_bf16, const uint16_t *grad_out, uint16_t *grad_query, uint16_t *grad_input_flatten,
+                             const VllmMsdaLayerGrads *grads, void *workspace, long workspace_bytes, vllm_stream_t stream);
+/* The three elementwise kernels of the backward, exposed for the parity tests.
+ * vllm_msda_prep_backward_f32: the backward of vllm_msda_prep_f32 -- dq [R, npad] bf16, columns [0, 2 M L P) = grad_loc * (sx, sy)
+ * (the location arithmetic's scale), [2 M L P, 3 M L P) = w * (grad_attw - sum_{L*P} grad_attw w) per head (w the softmax weights),
+ * [3 M L P, npad) zeros; npad >= 3 M L P.  16-byte aligned operands and npad % 8 == 0 select the vector kernels (same results).
+ * vllm_f32_to_bf16_masked: dst [rows, cols] bf16 = src, round to nearest even, rows with a non-zero row_mask byte (row_mask may be
+ * NULL) written as zeros whatever src holds there.  vllm_bf16_to_f32: n elements widened. */
+/* Alignment: element alignment only (16 bytes for the vector kernels). */
+int vllm_msda_prep_backward_f32(const float *grad_loc, const float *grad_attw, const float *attw, const float *reference_points,
+                                const int64_t *spatial_shapes, long R, int M, int L, int P, int ref_dim, int use_4d_normalizer,
+                                uint16_t *dq, int npad, vllm_stream_t stream);
+int vllm_f32_to_bf16_masked(const float *src, uint16_t *dst, long rows, int cols, const uint8_t *row_mask, vllm_stream_t stream);
+/* Alignment: src and dst 16 bytes. */
+int vllm_bf16_to_f32(const uint16_t *src, float *dst, long n, vllm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * f3. DCNv3 forward (InternImage det backbone).
  *

@@ -155,6 +155,11 @@ class VllmMsdaLayerDesc(ctypes.Structure):
                                   "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
 
 
+class VllmMsdaLayerGrads(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ("value_proj_w", "value_proj_b", "sampling_offsets_w", "sampling_offsets_b",
+                                  "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
+
+
 class VllmVitLayerTrain(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("hidden", "heads", "inter")] + [("eps", ctypes.c_float)] + \
                [(n, _P) for n in ("norm1_w", "qkv_w", "qkv_b", "q_norm_w", "k_norm_w", "proj_w", "proj_b", "ls1", "norm2_w",
@@ -193,6 +198,7 @@ class VllmVitEmbed(ctypes.Structure):
 def check_struct_layouts():
     L = lib()
     assert ctypes.sizeof(VllmMsdaLayerDesc) == L.vllm_msda_layer_desc_sizeof(), "VllmMsdaLayerDesc layout mismatch"
+    assert ctypes.sizeof(VllmMsdaLayerGrads) == L.vllm_msda_layer_grads_sizeof(), "VllmMsdaLayerGrads layout mismatch"
     assert ctypes.sizeof(VllmVitDesc) == L.vllm_vit_desc_sizeof(), "VllmVitDesc layout mismatch"
     assert ctypes.sizeof(VllmVitLayer) == L.vllm_vit_layer_sizeof(), "VllmVitLayer layout mismatch"
     assert ctypes.sizeof(VllmBridgeDesc) == L.vllm_bridge_desc_sizeof(), "VllmBridgeDesc layout mismatch"

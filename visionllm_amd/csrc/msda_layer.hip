@@ -16,6 +16,7 @@
 #include "common.hpp"
 #include <stdlib.h>
 #include "orchestrate.hpp"
+#include "msda_layer.hpp"
 #include "msda_sample.hpp"
 
 namespace vllm {
@@ -187,7 +188,7 @@ using namespace vllm;
 
 extern "C" unsigned long vllm_msda_layer_desc_sizeof(void) { return sizeof(VllmMsdaLayerDesc); }
 
-static int check_desc(const VllmMsdaLayerDesc *d)
+int vllm::msda_layer_check_desc(const VllmMsdaLayerDesc *d)
 {
     VLLM_REQUIRE(d, "msda_layer: null descriptor");
     VLLM_REQUIRE(d->d_model > 0 && d->n_heads > 0 && d->n_levels > 0 && d->n_points > 0, "msda_layer: bad sizes");
@@ -204,7 +205,7 @@ static int check_desc(const VllmMsdaLayerDesc *d)
 
 extern "C" long vllm_msda_layer_workspace_bytes(const VllmMsdaLayerDesc *d, int B, int Lq, int S)
 {
-    if (check_desc(d) != VLLM_OK || B < 0 || Lq < 0 || S < 0) return -1;
+    if (msda_layer_check_desc(d) != VLLM_OK || B < 0 || Lq < 0 || S < 0) return -1;
     return layer_ws(d, B, Lq, S).total;
 }
 
@@ -228,21 +229,38 @@ extern "C" int vllm_msda_layer_forward(const VllmMsdaLayerDesc *d, const uint16_
                                        const int64_t *lsi, int B, int Lq, int S, uint16_t *out, void *workspace, long ws_bytes,
                                        vllm_stream_t stream)
 {
-    TRY(check_desc(d));
+    TRY(msda_layer_check_desc(d));
     VLLM_REQUIRE(B >= 0 && Lq >= 0 && S >= 0, "msda_layer: negative size");
     if (B == 0 || Lq == 0) return VLLM_OK;
-    VLLM_REQUIRE(S > 0, "msda_layer: empty value");
-    VLLM_REQUIRE(query && ref && input_flatten && shapes && lsi && out, "msda_layer: null pointer");
     const LayerWs w = layer_ws(d, B, Lq, S);
     VLLM_REQUIRE(workspace && aligned16(workspace) && ws_bytes >= w.total, "msda_layer: workspace too small (%ld < %ld bytes) or misaligned", ws_bytes,
                  w.total);
-    VLLM_REQUIRE((long)B * S < (1L << 31) && (long)B * Lq < (1L << 31), "msda_layer: too many rows for one launch");
-    hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
+    const MsdaLayerBufs b = {(float *)(ws + w.value), (float *)(ws + w.off), (float *)(ws + w.logit), (float *)(ws + w.opout),
+                             (uint16_t *)(ws + w.opout_bf16)};
+    return msda_layer_run(d, query, ref, input_flatten, padding_mask, shapes, lsi, B, Lq, S, out, b, nullptr, (hipStream_t)stream);
+}
+
+// (the bf16-value operator needs 8 channels per lane: D / 8 a power of two, 8 <= D <= 512 -- vllm_msda_forward_bf16's own
+//  precondition; a d_model-256 layer with 64 heads (D = 4) keeps the fp32 value path instead of failing there.  ADVICE r4)
+bool vllm::msda_layer_value_may_be_bf16(const VllmMsdaLayerDesc *d, int Lq, int S)
+{
+    const int D = d->d_model / d->n_heads;
+    return Lq != S && D >= 8 && D <= 512 && D % 8 == 0 && ((D / 8) & (D / 8 - 1)) == 0;
+}
+
+// Every launch of the layer, behind the entries' argument gates (descriptor checked, B, Lq > 0, buffers sized and 16-byte aligned).
+int vllm::msda_layer_run(const VllmMsdaLayerDesc *d, const uint16_t *query, const float *ref, const uint16_t *input_flatten,
+                         const uint8_t *padding_mask, const int64_t *shapes, const int64_t *lsi, int B, int Lq, int S, uint16_t *out,
+                         const MsdaLayerBufs &b, int *value_is_bf16, hipStream_t st)
+{
+    VLLM_REQUIRE(S > 0, "msda_layer: empty value");
+    VLLM_REQUIRE(query && ref && input_flatten && shapes && lsi && out, "msda_layer: null pointer");
+    VLLM_REQUIRE((long)B * S < (1L << 31) && (long)B * Lq < (1L << 31), "msda_layer: too many rows for one launch");
+    vllm_stream_t stream = (vllm_stream_t)st;
     const int C = d->d_model, M = d->n_heads, L = d->n_levels, P = d->n_points, D = C / M, MLP = M * L * P;
-    float *value = (float *)(ws + w.value), *off = (float *)(ws + w.off), *lg = (float *)(ws + w.logit);
-    float *opout = (float *)(ws + w.opout);
-    uint16_t *opb = (uint16_t *)(ws + w.opout_bf16);
+    float *value = b.value, *off = b.loc, *lg = b.attw, *opout = b.opout;
+    uint16_t *opb = b.opout_bf16;
     prof_mark(PT_MSDA_LAYER, st);
     // value = value_proj(input_flatten), padded keys zeroed (ms_deform_attn.py:106-109) -- fp32 [B, S, M, D] where the LDS-tiled
     // operator can run (its windows are fp32: a bf16 value would cost its gather conversions it has no issue slots for, NOTES/rounds_1_to_4.md 3.6).
@@ -253,10 +271,8 @@ extern "C" int vllm_msda_layer_forward(const VllmMsdaLayerDesc *d, const uint16_
     GemmArgs va = gemm_args(input_flatten, C, d->value_proj_w, C, d->value_proj_b, value16, C, B * S, C, C);
     va.variant = 0; va.direct_store = 0;   // built for the streaming kernel (gemm_skinny_takes below), which a forced variant would bypass
     va.row_mask = padding_mask;
-    // (the bf16-value operator needs 8 channels per lane: D / 8 a power of two, 8 <= D <= 512 -- vllm_msda_forward_bf16's own
-    //  precondition; a d_model-256 layer with 64 heads (D = 4) keeps the fp32 value path instead of failing there.  ADVICE r4)
-    const bool d_bf16_ok = D >= 8 && D <= 512 && D % 8 == 0 && ((D / 8) & (D / 8 - 1)) == 0;
-    const bool v16 = Lq != S && d_bf16_ok && msda_layer_value_bf16() && gemm_skinny_takes(EPI_BIAS, va);
+    const bool v16 = msda_layer_value_may_be_bf16(d, Lq, S) && msda_layer_value_bf16() && gemm_skinny_takes(EPI_BIAS, va);
+    if (value_is_bf16) *value_is_bf16 = v16 ? 1 : 0;
     if (v16) TRY(gemm_bf16_launch(EPI_BIAS, va, st));
     else
     TRY(gemm(st, EPI_F32, input_flatten, C, d->value_proj_w, C, d->value_proj_b, (uint16_t *)value, C, B * S, C, C, nullptr,

@@ -1,4 +1,4 @@
-// Host-side scaffolding shared by the orchestrators (vit.cpp, vit_train.cpp, clip_train.cpp, bridge_train.cpp, embed_train.hip, msda_layer.hip): the
+// Host-side scaffolding shared by the orchestrators (vit.cpp, vit_train.cpp, clip_train.cpp, bridge_train.cpp, embed_train.hip, msda_layer.hip, msda_layer_train.cpp): the
 // pieces every entry point that strings kernels together on the caller's stream used to copy from the one before.  Host code only.
 #pragma once
 #include <initializer_list>

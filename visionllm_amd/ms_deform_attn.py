@@ -402,6 +402,160 @@ def msda_layer_prepare(query, reference_points, input_flatten, spatial_shapes, l
     return launch
 
 
+_LAYER_LINEARS = ("value_proj", "sampling_offsets", "attention_weights", "output_proj")   # the order of VllmMsdaLayerDesc / VllmMsdaLayerGrads
+
+
+def msda_layer_train_ok(query, input_flatten, *linears, reference_points=None):
+    """The native training node (vllm_msda_layer_forward_train / vllm_msda_layer_backward) serves bf16 modules on the GPU whose every
+    weight and bias is bf16; it does not differentiate with respect to the reference points (iterative box refinement that lets
+    gradients flow into them keeps the composed path)."""
+    if not (query.is_cuda and input_flatten.is_cuda and query.dtype == torch.bfloat16 and input_flatten.dtype == torch.bfloat16):
+        return False
+    if reference_points is not None and reference_points.requires_grad:
+        return False
+    if query.shape[-1] % 64 != 0:
+        return False
+    return all(lin.bias is not None and lin.weight.is_cuda and lin.weight.dtype == torch.bfloat16 and lin.bias.dtype == torch.bfloat16
+               for lin in linears)
+
+
+def _native_training_wanted(query, input_flatten, linears, reference_points):
+    """grad is enabled, something requires grad and the native node can serve the call"""
+    if not torch.is_grad_enabled():
+        return False
+    if not (query.requires_grad or input_flatten.requires_grad or any(p.requires_grad for lin in linears for p in lin.parameters())):
+        return False
+    return msda_layer_train_ok(query, input_flatten, *linears, reference_points=reference_points)
+
+
+def _train_desc(meta, ref_dim, C, params, keep):
+    n_heads, n_levels, n_points, use_4d = meta
+    desc = _lib.VllmMsdaLayerDesc()
+    desc.d_model, desc.n_heads, desc.n_levels, desc.n_points = C, n_heads, n_levels, n_points
+    desc.ref_dim, desc.use_4d_normalizer = ref_dim, int(bool(use_4d))
+    for i, name in enumerate(_LAYER_LINEARS):
+        w, b = _lib.aligned(params[2 * i].detach()), _lib.aligned(params[2 * i + 1].detach())
+        keep += [w, b]
+        setattr(desc, name + "_w", w.data_ptr())
+        setattr(desc, name + "_b", b.data_ptr())
+    return desc
+
+
+def _train_operands(query, reference_points, input_flatten, spatial_shapes, level_start_index, padding_mask):
+    """the C call's operands: contiguous, aligned as include/vllm_hip.h asks (a view at another storage offset is copied)"""
+    q, x = _lib.aligned(query.detach()), _lib.aligned(input_flatten.detach())
+    ref = _lib.aligned(reference_points.detach().to(torch.float32), 16 if reference_points.shape[-1] == 4 else 8)
+    shapes = spatial_shapes.to(device=q.device, dtype=torch.int64).contiguous()
+    lsi = level_start_index.to(device=q.device, dtype=torch.int64).contiguous()
+    mask = None if padding_mask is None else padding_mask.to(torch.uint8).contiguous()
+    return q, ref, x, shapes, lsi, mask
+
+
+class MSDeformAttnLayerFunction(Function):
+    """The whole layer as one autograd node over (query, input_flatten, the eight parameters): vllm_msda_layer_forward_train, whose
+    output has the bits of the inference call, and vllm_msda_layer_backward.  ``meta`` = (n_heads, n_levels, n_points,
+    use_4d_normalizer); reference_points [B, Lq, L, 2|4] (already expanded), spatial_shapes, level_start_index and padding_mask get no
+    gradient.  Inputs, parameters and the kept activations go through save_for_backward, so an in-place change between forward and
+    backward fails autograd's version check instead of producing wrong gradients."""
+
+    @staticmethod
+    def forward(ctx, meta, query, reference_points, input_flatten, spatial_shapes, level_start_index, padding_mask, *params):
+        B, Lq, C = query.shape
+        S = input_flatten.shape[1]
+        L = _lib.lib()
+        _lib.check_struct_layouts()
+        keep = []
+        desc = _train_desc(meta, reference_points.shape[-1], C, params, keep)
+        desc.geometry = known_geometry(spatial_shapes, Lq)
+        q, ref, x, shapes, lsi, mask = _train_operands(query, reference_points, input_flatten, spatial_shapes, level_start_index,
+                                                       padding_mask)
+        dev = q.device
+        nsaved = L.vllm_msda_layer_saved_bytes(ctypes.byref(desc), B, Lq, S)
+        _lib.check(0 if nsaved >= 0 else -1, "vllm_msda_layer_saved_bytes")
+        saved = torch.empty(nsaved, dtype=torch.uint8, device=dev)
+        out = torch.empty((B, Lq, C), dtype=torch.bfloat16, device=dev)
+        v16 = ctypes.c_int(0)
+        with torch.cuda.device(dev):
+            ws, wsb = _lib.sized_workspace(dev, L.vllm_msda_layer_forward_train_workspace_bytes(ctypes.byref(desc), B, Lq, S),
+                                           "vllm_msda_layer_forward_train_workspace_bytes")
+            _lib.check(L.vllm_msda_layer_forward_train(ctypes.byref(desc), _lib.ptr(q), _lib.ptr(ref), _lib.ptr(x), _lib.ptr(mask),
+                                                       _lib.ptr(shapes), _lib.ptr(lsi), B, Lq, S, _lib.ptr(out), _lib.ptr(saved), nsaved,
+                                                       ctypes.byref(v16), _lib.ptr(ws), wsb, _lib.current_stream(dev)),
+                       "vllm_msda_layer_forward_train")
+        ctx.meta, ctx.value_is_bf16, ctx.has_mask = meta, v16.value, padding_mask is not None
+        ctx.save_for_backward(query, reference_points, input_flatten, spatial_shapes, level_start_index, saved,
+                              *(() if padding_mask is None else (padding_mask,)), *params)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        t = ctx.saved_tensors
+        query, reference_points, input_flatten, spatial_shapes, level_start_index, saved = t[:6]
+        padding_mask = t[6] if ctx.has_mask else None
+        params = t[7:] if ctx.has_mask else t[6:]
+        B, Lq, C = query.shape
+        S = input_flatten.shape[1]
+        L = _lib.lib()
+        keep = []
+        desc = _train_desc(ctx.meta, reference_points.shape[-1], C, params, keep)
+        q, ref, x, shapes, lsi, mask = _train_operands(query, reference_points, input_flatten, spatial_shapes, level_start_index,
+                                                       padding_mask)
+        dev = q.device
+        need_q, need_x = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
+        need = list(ctx.needs_input_grad[7:])
+        alloc = list(need)
+        for i in range(0, 8, 2):   # a bias gradient rides on its weight's launch
+            alloc[i] = need[i] or need[i + 1]
+        bf = dict(dtype=torch.bfloat16, device=dev)
+        grads = [torch.empty(p.shape, **bf) if a else None for p, a in zip(params, alloc)]
+        gq = torch.empty((B, Lq, C), **bf) if need_q else None
+        gx = torch.empty((B, S, C), **bf) if need_x else None
+        gs = _lib.VllmMsdaLayerGrads()
+        for i, name in enumerate(_LAYER_LINEARS):
+            setattr(gs, name + "_w", None if grads[2 * i] is None else grads[2 * i].data_ptr())
+            setattr(gs, name + "_b", None if grads[2 * i + 1] is None else grads[2 * i + 1].data_ptr())
+        g = _lib.aligned(grad_out.to(torch.bfloat16))
+        with torch.cuda.device(dev):
+            ws, wsb = _lib.sized_workspace(dev, L.vllm_msda_layer_backward_workspace_bytes(ctypes.byref(desc), B, Lq, S),
+                                           "vllm_msda_layer_backward_workspace_bytes")
+            _lib.check(L.vllm_msda_layer_backward(ctypes.byref(desc), _lib.ptr(q), _lib.ptr(ref), _lib.ptr(x), _lib.ptr(mask),
+                                                  _lib.ptr(shapes), _lib.ptr(lsi), B, Lq, S, _lib.ptr(saved), saved.numel(),
+                                                  ctx.value_is_bf16, _lib.ptr(g), _lib.ptr(gq), _lib.ptr(gx), ctypes.byref(gs),
+                                                  _lib.ptr(ws), wsb, _lib.current_stream(dev)), "vllm_msda_layer_backward")
+        # (a weight gradient computed only for its bias is dropped)
+        return (None, gq, None, gx, None, None, None) + tuple(gr if n else None for gr, n in zip(grads, need))
+
+
+def msda_layer_train(query, reference_points, input_flatten, spatial_shapes, level_start_index, padding_mask, value_proj,
+                     sampling_offsets, attention_weights, output_proj, n_heads, n_levels, n_points, use_4d_normalizer=False):
+    """msda_layer_forward with a native backward (MSDeformAttnLayerFunction): same arguments, same output bits."""
+    B, Lq, C = query.shape
+    S = input_flatten.shape[1]
+    if reference_points.shape[-1] not in (2, 4):
+        raise ValueError("Last dim of reference_points must be 2 or 4, but get {} instead.".format(
+            reference_points.shape[-1]))
+    if reference_points.dim() != 4 or reference_points.shape[0] not in (1, B) or reference_points.shape[1] not in (1, Lq) or \
+            reference_points.shape[2] not in (1, n_levels):
+        raise RuntimeError(f"msda_layer_train: reference_points {tuple(reference_points.shape)} does not broadcast to "
+                           f"({B}, {Lq}, {n_levels}, 2|4)")
+    reference_points = reference_points.expand(B, Lq, n_levels, reference_points.shape[-1])
+    if tuple(input_flatten.shape) != (B, S, C):
+        raise RuntimeError(f"msda_layer_train: input_flatten {tuple(input_flatten.shape)} vs query {tuple(query.shape)}")
+    if tuple(spatial_shapes.shape) != (n_levels, 2) or level_start_index.numel() != n_levels:
+        raise RuntimeError(f"msda_layer_train: spatial_shapes {tuple(spatial_shapes.shape)} / level_start_index "
+                           f"({level_start_index.numel()}) do not describe {n_levels} levels")
+    if padding_mask is not None and tuple(padding_mask.shape) != (B, S):
+        raise RuntimeError(f"msda_layer_train: padding mask {tuple(padding_mask.shape)} must be ({B}, {S})")
+    linears = (value_proj, sampling_offsets, attention_weights, output_proj)
+    if not msda_layer_train_ok(query, input_flatten, *linears, reference_points=reference_points):
+        raise RuntimeError("msda_layer_train: bf16 CUDA tensors, d_model % 64 == 0, bf16 weights and biases, and reference_points "
+                           "that do not require grad (there is no fallback: use the composed path for anything else)")
+    params = [p for lin in linears for p in (lin.weight, lin.bias)]
+    return MSDeformAttnLayerFunction.apply((n_heads, n_levels, n_points, bool(use_4d_normalizer)), query, reference_points,
+                                           input_flatten, spatial_shapes, level_start_index, padding_mask, *params)
+
+
 def _msda_apply_fp32(value, spatial_shapes, level_start_index, sampling_locations, attention_weights, im2col_step):
     """The reference upcasts to fp32 around the op (ms_deform_attn.py:131-139; ...mask_dn.py:764-766)."""
     dtype = value.dtype
@@ -432,6 +586,7 @@ class MSDeformAttn(nn.Module):
         self.value_proj = nn.Linear(d_model, d_model)
         self.output_proj = nn.Linear(d_model, d_model)
         self.use_4D_normalizer = use_4D_normalizer
+        self.native_training = False   # True: under grad, bf16 modules run the native training node (msda_layer_train) instead of the composition below
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -442,6 +597,8 @@ class MSDeformAttn(nn.Module):
         N, Len_q, _ = query.shape
         N, Len_in, _ = input_flatten.shape
         fused = None
+        linears = (self.value_proj, self.sampling_offsets, self.attention_weights, self.output_proj)
+        native = self.native_training and _native_training_wanted(query, input_flatten, linears, reference_points)
         if msda_layer_fused_ok(query, input_flatten, self.value_proj, self.sampling_offsets, self.attention_weights,
                                self.output_proj, reference_points=reference_points):   # bf16 inference: one native call
             fused = msda_layer_prepare(query, reference_points, input_flatten, input_spatial_shapes,
@@ -451,6 +608,9 @@ class MSDeformAttn(nn.Module):
         assert level_pixels(input_spatial_shapes) == Len_in
         if fused is not None:
             return fused()
+        if native:
+            return msda_layer_train(query, reference_points, input_flatten, input_spatial_shapes, input_level_start_index,
+                                    input_padding_mask, *linears, self.n_heads, self.n_levels, self.n_points, self.use_4D_normalizer)
         value = self.value_proj(input_flatten)
         if input_padding_mask is not None:
             value = value.masked_fill(input_padding_mask[..., None], float(0))
@@ -502,6 +662,7 @@ class MultiScaleDeformableAttention(nn.Module):
         self.attention_weights = nn.Linear(embed_dims, num_heads * num_levels * num_points)
         self.value_proj = nn.Linear(embed_dims, embed_dims)
         self.output_proj = nn.Linear(embed_dims, embed_dims)
+        self.native_training = False   # as MSDeformAttn.native_training; dropout and the identity stay in torch, around the node
         self.init_weights()
 
     def init_weights(self):
@@ -522,6 +683,8 @@ class MultiScaleDeformableAttention(nn.Module):
         bs, num_query, _ = query.shape
         bs, num_value, _ = value.shape
         fused = None
+        linears = (self.value_proj, self.sampling_offsets, self.attention_weights, self.output_proj)
+        native = self.native_training and _native_training_wanted(query, value, linears, reference_points)
         if msda_layer_fused_ok(query, value, self.value_proj, self.sampling_offsets, self.attention_weights,
                                self.output_proj, reference_points=reference_points):
             fused = msda_layer_prepare(query, reference_points, value, spatial_shapes, level_start_index,
@@ -529,8 +692,10 @@ class MultiScaleDeformableAttention(nn.Module):
                                        self.attention_weights, self.output_proj, self.num_heads, self.num_levels,
                                        self.num_points)
         assert level_pixels(spatial_shapes) == num_value
-        if fused is not None:
-            output = fused()
+        if fused is not None or native:
+            output = fused() if fused is not None else msda_layer_train(
+                query, reference_points, value, spatial_shapes, level_start_index, key_padding_mask, *linears, self.num_heads,
+                self.num_levels, self.num_points)
             if not self.batch_first:
                 output = output.permute(1, 0, 2)
             return self.dropout(output) + identity
@@ -591,6 +756,7 @@ class GroundingDinoMultiscaleDeformableAttention(nn.Module):
         self.value_proj = nn.Linear(config.d_model, config.d_model)
         self.output_proj = nn.Linear(config.d_model, config.d_model)
         self.disable_custom_kernels = getattr(config, "disable_custom_kernels", False)
+        self.native_training = False   # as MSDeformAttn.native_training (calls with output_attentions keep the composed path)
         self._reset_parameters()
 
     def _reset_parameters(self):
@@ -607,6 +773,9 @@ class GroundingDinoMultiscaleDeformableAttention(nn.Module):
         batch_size, num_queries, _ = hidden_states.shape
         batch_size, sequence_length, _ = encoder_hidden_states.shape
         fused = None
+        linears = (self.value_proj, self.sampling_offsets, self.attention_weights, self.output_proj)
+        native = self.native_training and not output_attentions and _native_training_wanted(
+            hidden_states, encoder_hidden_states, linears, reference_points)
         if not output_attentions and msda_layer_fused_ok(hidden_states, encoder_hidden_states, self.value_proj,
                                                          self.sampling_offsets, self.attention_weights,
                                                          self.output_proj, reference_points=reference_points):
@@ -620,6 +789,10 @@ class GroundingDinoMultiscaleDeformableAttention(nn.Module):
                 "Make sure to align the spatial shapes with the sequence length of the encoder hidden states")
         if fused is not None:
             return fused(), None
+        if native:
+            return msda_layer_train(hidden_states, reference_points, encoder_hidden_states, spatial_shapes, level_start_index,
+                                    None if attention_mask is None else ~attention_mask, *linears, self.n_heads, self.n_levels,
+                                    self.n_points), None
         value = self.value_proj(encoder_hidden_states)
         if attention_mask is not None:
             value = value.masked_fill(~attention_mask[..., None], float(0))
