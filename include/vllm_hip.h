@@ -877,6 +877,85 @@ int vllm_vit_embed_backward(const VllmVitEmbed *desc, const void *pixels, int n_
                             uint16_t *grad_patch_w, uint16_t *grad_patch_b, uint16_t *grad_cls, uint16_t *grad_pos, void *workspace,
                             long workspace_bytes, vllm_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Region encoder, native route (visionllmv2/model/region_encoder.py:68-147 with mask_pool_type = 'grid_sample', the configuration
+ * modeling_visionllmv2.py:247-252 builds; trained by default, freeze_region_encoder=False).  One call forward, one backward, bf16,
+ * channels-last throughout.  These structs and calls are additions: no existing struct is touched, vllm_abi_version is unchanged.
+ *   forward:  im2col of images + masks (4 channels, kernel = stride = patch / 2) -> GEMM -> LayerNorm + GELU -> GEMM (the 2 x 2 / stride 2
+ *     conv: its im2col is a reshape of the first conv's output, whose rows are ordered (n, y2, x2, dy, dx)) -> LayerNorm + GELU -> GEMM (the
+ *     1 x 1 conv) = stem [n, h w, embed];  pooling weights w_k[n, pix] = (1 / L) sum_{l >= k} A_l[n, pix] / cnt_l from the sampling points
+ *     of every level (A_l: the corner-weight sums of vllm_point_sample_mean_f32, bit for bit; a level whose region has no valid point adds
+ *     0);  pooled[n, c] = sum_pix (w_0 stem + sum_k w_k level_k)[n, pix, c] in fp32, rounded once;  out = pooled up_w^T + up_b.
+ *     The reference accumulates feat = feat + level and pools every prefix sum: level k is part of every pooled map l >= k, hence the
+ *     suffix sum; its mean over the levels is inside the weights because up_dim is affine.  feat is never materialised.
+ *   backward: grad_out [n, out_dim] -> the parameter gradients and grad_level_k = bf16(w_k (x) (grad_out up_w)) named in `grads` (NULL =
+ *     not needed: that product is skipped and everything only it needed; a bias gradient comes out of its weight gradient's launch and
+ *     needs the weight's pointer too).  The weights are recomputed from the points.  No gradient for images, masks or points.
+ *     Every gradient is accumulated in fp32, rounded once, overwritten (the caller accumulates); no atomics on any output: run-to-run
+ *     identical.
+ * hidden / 4, hidden, embed, out_dim multiples of 64 (hidden <= 2048); patch even; H, W multiples of patch; h w = (H / patch)(W / patch)
+ * <= 4096; 1 .. 4 levels, each [n, h w, embed] bf16 with its own row and image strides (elements, multiples of 8; 16-byte aligned);
+ * points [levels, n, P, 2] fp32 (x, y) in [0, 1]^2 and valid [levels, n, P] uint8, as vllm_point_sample_mean_f32 takes them per level.
+ * images [n, 3, H, W] and masks [n, 1, H, W] contiguous, bf16 or fp32 (pixel_is_f32), rounded to bf16 on the way in.
+ * conv1_w [hidden/4, 4, k, k] (k = patch / 2), conv2_w [hidden, hidden/4, 2, 2], conv3_w [embed, hidden], up_w [out_dim, embed], as the
+ * modules store them; the padded / permuted copies the GEMMs read are rebuilt in the workspace on every call. */
+typedef struct VllmRegionEncoder {
+    int hidden, embed, out_dim, patch;
+    int n, H, W;                 /* regions; pixels per side */
+    int levels, points;          /* L; P */
+    int pixel_is_f32;            /* 0 bf16, 1 fp32 */
+    float eps;                   /* LayerNorm2d: 1e-6 */
+    int reserved0;
+    const uint16_t *conv1_w, *conv1_b, *ln1_w, *ln1_b, *conv2_w, *conv2_b, *ln2_w, *ln2_b, *conv3_w, *conv3_b, *up_w, *up_b;
+    const uint16_t *level[4];
+    long level_row_stride[4], level_image_stride[4];
+} VllmRegionEncoder;
+/* What the forward keeps for the backward (caller buffers, all written by the forward; M1 = n (2H/patch)(2W/patch), M2 = M1 / 4 rows):
+ *   a1 [M1, Kpad] the im2col matrix (Kpad = patch^2 rounded up to 64);  y1 / pre1 / g1 [M1, hidden/4] the first conv's output, its
+ *   LayerNorm and the GELU of that;  y2 / pre2 / g2 [M2, hidden];  stem [M2, embed];  pooled [n, embed].  All bf16. */
+typedef struct VllmRegionEncoderSaved {
+    uint16_t *a1, *y1, *pre1, *g1, *y2, *pre2, *g2, *stem, *pooled;
+} VllmRegionEncoderSaved;
+typedef struct VllmRegionEncoderGrads {
+    uint16_t *conv1_w, *conv1_b, *ln1_w, *ln1_b, *conv2_w, *conv2_b, *ln2_w, *ln2_b, *conv3_w, *conv3_b, *up_w, *up_b;
+    uint16_t *level[4];          /* [n, h w, embed] contiguous */
+} VllmRegionEncoderGrads;
+int vllm_region_encoder_sizeof(void);
+int vllm_region_encoder_saved_sizeof(void);
+int vllm_region_encoder_grads_sizeof(void);
+/* workspace: vllm_region_encoder_workspace_bytes(desc) bytes serve both calls (< 0 for a refused descriptor; host-only arithmetic; the
+ * pointers of the descriptor are not read).  Its content is ignored and nothing is written beyond it; a short, misaligned or missing
+ * workspace is refused before any launch.  Nothing is allocated, nothing synchronised; one stream.  n == 0: the forward does nothing,
+ * the backward zero-fills the parameter gradients.  A refused call (VLLM_EINVAL, message in vllm_last_error) writes nothing. */
+/* Alignment: the workspace, the parameters, the levels, every saved tensor, out, grad_out and every gradient 16 bytes; points 8 bytes;
+ * images and masks element alignment. */
+long vllm_region_encoder_workspace_bytes(const VllmRegionEncoder *desc);
+int vllm_region_encoder_forward(const VllmRegionEncoder *desc, const void *images, const void *masks, const float *points,
+                                const uint8_t *valid, uint16_t *out, const VllmRegionEncoderSaved *saved, void *workspace,
+                                long workspace_bytes, vllm_stream_t stream);
+int vllm_region_encoder_backward(const VllmRegionEncoder *desc, const float *points, const uint8_t *valid, const uint16_t *grad_out,
+                                 const VllmRegionEncoderSaved *saved, const VllmRegionEncoderGrads *grads, void *workspace,
+                                 long workspace_bytes, vllm_stream_t stream);
+long vllm_region_encoder_calls(void);           /* forward + backward calls of this process that reached their launches (tests) */
+long vllm_region_encoder_wgrad_launches(void);  /* weight-gradient GEMMs the backward calls of this process launched (tests) */
+/* Its building blocks (tests, tools).
+ * layernorm_gelu: pre = bf16(LayerNorm(x)), y = bf16(gelu_erf(pre)) -- the GELU of the ROUNDED value, which is what torch's bf16 modules
+ *   compute and what the backward's gelu'(saved pre) differentiates; fp32 statistics.  x [rows, C] with row stride ldx, pre_out (NULL =
+ *   not kept; y has the same bits either way) and y [rows, C] dense.  C a multiple of 64: 64 .. 512, or up to 4096 where C / 8 splits
+ *   over 8 .. 64 lanes with at most 8 chunks each.  x, weight, bias, pre_out, y 16-byte aligned, ldx a multiple of 8.
+ * region_im2col: A [n (2H/patch)(2W/patch), Kpad], rows (n, y2, x2, dy, dx), columns (c, ky, kx) with c = 3 the mask, pad columns zero.
+ * region_pool_weights: weights [levels, n, h w] fp32.  region_pool: `levels` = n_levels device pointers in a HOST array, strides in
+ *   elements.  region_outer: grad_map [n, hw, C] = bf16(weights[n, pix] g[n, c]). */
+int vllm_layernorm_gelu_bf16(const uint16_t *x, int ldx, const uint16_t *weight, const uint16_t *bias, uint16_t *pre_out, uint16_t *y,
+                             long rows, int C, float eps, vllm_stream_t stream);
+int vllm_region_im2col_bf16(const void *images, const void *masks, int pixel_is_f32, uint16_t *A, int n, int H, int W, int patch, int Kpad,
+                            vllm_stream_t stream);
+int vllm_region_pool_weights_f32(const float *points, const uint8_t *valid, float *weights, int n, int levels, int h, int w, int P,
+                                 vllm_stream_t stream);
+int vllm_region_pool_bf16(const float *weights, const uint16_t *stem, const uint16_t *const *levels, const long *level_row_stride,
+                          const long *level_image_stride, int n, int n_levels, int hw, int C, uint16_t *pooled, vllm_stream_t stream);
+int vllm_region_outer_bf16(const float *weights, const uint16_t *g, uint16_t *grad_map, int n, int hw, int C, vllm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,8 +195,28 @@ class VllmVitEmbed(ctypes.Structure):
                [(n, _P) for n in ("patch_w", "patch_b", "cls", "pos")]
 
 
+REGION_PARAMS = ("conv1_w", "conv1_b", "ln1_w", "ln1_b", "conv2_w", "conv2_b", "ln2_w", "ln2_b", "conv3_w", "conv3_b", "up_w", "up_b")
+
+
+class VllmRegionEncoder(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in ("hidden", "embed", "out_dim", "patch", "n", "H", "W", "levels", "points", "pixel_is_f32")] + \
+               [("eps", ctypes.c_float), ("reserved0", ctypes.c_int)] + [(n, _P) for n in REGION_PARAMS] + \
+               [("level", _P * 4), ("level_row_stride", ctypes.c_long * 4), ("level_image_stride", ctypes.c_long * 4)]
+
+
+class VllmRegionEncoderSaved(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ("a1", "y1", "pre1", "g1", "y2", "pre2", "g2", "stem", "pooled")]
+
+
+class VllmRegionEncoderGrads(ctypes.Structure):
+    _fields_ = [(n, _P) for n in REGION_PARAMS] + [("level", _P * 4)]
+
+
 def check_struct_layouts():
     L = lib()
+    assert ctypes.sizeof(VllmRegionEncoder) == L.vllm_region_encoder_sizeof(), "VllmRegionEncoder layout mismatch"
+    assert ctypes.sizeof(VllmRegionEncoderSaved) == L.vllm_region_encoder_saved_sizeof(), "VllmRegionEncoderSaved layout mismatch"
+    assert ctypes.sizeof(VllmRegionEncoderGrads) == L.vllm_region_encoder_grads_sizeof(), "VllmRegionEncoderGrads layout mismatch"
     assert ctypes.sizeof(VllmMsdaLayerDesc) == L.vllm_msda_layer_desc_sizeof(), "VllmMsdaLayerDesc layout mismatch"
     assert ctypes.sizeof(VllmMsdaLayerGrads) == L.vllm_msda_layer_grads_sizeof(), "VllmMsdaLayerGrads layout mismatch"
     assert ctypes.sizeof(VllmVitDesc) == L.vllm_vit_desc_sizeof(), "VllmVitDesc layout mismatch"

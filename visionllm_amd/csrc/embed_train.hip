@@ -201,6 +201,23 @@ Ws ws_layout(const Dims &q, int n)
 }
 
 }  // namespace
+
+// A Conv2d weight [C, K] as the module stores it <-> the K-padded copy [C, kpad] a GEMM reads (also the region encoder's first conv)
+int pad_weight_launch(const uint16_t *w, uint16_t *wp, int C, int K, int kpad, hipStream_t st)
+{
+    if (K % 2 == 0) VLLM_LAUNCH((embed_pad_weight_kernel<2>), dim3(grid_for((long)C * kpad / 2)), dim3(256), 0, st, w, wp, C, K, kpad);
+    else VLLM_LAUNCH((embed_pad_weight_kernel<1>), dim3(grid_for((long)C * kpad)), dim3(256), 0, st, w, wp, C, K, kpad);
+    VLLM_CHECK_LAUNCH("embed_pad_weight_kernel");
+    return VLLM_OK;
+}
+int unpad_weight_launch(const uint16_t *wp, uint16_t *w, int C, int K, int kpad, hipStream_t st)
+{
+    if (K % 2 == 0) VLLM_LAUNCH((embed_unpad_weight_kernel<2>), dim3(grid_for((long)C * K / 2)), dim3(256), 0, st, wp, w, C, K, kpad);
+    else VLLM_LAUNCH((embed_unpad_weight_kernel<1>), dim3(grid_for((long)C * K)), dim3(256), 0, st, wp, w, C, K, kpad);
+    VLLM_CHECK_LAUNCH("embed_unpad_weight_kernel");
+    return VLLM_OK;
+}
+
 }  // namespace vllm
 
 using namespace vllm;
@@ -231,9 +248,7 @@ extern "C" int vllm_vit_embed_forward(const VllmVitEmbed *d, const void *pixels,
     uint16_t *wp = (uint16_t *)(ws + w.wp), *col = (uint16_t *)(ws + w.col);
     const int C = q.C;
     TRY(sk_scratch_reset(sk, st, "vit_embed_forward"));
-    if (q.K % 2 == 0) VLLM_LAUNCH((embed_pad_weight_kernel<2>), dim3(grid_for((long)C * q.kpad / 2)), dim3(256), 0, st, d->patch_w, wp, C, q.K, q.kpad);
-    else VLLM_LAUNCH((embed_pad_weight_kernel<1>), dim3(grid_for((long)C * q.kpad)), dim3(256), 0, st, d->patch_w, wp, C, q.K, q.kpad);
-    VLLM_CHECK_LAUNCH("embed_pad_weight_kernel");
+    TRY(pad_weight_launch(d->patch_w, wp, C, q.K, q.kpad, st));
     // the statements of vllm_vit_forward's embedding step
     TRY(im2col_launch(pixels, d->pixel_is_f32, col, n, q.img, q.ps, q.kpad, st));
     TRY(gemm(st, EPI_EMBED, col, q.kpad, wp, q.kpad, d->patch_b, out, C, n * q.P, C, q.kpad, nullptr, d->pos, C, q.P, 0, sk, SK_SCRATCH_BYTES));
@@ -283,8 +298,5 @@ extern "C" int vllm_vit_embed_backward(const VllmVitEmbed *d, const void *pixels
         VLLM_LAUNCH((embed_im2col_cls_kernel<uint16_t>), dim3(grid_for(nitem)), dim3(256), 0, st, (const uint16_t *)pixels, col, n, q.img, q.ps, q.g, q.kpad);
     VLLM_CHECK_LAUNCH("embed_im2col_cls_kernel");
     TRY(gemm_wgrad_launch(grad_out, C, col, q.kpad, (int)((long)n * S), C, q.kpad, dw, q.kpad, nullptr, ws + w.wg, w.wg_bytes, st));
-    if (q.K % 2 == 0) VLLM_LAUNCH((embed_unpad_weight_kernel<2>), dim3(grid_for((long)C * q.K / 2)), dim3(256), 0, st, dw, grad_patch_w, C, q.K, q.kpad);
-    else VLLM_LAUNCH((embed_unpad_weight_kernel<1>), dim3(grid_for((long)C * q.K)), dim3(256), 0, st, dw, grad_patch_w, C, q.K, q.kpad);
-    VLLM_CHECK_LAUNCH("embed_unpad_weight_kernel");
-    return VLLM_OK;
+    return unpad_weight_launch(dw, grad_patch_w, C, q.K, q.kpad, st);
 }

@@ -226,6 +226,9 @@ int attn_fwd_launch(AttnArgs a, int D, hipStream_t st);
 int attn_bwd_launch(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *grad_out, int B, int S, int H, int D,
                     float softmax_scale, uint16_t *grad_qkv, void *workspace, long workspace_bytes, bool f16, hipStream_t st);
 
+// embed_train.hip: a Conv2d weight [C, K] as the module stores it <-> its K-padded copy [C, kpad] (16-byte aligned kpad rows; [C, K] 4-byte)
+int pad_weight_launch(const uint16_t *w, uint16_t *wp, int C, int K, int kpad, hipStream_t st);
+int unpad_weight_launch(const uint16_t *wp, uint16_t *w, int C, int K, int kpad, hipStream_t st);
 int im2col_launch(const void *pixels, int pixel_is_f32, uint16_t *A, int N, int img, int ps, int Kpad, hipStream_t st);
 int cls_rows_launch(const uint16_t *cls, const uint16_t *pos, uint16_t *hidden, int N, int S, int C, hipStream_t st);
 int pixel_shuffle_launch(const uint16_t *in, long in_tile_stride, int ldin, int tok0, uint16_t *out, int N, int hw,

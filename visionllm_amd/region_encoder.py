@@ -8,7 +8,12 @@ Under autograd (the feature map requires grad: the reference trains the region e
 ``torch.autograd.Function``s whose backward is native too (vllm_point_sample_mean_backward_f32 / _bf16: an outer product of
 the region's pixel weights and grad_out, include/vllm_hip.h section f4); gradients with respect to the sampling positions
 are not implemented.
+``RegionEncoder.native_branch = True`` replaces all of that -- the stem, the per-level add and pooling, up_dim, and torch's
+autograd of them -- by ONE native call forward (vllm_region_encoder_forward) and one backward (vllm_region_encoder_backward),
+channels-last, bf16, for the configuration the model builds ('grid_sample'); ``rand_sample`` and the point bookkeeping stay here.
 """
+import ctypes
+
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -183,11 +188,95 @@ def _mask_stem(hidden_dim, embed_dim, kernel_size):
     )
 
 
+_NATIVE_PARAMS = ("mask_embedding.0.weight", "mask_embedding.0.bias", "mask_embedding.1.weight", "mask_embedding.1.bias",
+                  "mask_embedding.3.weight", "mask_embedding.3.bias", "mask_embedding.4.weight", "mask_embedding.4.bias",
+                  "mask_embedding.6.weight", "mask_embedding.6.bias", "up_dim.weight", "up_dim.bias")   # (_lib.REGION_PARAMS' order)
+_NATIVE_SAVED = ("a1", "y1", "pre1", "g1", "y2", "pre2", "g2", "stem", "pooled")
+_MAX_LEVELS = 4
+
+
+def _native_desc(geo, params, levels):
+    hidden, embed, out_dim, patch, n, H, W, P, is_f32, eps = geo
+    d = _lib.VllmRegionEncoder(hidden=hidden, embed=embed, out_dim=out_dim, patch=patch, n=n, H=H, W=W, levels=len(levels), points=P,
+                               pixel_is_f32=is_f32, eps=eps, **{k: p.data_ptr() for k, p in zip(_lib.REGION_PARAMS, params)})
+    for i, lv in enumerate(levels):
+        d.level[i], d.level_row_stride[i], d.level_image_stride[i] = lv.data_ptr(), lv.stride(1), lv.stride(0)
+    return d
+
+
+def _native_saved(geo, device):
+    hidden, embed, _, patch, n, H, W = geo[:7]
+    m2 = n * (H // patch) * (W // patch)
+    kpad = (patch * patch + 63) // 64 * 64
+    cols = (kpad, hidden // 4, hidden // 4, hidden // 4, hidden, hidden, hidden, embed)
+    saved = [torch.empty((4 * m2 if i < 4 else m2, c), dtype=torch.bfloat16, device=device) for i, c in enumerate(cols)]
+    return saved + [torch.empty((n, embed), dtype=torch.bfloat16, device=device)]
+
+
+def _native_forward(geo, images, masks, coords, valid, params, levels):
+    """One call of vllm_region_encoder_forward -> (out [n, out_dim] bf16, the tensors it keeps for the backward)."""
+    dev = images.device
+    L = _lib.lib()
+    d = _native_desc(geo, params, levels)
+    saved = _native_saved(geo, dev)
+    sv = _lib.VllmRegionEncoderSaved(**{k: t.data_ptr() for k, t in zip(_NATIVE_SAVED, saved)})
+    out = torch.empty((geo[4], geo[2]), dtype=torch.bfloat16, device=dev)
+    with torch.cuda.device(dev):
+        ws, nbytes = _lib.sized_workspace(dev, L.vllm_region_encoder_workspace_bytes(ctypes.byref(d)), "vllm_region_encoder_workspace_bytes")
+        _lib.check(L.vllm_region_encoder_forward(ctypes.byref(d), _lib.ptr(images), _lib.ptr(masks), _lib.ptr(coords), _lib.ptr(valid), _lib.ptr(out),
+                                                 ctypes.byref(sv), _lib.ptr(ws), nbytes, _lib.current_stream(dev)), "vllm_region_encoder_forward")
+    return out, saved
+
+
+class _RegionEncoderFn(torch.autograd.Function):
+    """The native region encoder under autograd: vllm_region_encoder_forward / vllm_region_encoder_backward.  Differentiable in the twelve
+    parameters and in the levels; the levels themselves are not kept (the pooling is linear in them)."""
+
+    @staticmethod
+    def forward(ctx, geo, images, masks, coords, valid, *tensors):
+        params, levels = tensors[:12], tensors[12:]
+        out, saved = _native_forward(geo, images, masks, coords, valid, params, levels)
+        ctx.save_for_backward(coords, valid, *params, *saved)
+        ctx.geo, ctx.n_levels = geo, len(levels)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        coords, valid = ctx.saved_tensors[:2]
+        params, saved = ctx.saved_tensors[2:14], ctx.saved_tensors[14:]
+        geo, nl = ctx.geo, ctx.n_levels
+        hidden, embed, _, patch, n, H, W = geo[:7]
+        dev = grad_out.device
+        need = ctx.needs_input_grad[5:]
+        g = _lib.aligned(grad_out.to(torch.bfloat16))
+        # (a bias gradient comes out of its weight gradient's launch: a frozen weight beside a trained bias gets a buffer that is dropped)
+        want = [need[i] or (i % 2 == 0 and i not in (2, 6) and need[i + 1]) for i in range(12)]
+        grads = [torch.empty_like(p) if w else None for p, w in zip(params, want)]
+        glev = [torch.empty((n, (H // patch) * (W // patch), embed), dtype=torch.bfloat16, device=dev) if need[12 + i] else None for i in range(nl)]
+        gs = _lib.VllmRegionEncoderGrads(**{k: (t.data_ptr() if t is not None else None) for k, t in zip(_lib.REGION_PARAMS, grads)})
+        for i, t in enumerate(glev):
+            gs.level[i] = t.data_ptr() if t is not None else None
+        # (the backward reads no level: the descriptor names none)
+        d = _native_desc(geo, params, [])
+        d.levels = nl
+        sv = _lib.VllmRegionEncoderSaved(**{k: t.data_ptr() for k, t in zip(_NATIVE_SAVED, saved)})
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            ws, nbytes = _lib.sized_workspace(dev, L.vllm_region_encoder_workspace_bytes(ctypes.byref(d)), "vllm_region_encoder_workspace_bytes")
+            _lib.check(L.vllm_region_encoder_backward(ctypes.byref(d), _lib.ptr(coords), _lib.ptr(valid), _lib.ptr(g), ctypes.byref(sv), ctypes.byref(gs),
+                                                      _lib.ptr(ws), nbytes, _lib.current_stream(dev)), "vllm_region_encoder_backward")
+        grads = [t if nd else None for t, nd in zip(grads, need[:12])]
+        return (None, None, None, None, None, *grads, *glev)
+
+
 class RegionEncoder(nn.Module):
     """region_encoder.py:68-147 with the reference's parameter names (mask_embedding.*, region_query, region_attn.*,
-    up_dim.*)."""
+    up_dim.*).  ``native_branch = True`` (grid_sample pooling, bf16) runs the whole branch -- stem, level pooling, up_dim -- as ONE native
+    call forward and one backward instead of the torch modules below; the default keeps every statement of ``forward`` as it is."""
 
     POOL_TYPES = ("mean", "cross_attn", "grid_sample")
+    native_branch = False
 
     def __init__(self, hidden_dim, embed_dim, out_dim, patch_size=14, mask_pool_type="mean"):
         super().__init__()
@@ -217,16 +306,77 @@ class RegionEncoder(nn.Module):
         q = self.region_query.weight.unsqueeze(0).repeat(feat.shape[0], 1, 1)
         return kv, self.region_attn(q, kv, kv)[0].squeeze(1)
 
-    def _pool_points(self, feat, masks):
+    def _sample_points(self, masks):
+        """The index bookkeeping of one level (:127-134) -> (coords [regions, points, (x, y)], valid [regions, points])."""
         H, W = masks.shape[-2:]
         divisor = torch.tensor([1, H, W], device=masks.device)[None,]
         pts = nn.utils.rnn.pad_sequence([rand_sample(m, divisor, self.num_points) for m in masks], padding_value=-1)
         pts = pts.permute(1, 0, 2)                        # [regions, points, (id, y, x)], -1 padded
         valid = pts.sum(dim=-1) >= 0
-        return point_sample_masked_mean(feat, pts[:, :, -2:].flip(dims=[-1]), valid)   # native: sample + masked mean
+        return pts[:, :, -2:].flip(dims=[-1]), valid
+
+    def _pool_points(self, feat, masks):
+        return point_sample_masked_mean(feat, *self._sample_points(masks))   # native: sample + masked mean
+
+    def _native_refuse(self, images, masks, image_features):
+        """The limits of the native route, each named before any launch."""
+        who = "RegionEncoder (native_branch)"
+        if self.mask_pool_type != "grid_sample":
+            raise NotImplementedError(f"{who}: mask_pool_type '{self.mask_pool_type}': only 'grid_sample' has a native route")
+        params = [self.get_parameter(k) for k in _NATIVE_PARAMS]
+        hidden, embed, out_dim = params[4].shape[0], params[8].shape[0], params[10].shape[0]
+        if hidden % 4 or (hidden // 4) % 64 or hidden % 64:
+            raise ValueError(f"{who}: hidden_dim {hidden}: hidden_dim // 4 and hidden_dim must be multiples of 64")
+        if embed % 64 or out_dim % 64:
+            raise ValueError(f"{who}: embed_dim {embed} and out_dim {out_dim} must be multiples of 64")
+        H, W = images.shape[-2:]
+        if H % self.patch_size or W % self.patch_size:
+            raise ValueError(f"{who}: H {H} and W {W} must be multiples of patch_size {self.patch_size}")
+        if not 1 <= len(image_features) <= _MAX_LEVELS:
+            raise ValueError(f"{who}: {len(image_features)} levels: at most {_MAX_LEVELS} levels (and at least one)")
+        if images.requires_grad or masks.requires_grad:
+            raise NotImplementedError(f"{who}: images / masks require grad, and the native backward produces no pixel gradients")
+        if any(p.dtype != torch.bfloat16 or not p.is_cuda for p in params):
+            raise RuntimeError(f"{who}: the parameters must be bf16 CUDA tensors (no CPU fallback, no other dtype)")
+        if not images.is_cuda or images.dtype not in (torch.bfloat16, torch.float32):
+            raise RuntimeError(f"{who}: images must be a bf16 or fp32 CUDA tensor")
+        return params, hidden, embed, out_dim
+
+    def _forward_native(self, images, masks, image_features):
+        image_features = list(image_features)
+        params, hidden, embed, out_dim = self._native_refuse(images, masks, image_features)
+        masks = masks.to(images.dtype)
+        n, (H, W) = len(images), images.shape[-2:]
+        hw = (H // self.patch_size) * (W // self.patch_size)
+        levels, drawn = [], []
+        for level in image_features:
+            if level.dim() == 4:
+                level = level.permute(0, 2, 3, 1).reshape(n, hw, -1)
+            if level.shape != (n, hw, embed):
+                raise ValueError(f"RegionEncoder (native_branch): a level of shape {tuple(level.shape)}, expected {(n, hw, embed)}")
+            level = level.to(torch.bfloat16)
+            # read in place, strided views included (hidden states [:, 1:]); copied only where 16-byte rows fail
+            if level.stride(2) != 1 or level.stride(1) % 8 or level.stride(0) % 8 or level.data_ptr() % 16:
+                level = _lib.aligned(level)
+            levels.append(level)
+            drawn.append(self._sample_points(masks))          # (once per level, in level order: the generator use of forward())
+        P = max(1, max(c.shape[1] for c, _ in drawn))
+        coords = torch.zeros((len(drawn), n, P, 2), dtype=torch.float32, device=images.device)
+        valid = torch.zeros((len(drawn), n, P), dtype=torch.uint8, device=images.device)
+        for l, (c, v) in enumerate(drawn):
+            coords[l, :c.shape[0], :c.shape[1]] = c
+            valid[l, :v.shape[0], :v.shape[1]] = v
+        geo = (hidden, embed, out_dim, self.patch_size, n, H, W, P, int(images.dtype == torch.float32), self.mask_embedding[1].eps)
+        params = [_lib.aligned(p) for p in params]
+        images, masks = images.contiguous(), masks.contiguous()
+        if torch.is_grad_enabled() and any(t.requires_grad for t in params + levels):
+            return _RegionEncoderFn.apply(geo, images, masks, coords, valid, *params, *levels)
+        return _native_forward(geo, images, masks, coords, valid, [p.detach() for p in params], [lv.detach() for lv in levels])[0]
 
     def forward(self, images, masks, image_features):
         assert images.shape[-2:] == masks.shape[-2:]
+        if self.native_branch:
+            return self._forward_native(images, masks, image_features)
         masks = masks.to(images.dtype)
         feat = self.mask_embedding(torch.cat([images, masks], dim=1))
         n, (h, w) = len(images), feat.shape[-2:]
