@@ -608,6 +608,38 @@ int vllm_splice_visual_tokens_backward_bf16(const int32_t *workspace, const uint
 int vllm_copy_rows_bf16(const uint16_t *src, const int64_t *src_idx, uint16_t *dst, const int64_t *dst_idx, long n,
                         int C, long src_rows, long dst_rows, vllm_stream_t stream);
 
+/* Backward of those four loops: two row kernels, driven by index arrays the forward built on the device.
+ *
+ * Segment sum: dst[d, :] = bf16( sum_{k = seg_ptr[d]}^{seg_ptr[d+1]-1} float(src[src_idx[k], :]) ) for d < dst_rows.
+ * Replaces the autograd of: the sequential `torch.cat([..., emb_embeddings_*, ...])` of modeling_visionllmv2.py:432-527 (gradient of the
+ * query tables: a table row sums grad_out over the positions it was written to), `hidden_states[b, selected]` of :775-787 (gradient of
+ * the LLM hidden states: segments of 0 or 1 term) and the per-region tile selection of :644-681 (gradient of the tower's last three
+ * levels: a tile row sums grad_out over the regions that read it).
+ *   src [src_rows, C] bf16, seg_ptr [dst_rows + 1] and src_idx [n_idx]: DEVICE int64, dst [dst_rows, C] bf16; C % 8 == 0.
+ *   Terms are added in fp32 in ascending k and rounded to bf16 once.  An empty segment gives a zero row; a segment of one term is a
+ *   bit-exact copy for every finite or infinite value (-0.0 included).  Every dst row is written by the call: no zero-fill by the
+ *   caller, no atomics, the same bits on every run.  src is never written.
+ *   Each segment is clamped to [0, n_idx] before it is walked; a pair with seg_ptr[d+1] < seg_ptr[d] is an empty segment; a term whose
+ *   src_idx[k] lies outside [0, src_rows) contributes nothing (the row mover's "skipped" rule): no content of the index arrays can make
+ *   the kernel read or write outside the four buffers.
+ *   Refused (VLLM_EINVAL, nothing written, decided before any launch): C <= 0 or C % 8 != 0; a negative size; src or dst off 16 bytes; a
+ *   NULL seg_ptr or dst with dst_rows > 0; a NULL src or src_idx with n_idx > 0.  dst_rows == 0 is accepted without a launch; n_idx == 0
+ *   with src == NULL is accepted and every row becomes zero. */
+/* Alignment: src and dst 16 bytes. */
+int vllm_rows_segment_sum_bf16(const uint16_t *src, long src_rows, const int64_t *seg_ptr, const int64_t *src_idx, long n_idx,
+                               uint16_t *dst, long dst_rows, int C, vllm_stream_t stream);
+
+/* Masked copy: dst[r, :] = zero_row[r] ? 0 : src[r, :] for r < rows.  Replaces the autograd of the index assignments
+ * `inputs_embeds[selected] = region_features` (modeling_visionllmv2.py:688-698) and of the rows the [EMB] splice replaces (:432-527):
+ * the gradient of inputs_embeds is grad_out with the overwritten rows set to zero.
+ *   src, dst [rows, C] bf16, C % 8 == 0; zero_row [rows]: DEVICE uint8.  A row whose flag is non-zero is stored as zeros and its src
+ *   row is NOT read (no read traffic), so non-finite values there do not propagate -- the same deliberate departure as
+ *   vllm_splice_visual_tokens_backward_bf16.  Kept rows are bit-exact copies.
+ *   Refused (VLLM_EINVAL, nothing written, decided before any launch): C <= 0 or C % 8 != 0; rows < 0; src or dst off 16 bytes; a NULL
+ *   pointer with rows > 0.  rows == 0 is accepted without a launch. */
+/* Alignment: src and dst 16 bytes. */
+int vllm_copy_rows_masked_bf16(const uint16_t *src, const uint8_t *zero_row, uint16_t *dst, long rows, int C, vllm_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------
  * B1. Vision encoder (the `vis_encoder` slot): one call runs patch-embed + all layers.
  *

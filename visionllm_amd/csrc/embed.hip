@@ -287,6 +287,73 @@ __global__ __launch_bounds__(256) void splice_backward_kernel(const int32_t *__r
     }
 }
 
+// ---- backward of the other four token loops: two row kernels driven by index arrays the forward built in torch ----------------------
+// Segment sum.  A wave owns (dst row d, slab of 64 x 8 channels): each lane keeps 8 fp32 sums of one 16-byte chunk, so a gradient of
+// 4 or 64 table rows x 4096 channels still spreads over C / 512 waves per row.  The segment bounds and the term indices are wave-uniform
+// loads; the load of term k + 1 is issued before term k is widened and added (segments are 0 to 8 terms long in practice).  The sums
+// start from -0.0, the identity of the fp32 add for EVERY value (+0.0 would turn a lone -0.0 term into +0.0), and a segment without a
+// valid term stores +0.0, so one term is a bit-exact copy and no term is a zero row.  A term whose row lies outside [0, src_rows) is
+// skipped, a segment is clamped to [0, n_idx] first: no content of seg_ptr / src_idx reaches outside the four buffers.
+__global__ __launch_bounds__(256) void rows_segment_sum_kernel(const uint16_t *__restrict__ src, long src_rows,
+                                                               const int64_t *__restrict__ seg_ptr, const int64_t *__restrict__ src_idx,
+                                                               long n_idx, uint16_t *__restrict__ dst, long dst_rows, int C)
+{
+    const int cch = C / 8, n_slabs = (cch + 63) / 64, lane = threadIdx.x & 63;
+    const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
+    const uint4_t z = {0u, 0u, 0u, 0u};
+    for (long it = wave; it < dst_rows * n_slabs; it += nwaves) {
+        const long d = it / n_slabs;
+        const int ck = (int)(it - d * n_slabs) * 64 + lane;
+        const bool act = ck < cch;
+        long lo = seg_ptr[d], hi = seg_ptr[d + 1];
+        lo = lo < 0 ? 0 : lo > n_idx ? n_idx : lo;
+        hi = hi < 0 ? 0 : hi > n_idx ? n_idx : hi;   // (hi < lo: the loop below does not run -- an empty segment)
+        float acc[8] = {-0.f, -0.f, -0.f, -0.f, -0.f, -0.f, -0.f, -0.f};
+        bool any = false, cur_ok = false;
+        uint4_t cur = z;
+        if (lo < hi) {
+            const long r = src_idx[lo];
+            cur_ok = r >= 0 && r < src_rows;
+            if (cur_ok && act) cur = *reinterpret_cast<const uint4_t *>(src + r * C + ck * 8);
+        }
+        for (long k = lo; k < hi; ++k) {
+            uint4_t nxt = z;
+            bool nxt_ok = false;
+            if (k + 1 < hi) {
+                const long r = src_idx[k + 1];
+                nxt_ok = r >= 0 && r < src_rows;
+                if (nxt_ok && act) nxt = *reinterpret_cast<const uint4_t *>(src + r * C + ck * 8);
+            }
+            if (cur_ok) {
+                any = true;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { acc[2 * e] += bf16lo_to_f32(cur[e]); acc[2 * e + 1] += bf16hi_to_f32(cur[e]); }
+            }
+            cur = nxt;
+            cur_ok = nxt_ok;
+        }
+        if (!act) continue;
+        uint4_t o = z;
+        if (any) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = pack_bf16x2(acc[2 * e], acc[2 * e + 1]);
+        }
+        *reinterpret_cast<uint4_t *>(dst + d * C + ck * 8) = o;
+    }
+}
+
+// dst[r, :] = flag[r] ? 0 : src[r, :]; a wave per row.  A flagged row's source is not read.
+__global__ __launch_bounds__(256) void copy_rows_masked_kernel(const uint16_t *__restrict__ src, const uint8_t *__restrict__ flag,
+                                                               uint16_t *__restrict__ dst, long rows, int C)
+{
+    const int cch = C / 8, lane = threadIdx.x & 63;
+    const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
+    for (long r = wave; r < rows; r += nwaves) {
+        if (flag[r]) zero_row(dst + r * C, cch, lane);
+        else move_row(src + r * C, dst + r * C, cch, lane);
+    }
+}
+
 static inline unsigned grid_for(long n)
 {
     long b = (n + 255) / 256;
@@ -420,6 +487,35 @@ extern "C" int vllm_copy_rows_bf16(const uint16_t *src, const int64_t *src_idx, 
     VLLM_LAUNCH(copy_rows_kernel, dim3(grid_for(n * 64)), dim3(256), 0, (hipStream_t)stream, src, src_idx, dst, dst_idx, n, C,
                 src_rows, dst_rows);
     VLLM_CHECK_LAUNCH("copy_rows_kernel");
+    return VLLM_OK;
+}
+
+extern "C" int vllm_rows_segment_sum_bf16(const uint16_t *src, long src_rows, const int64_t *seg_ptr, const int64_t *src_idx, long n_idx,
+                                          uint16_t *dst, long dst_rows, int C, vllm_stream_t stream)
+{
+    VLLM_REQUIRE(C > 0 && C % 8 == 0, "rows_segment_sum: C must be a positive multiple of 8");
+    VLLM_REQUIRE(src_rows >= 0 && n_idx >= 0 && dst_rows >= 0, "rows_segment_sum: src_rows, n_idx and dst_rows must not be negative");
+    VLLM_REQUIRE(aligned16(src) && aligned16(dst), "rows_segment_sum: src and dst must be 16-byte aligned");
+    if (dst_rows == 0) return VLLM_OK;
+    VLLM_REQUIRE(seg_ptr && dst, "rows_segment_sum: null seg_ptr or dst");
+    VLLM_REQUIRE(n_idx == 0 || (src && src_idx), "rows_segment_sum: null src or src_idx with n_idx > 0");
+    const long items = dst_rows * ((C / 8 + 63) / 64);
+    VLLM_LAUNCH(rows_segment_sum_kernel, dim3(grid_for(items * 64)), dim3(256), 0, (hipStream_t)stream, src, src_rows, seg_ptr, src_idx,
+                n_idx, dst, dst_rows, C);
+    VLLM_CHECK_LAUNCH("rows_segment_sum_kernel");
+    return VLLM_OK;
+}
+
+extern "C" int vllm_copy_rows_masked_bf16(const uint16_t *src, const uint8_t *zero_row, uint16_t *dst, long rows, int C,
+                                          vllm_stream_t stream)
+{
+    VLLM_REQUIRE(C > 0 && C % 8 == 0, "copy_rows_masked: C must be a positive multiple of 8");
+    VLLM_REQUIRE(rows >= 0, "copy_rows_masked: rows must not be negative");
+    VLLM_REQUIRE(aligned16(src) && aligned16(dst), "copy_rows_masked: src and dst must be 16-byte aligned");
+    if (rows == 0) return VLLM_OK;
+    VLLM_REQUIRE(src && zero_row && dst, "copy_rows_masked: null src, zero_row or dst");
+    VLLM_LAUNCH(copy_rows_masked_kernel, dim3(grid_for(rows * 64)), dim3(256), 0, (hipStream_t)stream, src, zero_row, dst, rows, C);
+    VLLM_CHECK_LAUNCH("copy_rows_masked_kernel");
     return VLLM_OK;
 }
 
