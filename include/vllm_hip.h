@@ -321,6 +321,60 @@ int vllm_dcnv3_backward_f16(const uint16_t *input, const uint16_t *offset, const
                             vllm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * f3b. The whole DCNv3 layer, bf16 modules (inference).
+ *
+ * Replaces the body of DCNv3.forward, visionllmv2/model/ops_dcnv3/modules/dcnv3.py:313-351, with the CenterFeatureScaleModule
+ * above it (:206-219), for the configuration the InternImage-H det backbone builds: LayerNorm + GELU behind the depth-wise conv,
+ * 3 x 3 sampling kernel, stride 1, pad == dilation (output H x W):
+ *     x_proj = input_proj(input);  x1 = GELU(LayerNorm(dw_conv(input)));  offset = offset(x1);  mask = softmax_9(mask(x1));
+ *     core = dcnv3(x_proj, offset, mask);  s = sigmoid(center_feature_scale_proj(x1));  out = output_proj(core (1 - s) + x_proj s)
+ * Five launches: GEMM, conv + LayerNorm + GELU, GEMM (fp32 rows of offsets, logits and centre logits), softmax + sampling + blend, GEMM.
+ * x_proj and x1 are bf16 (what the bf16 module holds); the conv result, the statistics, offsets, logits, softmax weights, the
+ * sampled sum and the blend are fp32; core is rounded to bf16 once, as output_proj's operand.
+ *
+ * proj_w / proj_b are ONE packed linear over x1, rows in this order: [0, 18 G) offset.weight, [18 G, 27 G) mask.weight,
+ * [27 G, 28 G) center_feature_scale_proj_weight (only with center_feature_scale), then zero rows up to n_proj; n_proj is a multiple
+ * of 8 and at least the used rows.
+ * Accepted: channels % 64 == 0, channels / group in {8, 16, 32, 64}, kernel_size == 3, dw_kernel_size odd in 1 .. 7, dilation >= 1,
+ * center_feature_scale 0 / 1, ln_eps >= 0.  Everything else is refused.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct VllmDcnv3LayerDesc {
+    int32_t channels, group, kernel_size, dw_kernel_size, dilation;
+    int32_t center_feature_scale;   /* 0 / 1 */
+    int32_t n_proj;                 /* rows of the packed projection */
+    float offset_scale, ln_eps;
+    int32_t reserved0;              /* 0 */
+    const uint16_t *input_proj_w, *input_proj_b;     /* [C, C], [C]                 (device, bf16) */
+    const uint16_t *dw_w, *dw_b;                     /* [C, dwk * dwk] (nn.Conv2d depth-wise weight [C, 1, k, k] as stored), [C] */
+    const uint16_t *ln_w, *ln_b;                     /* [C], [C] */
+    const uint16_t *proj_w, *proj_b;                 /* [n_proj, C], [n_proj] */
+    const uint16_t *output_proj_w, *output_proj_b;   /* [C, C], [C] */
+} VllmDcnv3LayerDesc;
+unsigned long vllm_dcnv3_layer_desc_sizeof(void);
+/* Bytes of device scratch vllm_dcnv3_layer_forward needs; host-only; negative for a refused descriptor or negative sizes. */
+long vllm_dcnv3_layer_workspace_bytes(const VllmDcnv3LayerDesc *desc, int N, int H, int W);
+/* input, out [N, H, W, C] bf16.  One stream, no allocation, no synchronisation.  A refused call (bad descriptor, NULL or misaligned
+ * pointer, short or misaligned workspace, N H W >= 2^31: VLLM_EINVAL, reason in vllm_last_error()) has enqueued nothing; N H W == 0
+ * returns VLLM_OK without a launch. */
+/* Alignment: input, out, every weight / bias of the descriptor and workspace 16 bytes. */
+int vllm_dcnv3_layer_forward(const VllmDcnv3LayerDesc *desc, const uint16_t *input, int N, int H, int W, uint16_t *out,
+                             void *workspace, long workspace_bytes, vllm_stream_t stream);
+long vllm_dcnv3_layer_calls(void);   /* calls of vllm_dcnv3_layer_forward in this process that reached their launches (tests) */
+/* The two kernels of the layer, exposed for the parity tests.
+ * vllm_dwconv_ln_gelu_bf16: out [N, H, W, C] = GELU_erf(LayerNorm_C(depth-wise dwk x dwk conv of x [N, H, W, C], zero padding dwk / 2,
+ *   + dw_b) * ln_w + ln_b), channels-last, fp32 from the taps to the one rounding of the result.  C a multiple of 8, at most 4096; dwk
+ *   odd in 1 .. 7; N H W < 2^31.  A tap outside the image reads nothing that reaches a result.
+ * vllm_dcnv3_sample_fused_bf16: x_proj [N, H, W, G D] bf16, om [N H W, ld_om] fp32 rows of (18 G offsets | 9 G logits | G centre
+ *   logits with center_feature_scale) -- columns behind them are never read; out [N, H, W, G D] bf16 = core (1 - s) + x_proj s with
+ *   core the 3 x 3 DCNv3 sum (stride 1, pad == dilation) under the softmax of the 9 logits and s = sigmoid(centre logit) (s = 0
+ *   without the flag).  D in {8, 16, 32, 64}, ld_om a multiple of 4 and >= the used columns, N H W < 2^31. */
+/* Alignment (both): every pointer 16 bytes. */
+int vllm_dwconv_ln_gelu_bf16(const uint16_t *x, const uint16_t *dw_w, const uint16_t *dw_b, const uint16_t *ln_w, const uint16_t *ln_b,
+                             int N, int H, int W, int C, int dwk, float eps, uint16_t *out, vllm_stream_t stream);
+int vllm_dcnv3_sample_fused_bf16(const uint16_t *x_proj, const float *om, int ld_om, int N, int H, int W, int G, int D, int dilation,
+                                 float offset_scale, int center_feature_scale, uint16_t *out, vllm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * f4. Region-encoder point sampling.
  *
  * Replaces: point_sample (F.grid_sample(input, 2*coords-1), bilinear, zeros padding, align_corners=False) and the masked

@@ -160,6 +160,14 @@ class VllmMsdaLayerGrads(ctypes.Structure):
                                   "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
 
 
+class VllmDcnv3LayerDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("channels", "group", "kernel_size", "dw_kernel_size", "dilation", "center_feature_scale",
+                                              "n_proj")] + \
+               [("offset_scale", ctypes.c_float), ("ln_eps", ctypes.c_float), ("reserved0", ctypes.c_int32)] + \
+               [(n, _P) for n in ("input_proj_w", "input_proj_b", "dw_w", "dw_b", "ln_w", "ln_b", "proj_w", "proj_b",
+                                  "output_proj_w", "output_proj_b")]
+
+
 class VllmVitLayerTrain(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("hidden", "heads", "inter")] + [("eps", ctypes.c_float)] + \
                [(n, _P) for n in ("norm1_w", "qkv_w", "qkv_b", "q_norm_w", "k_norm_w", "proj_w", "proj_b", "ls1", "norm2_w",
@@ -219,6 +227,7 @@ def check_struct_layouts():
     assert ctypes.sizeof(VllmRegionEncoderGrads) == L.vllm_region_encoder_grads_sizeof(), "VllmRegionEncoderGrads layout mismatch"
     assert ctypes.sizeof(VllmMsdaLayerDesc) == L.vllm_msda_layer_desc_sizeof(), "VllmMsdaLayerDesc layout mismatch"
     assert ctypes.sizeof(VllmMsdaLayerGrads) == L.vllm_msda_layer_grads_sizeof(), "VllmMsdaLayerGrads layout mismatch"
+    assert ctypes.sizeof(VllmDcnv3LayerDesc) == L.vllm_dcnv3_layer_desc_sizeof(), "VllmDcnv3LayerDesc layout mismatch"
     assert ctypes.sizeof(VllmVitDesc) == L.vllm_vit_desc_sizeof(), "VllmVitDesc layout mismatch"
     assert ctypes.sizeof(VllmVitLayer) == L.vllm_vit_layer_sizeof(), "VllmVitLayer layout mismatch"
     assert ctypes.sizeof(VllmBridgeDesc) == L.vllm_bridge_desc_sizeof(), "VllmBridgeDesc layout mismatch"

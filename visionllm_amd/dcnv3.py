@@ -7,11 +7,13 @@ SURVEY.md section 8 row f3.  Same names, argument order and error behaviour as
   ``dcnv3_backward`` -> ``vllm_dcnv3_backward_f32 / _f64``);
 * ``DCNv3`` (module)       -- visionllmv2/model/ops_dcnv3/modules/dcnv3.py:222-349: the projections, depth-wise conv,
   norm / activation and softmax stay torch modules with the reference's parameter names, the sampling core is the native
-  kernel (fp32, as the reference upcasts around it, :330-340).
+  kernel (fp32, as the reference upcasts around it, :330-340).  ``DCNv3.native_layer = True`` runs the inference forward of a bf16
+  module as one native call instead (``vllm_dcnv3_layer_forward``, csrc/dcnv3_layer.hip; conditions: ``native_layer_applies``).
 
 The compute is libvllm_hip.so (visionllm_amd/csrc/dcnv3.hip); like the reference's extension ("Not implement on cpu",
 src/cpu/dcnv3_cpu.cpp:25) it raises for CPU tensors.
 """
+import ctypes
 import warnings
 
 import torch
@@ -193,6 +195,11 @@ class DCNv3(nn.Module):
         self.offset_scale, self.channels, self.kernel_size, self.dw_kernel_size = offset_scale, channels, kernel_size, dw_kernel_size
         self.stride, self.dilation, self.pad, self.group, self.group_channels = stride, dilation, pad, group, d
         self.center_feature_scale = center_feature_scale
+        self.norm_layer, self.act_layer = norm_layer, act_layer
+        # True: a bf16 module on the GPU runs its inference forward as ONE native call (vllm_dcnv3_layer_forward) wherever
+        # native_layer_applies() holds; every other call, and every call with the default, runs the composed statements of forward()
+        self.native_layer = False
+        self._native_pack = None   # (signature of the source parameters, packed projection weight, bias): packed_projection()
         self.dw_conv = nn.Sequential(
             nn.Conv2d(channels, channels, kernel_size=dw_kernel_size, stride=1, padding=(dw_kernel_size - 1) // 2,
                       groups=channels),
@@ -219,6 +226,8 @@ class DCNv3(nn.Module):
 
     def forward(self, input):
         """(N, H, W, C) -> (N, H, W, C)"""
+        if self.native_layer and self.native_layer_applies(input):
+            return self._native_forward(input)
         N, H, W, _ = input.shape
         x = self.input_proj(input)
         x_proj = x
@@ -235,3 +244,76 @@ class DCNv3(nn.Module):
             cfs = cfs[..., None].repeat(1, 1, 1, 1, self.channels // self.group).flatten(-2)
             x = x * (1 - cfs) + x_proj * cfs
         return self.output_proj(x)
+
+    # ---- the native layer (include/vllm_hip.h, section f3b) ----
+    def native_layer_applies(self, input):
+        """What vllm_dcnv3_layer_forward serves: inference (grad mode off) of a bf16 module on the input's GPU, LayerNorm + GELU behind
+        the depth-wise conv, stride 1, pad == dilation, and the descriptor's limits."""
+        if torch.is_grad_enabled() or not input.is_cuda or input.dtype != torch.bfloat16 or input.dim() != 4 or \
+                input.shape[-1] != self.channels:
+            return False
+        if self.norm_layer != "LN" or self.act_layer != "GELU" or self.stride != 1 or self.pad != self.dilation or self.dilation < 1:
+            return False
+        if self.channels % 64 or self.channels > 4096 or self.group_channels not in (8, 16, 32, 64) or self.kernel_size != 3 or \
+                self.dw_kernel_size % 2 != 1 or not 1 <= self.dw_kernel_size <= 7:
+            return False
+        # (the reference declares the two centre-feature-scale parameters fp32 and rounds them to x1's dtype in forward; a model
+        #  converted wholesale holds them in bf16 already: the packed rows are the same)
+        fp32_names = ("center_feature_scale_proj_weight", "center_feature_scale_proj_bias")
+        for name, p in self.named_parameters():
+            if p.device != input.device or not (p.dtype == torch.bfloat16 or (p.dtype == torch.float32 and name in fp32_names)):
+                return False
+        return True
+
+    def packed_projection(self):
+        """The offset, mask and centre-feature-scale linears over x1 as ONE linear: rows [0, 18 G) offset.weight, [18 G, 27 G)
+        mask.weight, [27 G, 28 G) center_feature_scale_proj_weight (with the flag), zero rows up to a multiple of 8.
+        -> (weight [n_proj, C], bias [n_proj]) in offset.weight's dtype, rebuilt when a source parameter changes."""
+        src = [self.offset.weight, self.offset.bias, self.mask.weight, self.mask.bias]
+        if self.center_feature_scale:
+            src += [self.center_feature_scale_proj_weight, self.center_feature_scale_proj_bias]
+        key = tuple((p.data_ptr(), p._version, p.dtype, p.device) for p in src)
+        if self._native_pack is None or self._native_pack[0] != key:
+            dt = self.offset.weight.dtype
+            ws, bs = [p.detach().to(dt) for p in src[0::2]], [p.detach().to(dt) for p in src[1::2]]
+            used = sum(w.shape[0] for w in ws)
+            n_proj = (used + 7) // 8 * 8
+            w = torch.zeros((n_proj, self.channels), dtype=dt, device=self.offset.weight.device)
+            b = torch.zeros((n_proj,), dtype=dt, device=self.offset.weight.device)
+            w[:used] = torch.cat(ws, 0)
+            b[:used] = torch.cat(bs, 0)
+            self._native_pack = (key, w, b)
+        return self._native_pack[1], self._native_pack[2]
+
+    def native_descriptor(self):
+        """-> (VllmDcnv3LayerDesc of this module, the tensors its pointers refer to: keep them until the call has been enqueued).
+        Parameters that are views at an unaligned storage offset are copied (the kernels read 16-byte vectors)."""
+        pw, pb = self.packed_projection()
+        conv, ln = self.dw_conv[0], self.dw_conv[1][-1]
+        desc = _lib.VllmDcnv3LayerDesc()
+        desc.channels, desc.group, desc.kernel_size, desc.dw_kernel_size = self.channels, self.group, self.kernel_size, self.dw_kernel_size
+        desc.dilation, desc.center_feature_scale, desc.n_proj = self.dilation, int(bool(self.center_feature_scale)), pw.shape[0]
+        desc.offset_scale, desc.ln_eps = float(self.offset_scale), float(ln.eps)
+        keep = []
+        for name, t in (("input_proj_w", self.input_proj.weight), ("input_proj_b", self.input_proj.bias), ("dw_w", conv.weight),
+                        ("dw_b", conv.bias), ("ln_w", ln.weight), ("ln_b", ln.bias), ("proj_w", pw), ("proj_b", pb),
+                        ("output_proj_w", self.output_proj.weight), ("output_proj_b", self.output_proj.bias)):
+            a = _lib.aligned(t.detach())
+            keep.append(a)
+            setattr(desc, name, a.data_ptr())
+        return desc, keep
+
+    def _native_forward(self, input):
+        N, H, W, _ = input.shape
+        x = _lib.aligned(input)
+        desc, keep = self.native_descriptor()
+        L = _lib.lib()
+        nbytes = L.vllm_dcnv3_layer_workspace_bytes(ctypes.byref(desc), N, H, W)
+        _lib.check(0 if nbytes >= 0 else -1, "vllm_dcnv3_layer_workspace_bytes")
+        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+        out = torch.empty_like(x)
+        with torch.cuda.device(x.device):
+            _lib.check(L.vllm_dcnv3_layer_forward(ctypes.byref(desc), _lib.ptr(x), N, H, W, _lib.ptr(out), _lib.ptr(ws), nbytes,
+                                                  _lib.current_stream(x.device)), "vllm_dcnv3_layer_forward")
+        del keep   # (alive until here: the call has been enqueued, and the allocator orders any reuse behind it on this stream)
+        return out
