@@ -156,7 +156,7 @@ def _ws_entries():
         add(f"clip_layer_backward_{tag}", L.vllm_clip_layer_backward_workspace_bytes(ctypes.byref(ld), B, S),
             lambda w, n, ld=ld, B=B, S=S: L.vllm_clip_layer_backward(ctypes.byref(ld), p, B, S, p, ctypes.byref(sv), p, ctypes.byref(gr), vp(w), n,
                                                                      None))
-        # forward: [sk][xn] (clip_train.cpp, "forward: [sk][xn]"): the stream-K scratch from 1024 rows on, LN1(x) / LN2(x1) [M, C] bf16; every
+        # forward: [sk][xn] (layer_train.cpp, "forward: [sk][xn][qkn]", qkn without bytes): the stream-K scratch from 1024 rows on, LN1(x) / LN2(x1) [M, C] bf16; every
         # piece rounded up to 256 bytes
         M, C = B * S, 128
         fwd = (align256(L.vllm_gemm_scratch_bytes()) if M >= 1024 else 0) + align256(M * C * 2)

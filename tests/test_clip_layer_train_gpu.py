@@ -1,4 +1,4 @@
-"""GPU: training one CLIP encoder layer (clip_train.cpp), its new row-wise kernel (norm.hip), the two quick-GELU training epilogues and
+"""GPU: training one CLIP encoder layer (layer_train.cpp), its new row-wise kernel (norm.hip), the two quick-GELU training epilogues and
 the tower from pixels (clip_vit.py).
 
 Yardstick: torch fp64 autograd of HF 4.34's statements restated in clip_layer_train_inputs.py, on the same bf16 parameters, input and
@@ -515,7 +515,7 @@ def test_clip_layer_train_workspace(idx, frozen, monkeypatch):
 
 @pytest.mark.parametrize("idx", [0, 2])
 def test_clip_layer_forward_train_takes_the_head_of_the_workspace(idx):
-    """The training forward is served by [sk][xn] alone (clip_train.cpp's layout comment; the number is derived here, as in
+    """The training forward is served by [sk][xn] alone (layer_train.cpp's layout comment, qkn without bytes; the number is derived here, as in
     test_clip_layer_train_cpu.py): straight through the C ABI with exactly those bytes, hostile and guarded."""
     from visionllm_amd.clip_vit import _SAVED, _fused_params, _layer_desc
     L = _lib.lib()

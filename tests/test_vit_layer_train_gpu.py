@@ -1,4 +1,4 @@
-"""GPU: training one InternViT encoder layer (vit_train.cpp) and its new row-wise kernels (norm.hip) and GEMM epilogue.
+"""GPU: training one InternViT encoder layer (layer_train.cpp) and its new row-wise kernels (norm.hip) and GEMM epilogue.
 
 Yardstick: torch fp64 autograd of the reference's statements restated in vit_layer_train_inputs.py, on the same bf16 parameters, input
 and grad_out.  The kernels alone are judged per element (1 bf16 ulp + 2^-17 of the natural magnitude, the LayerNorm backward test's

@@ -10,7 +10,7 @@ Three entries have a contract of their own, stated in the header, and are tried 
     keeps the stream-K route from being planned (gemm256_launch plans it when the slots of every CU fit); what is refused is a scratch
     that cannot hold the 4096 flag bytes and one 262144-byte slot, and a misaligned one.
   * vllm_bridge_forward_train / vllm_vit_layer_forward_train need only the head of the backward's workspace ([sk] / [sk][xn][qkn]); the
-    sizes are derived here from the layout comments of bridge_train.cpp / vit_train.cpp, not read from the library.
+    sizes are derived here from the layout comments of bridge_train.cpp / layer_train.cpp, not read from the library.
   * the splice takes no byte count (vllm_splice_workspace_ints int32 words, element alignment): NULL is what can be refused."""
 import ctypes
 
@@ -124,7 +124,7 @@ def _entries():
         add(f"vit_layer_backward_{tag}", L.vllm_vit_layer_backward_workspace_bytes(ctypes.byref(ld), B, S),
             lambda w, n, ld=ld, g=g, B=B, S=S: L.vllm_vit_layer_backward(ctypes.byref(ld), p, B, S, p, ctypes.byref(sv), p, ctypes.byref(g),
                                                                          vp(w), n, None))
-        # forward: [sk][xn][qkn] (vit_train.cpp, "forward: [sk][xn][qkn]"): the stream-K scratch from 1024 rows on, norm1(x) / norm2(x1)
+        # forward: [sk][xn][qkn] (layer_train.cpp, "forward: [sk][xn][qkn]"): the stream-K scratch from 1024 rows on, norm1(x) / norm2(x1)
         # [M, C] bf16, the post-norm q, k beside v [M, 3C] bf16 with QK-norm; every piece rounded up to 256 bytes
         M, C = B * S, 128
         fwd = (align256(L.vllm_gemm_scratch_bytes()) if M >= 1024 else 0) + align256(M * C * 2) + (align256(M * 3 * C * 2) if qkn else 0)

@@ -540,7 +540,7 @@ def test_vit_layer_train_workspace(idx, frozen, monkeypatch):
 
 @pytest.mark.parametrize("idx", [0, 2])
 def test_vit_layer_forward_train_takes_the_head_of_the_workspace(idx):
-    """The training forward is served by [sk][xn][qkn] alone (vit_train.cpp's layout comment; the number is derived here, as in
+    """The training forward is served by [sk][xn][qkn] alone (layer_train.cpp's layout comment; the number is derived here, as in
     test_workspace_contract_cpu.py): straight through the C ABI with exactly those bytes, hostile and guarded, it writes the bits the
     module's forward does with the backward's whole workspace."""
     import test_vit_layer_train_gpu as TL

@@ -188,6 +188,20 @@ def test_workspace_sizes_are_the_recorded_ones(name, query, table):
     assert got == table
 
 
+@pytest.mark.parametrize("act", [_lib.EPI_GELU, _lib.EPI_QUICK_GELU])
+def test_clip_layer_sizes_are_those_of_an_internvit_layer_without_qk_norm(act):
+    """One layout serves both layer families: without a QK-norm its qkn slot has no bytes, and LayerNorm's weight + bias partials are the
+    size of the QK-norm's q + k partials.  So for every LAYER_BWD row without QK-norm (no rows and the refusals included)
+    vllm_clip_layer_backward_workspace_bytes answers the InternViT number, whichever the activation."""
+    rows = [(args, want) for args, want in LAYER_BWD if not args[3]]
+    assert len(rows) == 8 and sum(want == -1 for _, want in rows) == 3
+    got = []
+    for (hidden, heads, inter, _, B, S), _ in rows:
+        d = _fill(_lib.VllmClipLayerTrain, dict(hidden=hidden, heads=heads, inter=inter, act=act, eps=1e-5))
+        got.append(_lib.lib().vllm_clip_layer_backward_workspace_bytes(ctypes.byref(d), B, S))
+    assert got == [want for _, want in rows]
+
+
 def test_null_descriptors_answer_minus_one():
     L = _lib.lib()
     assert L.vllm_bridge_workspace_bytes(None, 1, 1024) == -1

@@ -21,7 +21,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .vit_common import (EncoderPlan, _require_bf16_cuda, embed_pixels, fold_norm_into_linear, kpad_for, model_output, norm_folding_applies,
+from .vit_common import (EncoderPlan, LayerTrainABI, _require_bf16_cuda, embed_pixels, fold_norm_into_linear, kpad_for, model_output, norm_folding_applies,
                          plan_ptr, padded_patch_weight, run_encoder)
 
 try:
@@ -137,37 +137,16 @@ def _fused_params(mp):
     return (d(n1w), d(n1b), torch.cat([d(qw), d(kw), d(vw)], 0), torch.cat([d(qb), d(kb), d(vb)], 0)) + tuple(d(t) for t in mp[8:])
 
 
-def _layer_desc(meta, params, keep):
+_TRAIN = LayerTrainABI("clip", _lib.VllmClipLayerTrain, _lib.VllmClipLayerSaved, _lib.VllmClipLayerGrads, _LAYER_PARAMS, _SAVED)
+
+
+def _scalars(meta):
     heads, inter, act, eps = meta
-    fields = {}
-    for name, t in zip(_LAYER_PARAMS, params):
-        _require_bf16_cuda(name, t)
-        a = _lib.aligned(t.detach())
-        keep.append(a)
-        fields[name] = a.data_ptr()
-    return _lib.VllmClipLayerTrain(hidden=params[0].shape[0], heads=heads, inter=inter, act=act, eps=eps, **fields)
+    return dict(heads=heads, inter=inter, act=act, eps=eps)
 
 
-def _layer_forward(meta, x, params):
-    """vllm_clip_layer_forward_train on x [B, S, C] (16-byte aligned) and the parameters in _LAYER_PARAMS order -> (out, the saved tensors
-    in _SAVED order)."""
-    keep = []
-    d = _layer_desc(meta, params, keep)
-    B, S, C = x.shape
-    heads, inter = meta[0], meta[1]
-    dev, M = x.device, B * S
-    L = _lib.lib()
-    _lib.check_struct_layouts()
-    bf = dict(dtype=torch.bfloat16, device=dev)
-    out = torch.empty((B, S, C), **bf)
-    saved = [torch.empty((M, 3 * C), **bf), torch.empty((M, C), **bf), torch.empty((B, heads, S), dtype=torch.float32, device=dev),
-             torch.empty((M, C), **bf), torch.empty((M, inter), **bf), torch.empty((M, inter), **bf)]
-    sv = _lib.VllmClipLayerSaved(**{n: t.data_ptr() for n, t in zip(_SAVED, saved)})
-    with torch.cuda.device(dev):
-        ws, wsb = _lib.sized_workspace(dev, L.vllm_clip_layer_backward_workspace_bytes(ctypes.byref(d), B, S), "vllm_clip_layer_backward_workspace_bytes")
-        _lib.check(L.vllm_clip_layer_forward_train(ctypes.byref(d), _lib.ptr(x), B, S, _lib.ptr(out), ctypes.byref(sv), _lib.ptr(ws), wsb,
-                                                   _lib.current_stream(dev)), "vllm_clip_layer_forward_train")
-    return out, saved
+def _layer_desc(meta, params, keep):
+    return _TRAIN.desc(_scalars(meta), params, keep)
 
 
 class _ClipLayerTrain(torch.autograd.Function):
@@ -177,41 +156,25 @@ class _ClipLayerTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, meta, x, *mp):
-        out, saved = _layer_forward(meta, x, _fused_params(mp))
+        out, saved = _TRAIN.forward(_scalars(meta), x, _fused_params(mp))
         ctx.meta = meta
         ctx.save_for_backward(x, *saved, *mp)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        meta = ctx.meta
         t = ctx.saved_tensors
         x, saved, mp = t[0], t[1:1 + len(_SAVED)], t[1 + len(_SAVED):]
-        params = _fused_params(mp)
-        keep = []
-        d = _layer_desc(meta, params, keep)
-        B, S, C = x.shape
-        dev = x.device
-        need_x = ctx.needs_input_grad[1]
+        C = x.shape[-1]
         nm = dict(zip(_MODULE_PARAMS, ctx.needs_input_grad[2:]))
         need = {n: nm.get(n, False) for n in _LAYER_PARAMS}
         need["qkv_w"] = nm["q_w"] or nm["k_w"] or nm["v_w"]
         need["qkv_b"] = nm["q_b"] or nm["k_b"] or nm["v_b"]
-        for b, w in (("qkv_b", "qkv_w"), ("proj_b", "proj_w"), ("fc1_b", "fc1_w"), ("fc2_b", "fc2_w")):   # a bias gradient rides on its weight's launch
-            need[w] = need[w] or need[b]
-        g = _lib.aligned(gout.to(torch.bfloat16))
-        grads = {n: (torch.empty(p.shape, dtype=torch.bfloat16, device=dev) if need[n] else None) for n, p in zip(_LAYER_PARAMS, params)}
-        gx = torch.empty_like(x) if need_x else None
-        gs = _lib.VllmClipLayerGrads(**{n: (t_.data_ptr() if t_ is not None else None) for n, t_ in grads.items()})
-        sv = _lib.VllmClipLayerSaved(**{n: t_.data_ptr() for n, t_ in zip(_SAVED, saved)})
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            ws, wsb = _lib.sized_workspace(dev, L.vllm_clip_layer_backward_workspace_bytes(ctypes.byref(d), B, S),
-                                           "vllm_clip_layer_backward_workspace_bytes")
-            _lib.check(L.vllm_clip_layer_backward(ctypes.byref(d), _lib.ptr(x), B, S, _lib.ptr(g), ctypes.byref(sv), _lib.ptr(gx),
-                                                  ctypes.byref(gs), _lib.ptr(ws), wsb, _lib.current_stream(dev)), "vllm_clip_layer_backward")
+        gx, grads = _TRAIN.backward(_scalars(ctx.meta), x, saved, _fused_params(mp), gout, ctx.needs_input_grad[1],
+                                    [need[n] for n in _LAYER_PARAMS])
+        grads = dict(zip(_LAYER_PARAMS, grads))
         out = []
-        for n in _MODULE_PARAMS:   # (a weight gradient computed only for its bias, or a q / k / v slice nobody asked for, is dropped)
+        for n in _MODULE_PARAMS:   # (a q / k / v slice nobody asked for is dropped)
             if not nm[n]:
                 out.append(None)
             elif n[0] in "qkv" and n[1] == "_":
@@ -259,7 +222,7 @@ class _CLIPEncoderLayer(nn.Module):
         x = _lib.aligned(x)   # (16-byte aligned rows: a view at another storage offset is copied -- differentiably)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in mp)):
             return (_ClipLayerTrain.apply(self._meta, x, *mp),)
-        return (_layer_forward(self._meta, x.detach(), _fused_params(mp))[0],)
+        return (_TRAIN.forward(_scalars(self._meta), x.detach(), _fused_params(mp))[0],)
 
 
 class _CLIPEncoder(nn.Module):

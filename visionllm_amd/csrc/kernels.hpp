@@ -14,11 +14,11 @@ enum GemmEpilogue : int {
     EPI_GELU_BWD = VLLM_EPI_GELU_BWD,
     EPI_MSDA = 100,   // internal (msda_layer.hip): offsets -> sampling locations, logits -> softmax weights, both fp32
     EPI_GELU_SAVE = 101,   // internal (bridge_train.cpp): EPI_GELU that also stores the pre-activation to GemmArgs::pre
-    EPI_RESIDUAL_SAVE = 102,   // internal (vit_train.cpp): EPI_RESIDUAL that also stores bf16(x W^T + b), the pre-LayerScale output, to GemmArgs::pre
-    // internal (clip_train.cpp): EPI_QUICK_GELU that also stores bf16(x W^T + b), the pre-activation, to GemmArgs::pre (EPI_GELU_SAVE's rule:
+    EPI_RESIDUAL_SAVE = 102,   // internal (layer_train.cpp): EPI_RESIDUAL that also stores bf16(x W^T + b), the pre-LayerScale output, to GemmArgs::pre
+    // internal (layer_train.cpp): EPI_QUICK_GELU that also stores bf16(x W^T + b), the pre-activation, to GemmArgs::pre (EPI_GELU_SAVE's rule:
     // one workgroup per tile without a stream-K tail where the persistent schedule would take EPI_QUICK_GELU, so Y keeps the inference bits)
     EPI_QUICK_GELU_SAVE = 103,
-    EPI_QUICK_GELU_BWD = 104,   // internal (clip_train.cpp): y = (x W^T) * q'(res[m, n]), q(h) = h sigmoid(1.702 h), res = the saved pre-activation; no bias
+    EPI_QUICK_GELU_BWD = 104,   // internal (layer_train.cpp): y = (x W^T) * q'(res[m, n]), q(h) = h sigmoid(1.702 h), res = the saved pre-activation; no bias
     // internal (gemm256p.hip): the instantiation of EPI_RESIDUAL whose residual comes in through the operand ring.  A value of its
     // own and no further template flag, for two reasons: the kernel's name tells the two routes apart in a profile
     // (gemm256p_kernel<110, ...> against <3, ...>), and tests/test_capi.py counts the instantiations named gemm256p_kernel<3, ...>
@@ -129,12 +129,12 @@ long ln_bwd_workspace_bytes(long rows, int C);
 int ln_bwd_launch(const uint16_t *x, int ldx, const float *dz, int ldz, const uint16_t *gamma, float eps, long rows, int C,
                   uint16_t *dx, int lddx, uint16_t *grad_w, uint16_t *grad_b, void *ws, long ws_bytes, hipStream_t st);
 
-// InternViT layer backward, row-wise pieces (norm.hip; orchestrated by vit_train.cpp)
+// InternViT layer backward, row-wise pieces (norm.hip; orchestrated by layer_train.cpp)
 long rms_bwd_workspace_bytes(long rows, int C, int G);
 int rms_bwd_launch(const uint16_t *x, int ldx, const uint16_t *gy, int ldgy, const uint16_t *w, const uint16_t *w2, int G, float eps, long rows,
                    int C, uint16_t *gx, int ldgx, const uint16_t *gres, int ldgr, uint16_t *gw, uint16_t *gw2, void *ws, long ws_bytes,
                    hipStream_t st);
-// CLIP layer backward, row-wise piece (norm.hip; orchestrated by clip_train.cpp): nn.LayerNorm backward with bf16 grad_y and a residual gradient
+// CLIP layer backward, row-wise piece (norm.hip; orchestrated by layer_train.cpp): nn.LayerNorm backward with bf16 grad_y and a residual gradient
 long ln_res_bwd_workspace_bytes(long rows, int C);
 int ln_res_bwd_launch(const uint16_t *x, int ldx, const uint16_t *gy, int ldgy, const uint16_t *w, float eps, long rows, int C, uint16_t *gx,
                       int ldgx, const uint16_t *gres, int ldgr, uint16_t *gw, uint16_t *gb, void *ws, long ws_bytes, hipStream_t st);

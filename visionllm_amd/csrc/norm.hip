@@ -178,7 +178,7 @@ int norm_bf16_launch(bool rms, const uint16_t *x, int ldx, const uint16_t *w, co
 }
 
 
-// ---- backward of the row-wise pieces of an InternViT layer (vit_train.cpp) -------------------------------------------------
+// ---- backward of the row-wise pieces of an InternViT layer (layer_train.cpp) -----------------------------------------------
 //   rms_bwd_kernel   InternRMSNorm backward (modeling_intern_vit.py:33-44 under autograd; q_norm / k_norm :131-134 with G = 2): per row
 //                    the statistic is recomputed from x in fp32;  xhat = x r,  g = grad_y w,
 //                    grad_x = r (g - xhat mean(g xhat)) [+ grad_res]  (one rounding),  grad_w = sum_rows grad_y xhat  (xhat NOT rounded).
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(RB_THREADS) void rms_bwd_kernel(const uint16_t *__r
     }
 }
 
-// nn.LayerNorm backward inside the CLIP layer's chain (clip_train.cpp): rms_bwd_kernel's walk with a mean.  Per row the mean and the
+// nn.LayerNorm backward inside the CLIP layer's chain (layer_train.cpp): rms_bwd_kernel's walk with a mean.  Per row the mean and the
 // second moment about it are recomputed from x in fp32 (two passes over the registers: no cancellation);  xhat = (x - mean) r,
 // g = grad_y gamma,  grad_x = r (g - mean(g) - xhat mean(g xhat)) [+ grad_res]  (one rounding),  grad_w = sum_rows grad_y xhat  (xhat NOT
 // rounded),  grad_b = sum_rows grad_y.  The partials are [2][nbv][C]: grad_w's, then grad_b's.  A chunk past the row's end (a thread

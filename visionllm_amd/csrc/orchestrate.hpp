@@ -1,4 +1,4 @@
-// Host-side scaffolding shared by the orchestrators (vit.cpp, vit_train.cpp, clip_train.cpp, bridge_train.cpp, embed_train.hip, msda_layer.hip, msda_layer_train.cpp): the
+// Host-side scaffolding shared by the orchestrators (vit.cpp, layer_train.cpp, bridge_train.cpp, embed_train.hip, msda_layer.hip, msda_layer_train.cpp): the
 // pieces every entry point that strings kernels together on the caller's stream used to copy from the one before.  Host code only.
 #pragma once
 #include <initializer_list>
@@ -42,6 +42,23 @@ inline int linear_dgrad(hipStream_t st, int epi, const uint16_t *dY, const uint1
     if (pre) { a.res = pre; a.ldr = in; }
     gemm_set_scratch(a, sk, sk_bytes);
     return gemm_bf16_launch(epi, a, st);
+}
+
+// Attention over packed qkv: q and k are the first two column blocks of the [B S, 3C] slab `qk`, v the third of the slab `qkv` (the same
+// slab, unless a QK-norm has written q / k elsewhere); out [B, S, H, D]; `lse` [B, H, S] in the training forward only.
+inline AttnArgs packed_qkv_attn(const uint16_t *qk, const uint16_t *qkv, uint16_t *out, int B, int S, int H, int D, float scale,
+                                float *lse = nullptr)
+{
+    const int C = H * D;
+    AttnArgs a;
+    a.q = qk; a.k = qk + C; a.v = qkv + 2 * C; a.out = out;
+    a.q_bs = a.k_bs = a.v_bs = (long)S * 3 * C;
+    a.q_ts = a.k_ts = a.v_ts = 3 * C;
+    a.q_hs = a.k_hs = a.v_hs = D;
+    a.B = B; a.S = S; a.H = H; a.nqt = 0;
+    a.scale_log2e = scale * 1.4426950408889634f;
+    a.lse = lse;
+    return a;
 }
 
 }  // namespace vllm

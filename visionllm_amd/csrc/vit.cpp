@@ -188,17 +188,8 @@ extern "C" int vllm_vit_forward(const VllmVitDesc *d, const void *pixels, int n,
             if (L.q_norm_w) TRY(norm_bf16_launch(true, qkv, 3 * C, L.q_norm_w, nullptr, qkv, 3 * C, M, C, d->eps, st));
             if (L.k_norm_w) TRY(norm_bf16_launch(true, qkv + C, 3 * C, L.k_norm_w, nullptr, qkv + C, 3 * C, M, C, d->eps, st));
         }
-        {
-            AttnArgs a;
-            a.q = qkv; a.k = qkv + C; a.v = qkv + 2 * C; a.out = ao;
-            a.q_bs = a.k_bs = a.v_bs = (long)S * 3 * C;
-            a.q_ts = a.k_ts = a.v_ts = 3 * C;
-            a.q_hs = a.k_hs = a.v_hs = D;
-            a.B = n; a.S = S; a.H = H; a.nqt = 0;
-            a.scale_log2e = scale * 1.4426950408889634f;
-            prof_mark(PT_ATTN, st);
-            TRY(attn_fwd_launch(a, D, st));
-        }
+        prof_mark(PT_ATTN, st);
+        TRY(attn_fwd_launch(packed_qkv_attn(qkv, qkv, ao, n, S, H, D, scale), D, st));
         prof_mark(PT_PROJ, st);
         if (fold) TRY(gemm_ln(EPI_RESIDUAL, ao, C, L.proj_w, C, L.proj_b, hmid, C, C, C, L.ls1, h, C, ln_b, nullptr, nullptr, nullptr));
         else TRY(gemm(st, EPI_RESIDUAL, ao, C, L.proj_w, C, L.proj_b, hmid, C, (int)M, C, C, L.ls1, h, C, 0, 0, sk, SK_SCRATCH_BYTES));

@@ -24,7 +24,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .vit_common import (EncoderPlan, _require_bf16_cuda, embed_pixels, fold_norm_into_linear, kpad_for, model_output, norm_folding_applies,
+from .vit_common import (EncoderPlan, LayerTrainABI, _require_bf16_cuda, embed_pixels, fold_norm_into_linear, kpad_for, model_output, norm_folding_applies,
                          plan_ptr, padded_patch_weight, run_encoder)
 
 try:
@@ -172,40 +172,16 @@ _LAYER_PARAMS = ("norm1_w", "qkv_w", "qkv_b", "q_norm_w", "k_norm_w", "proj_w", 
 _SAVED = ("qkv", "ctx", "lse", "y1", "x1", "h1", "a1", "y2")   # VllmVitLayerSaved
 
 
-def _layer_desc(meta, params, keep):
+_TRAIN = LayerTrainABI("vit", _lib.VllmVitLayerTrain, _lib.VllmVitLayerSaved, _lib.VllmVitLayerGrads, _LAYER_PARAMS, _SAVED)
+
+
+def _scalars(meta):
     heads, inter, eps = meta
-    fields = {}
-    for name, t in zip(_LAYER_PARAMS, params):
-        if t is None:
-            fields[name] = None
-            continue
-        _require_bf16_cuda(name, t)
-        a = _lib.aligned(t.detach())
-        keep.append(a)
-        fields[name] = a.data_ptr()
-    return _lib.VllmVitLayerTrain(hidden=params[0].shape[0], heads=heads, inter=inter, eps=eps, **fields)
+    return dict(heads=heads, inter=inter, eps=eps)
 
 
-def _layer_forward(meta, x, params, want_saved):
-    """vllm_vit_layer_forward_train on x [B, S, C] (16-byte aligned) -> (out, the saved tensors in _SAVED order or None)."""
-    keep = []
-    d = _layer_desc(meta, params, keep)
-    B, S, C = x.shape
-    heads, inter, _ = meta
-    dev, M = x.device, B * S
-    L = _lib.lib()
-    _lib.check_struct_layouts()
-    bf = dict(dtype=torch.bfloat16, device=dev)
-    out = torch.empty((B, S, C), **bf)
-    saved = [torch.empty((M, 3 * C), **bf), torch.empty((M, C), **bf), torch.empty((B, heads, S), dtype=torch.float32, device=dev),
-             torch.empty((M, C), **bf), torch.empty((M, C), **bf), torch.empty((M, inter), **bf), torch.empty((M, inter), **bf),
-             torch.empty((M, C), **bf)]
-    sv = _lib.VllmVitLayerSaved(**{n: t.data_ptr() for n, t in zip(_SAVED, saved)})
-    with torch.cuda.device(dev):
-        ws, wsb = _lib.sized_workspace(dev, L.vllm_vit_layer_backward_workspace_bytes(ctypes.byref(d), B, S), "vllm_vit_layer_backward_workspace_bytes")
-        _lib.check(L.vllm_vit_layer_forward_train(ctypes.byref(d), _lib.ptr(x), B, S, _lib.ptr(out), ctypes.byref(sv), _lib.ptr(ws), wsb,
-                                                  _lib.current_stream(dev)), "vllm_vit_layer_forward_train")
-    return out, (saved if want_saved else None)
+def _layer_desc(meta, params, keep):
+    return _TRAIN.desc(_scalars(meta), params, keep)
 
 
 class _VitLayerTrain(torch.autograd.Function):
@@ -215,39 +191,17 @@ class _VitLayerTrain(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, meta, x, *params):
-        out, saved = _layer_forward(meta, x, params, True)
+        out, saved = _TRAIN.forward(_scalars(meta), x, params)
         ctx.meta = meta
         ctx.save_for_backward(x, *saved, *params)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        meta = ctx.meta
         t = ctx.saved_tensors
         x, saved, params = t[0], t[1:1 + len(_SAVED)], t[1 + len(_SAVED):]
-        keep = []
-        d = _layer_desc(meta, params, keep)
-        B, S, C = x.shape
-        dev = x.device
-        need = list(ctx.needs_input_grad[2:])
-        need_x = ctx.needs_input_grad[1]
-        idx = {n: i for i, n in enumerate(_LAYER_PARAMS)}
-        for b, w in (("qkv_b", "qkv_w"), ("proj_b", "proj_w"), ("fc1_b", "fc1_w"), ("fc2_b", "fc2_w")):   # a bias gradient rides on its weight's launch
-            ask_w = need[idx[b]] and params[idx[b]] is not None
-            need[idx[w]] = need[idx[w]] or ask_w
-        g = _lib.aligned(gout.to(torch.bfloat16))
-        grads = [torch.empty(p.shape, dtype=torch.bfloat16, device=dev) if (n and p is not None) else None for n, p in zip(need, params)]
-        gx = torch.empty_like(x) if need_x else None
-        gs = _lib.VllmVitLayerGrads(**{n: (t_.data_ptr() if t_ is not None else None) for n, t_ in zip(_LAYER_PARAMS, grads)})
-        sv = _lib.VllmVitLayerSaved(**{n: t_.data_ptr() for n, t_ in zip(_SAVED, saved)})
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            ws, wsb = _lib.sized_workspace(dev, L.vllm_vit_layer_backward_workspace_bytes(ctypes.byref(d), B, S),
-                                           "vllm_vit_layer_backward_workspace_bytes")
-            _lib.check(L.vllm_vit_layer_backward(ctypes.byref(d), _lib.ptr(x), B, S, _lib.ptr(g), ctypes.byref(sv), _lib.ptr(gx),
-                                                 ctypes.byref(gs), _lib.ptr(ws), wsb, _lib.current_stream(dev)), "vllm_vit_layer_backward")
-        out = [t_ if n else None for t_, n in zip(grads, ctx.needs_input_grad[2:])]   # (a weight gradient computed only for its bias is dropped)
-        return (None, gx) + tuple(out)
+        gx, grads = _TRAIN.backward(_scalars(ctx.meta), x, saved, params, gout, ctx.needs_input_grad[1], ctx.needs_input_grad[2:])
+        return (None, gx) + tuple(grads)
 
 
 class InternVisionEncoderLayer(nn.Module):
@@ -290,7 +244,7 @@ class InternVisionEncoderLayer(nn.Module):
         x = _lib.aligned(x)   # (16-byte aligned rows: a view at another storage offset is copied -- differentiably)
         if torch.is_grad_enabled() and (x.requires_grad or any(p is not None and p.requires_grad for p in params)):
             return _VitLayerTrain.apply(meta, x, *params)
-        return _layer_forward(meta, x.detach(), params, False)[0]
+        return _TRAIN.forward(_scalars(meta), x.detach(), params)[0]
 
 
 class InternVisionEncoder(nn.Module):

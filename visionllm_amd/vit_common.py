@@ -155,6 +155,73 @@ class _EmbedTrain(torch.autograd.Function):
         return (None,) + tuple(grads)
 
 
+class LayerTrainABI:
+    """What the autograd nodes of the two encoder-layer families share: the calls of vllm_<family>_layer_forward_train /
+    vllm_<family>_layer_backward around the family's three structs.  ``params`` / ``saved``: the member names of the descriptor's
+    parameter pointers (= those of the gradient table) and of the saved table, in the structs' order.  ``scalars`` of a call are the
+    descriptor's remaining members but ``hidden`` (heads, inter, eps, CLIP: act)."""
+
+    _BIAS_RIDES_ON = (("qkv_b", "qkv_w"), ("proj_b", "proj_w"), ("fc1_b", "fc1_w"), ("fc2_b", "fc2_w"))
+
+    def __init__(self, family, desc_cls, saved_cls, grads_cls, params, saved):
+        self.desc_cls, self.saved_cls, self.grads_cls, self.params, self.saved = desc_cls, saved_cls, grads_cls, params, saved
+        self.ws_query, self.fwd, self.bwd = (f"vllm_{family}_layer_{n}" for n in ("backward_workspace_bytes", "forward_train", "backward"))
+
+    def desc(self, scalars, params, keep):
+        """The descriptor for bf16 CUDA parameters in ``self.params`` order (None: the layer has none); ``keep`` receives the 16-byte
+        aligned tensors whose pointers it holds."""
+        fields = {}
+        for name, t in zip(self.params, params):
+            if t is None:
+                fields[name] = None
+                continue
+            _require_bf16_cuda(name, t)
+            a = _lib.aligned(t.detach())
+            keep.append(a)
+            fields[name] = a.data_ptr()
+        return self.desc_cls(hidden=params[0].shape[0], **scalars, **fields)
+
+    def _call(self, entry, d, x, *args):
+        B, S, _ = x.shape
+        dev = x.device
+        L = _lib.lib()
+        with torch.cuda.device(dev):
+            ws, wsb = _lib.sized_workspace(dev, getattr(L, self.ws_query)(ctypes.byref(d), B, S), self.ws_query)
+            _lib.check(getattr(L, entry)(ctypes.byref(d), _lib.ptr(x), B, S, *args, _lib.ptr(ws), wsb, _lib.current_stream(dev)), entry)
+
+    def _saved_table(self, saved):
+        return ctypes.byref(self.saved_cls(**{n: t.data_ptr() for n, t in zip(self.saved, saved)}))
+
+    def forward(self, scalars, x, params):
+        """The training forward on x [B, S, C] (16-byte aligned) -> (out, the saved tensors in ``self.saved`` order)."""
+        keep = []
+        d = self.desc(scalars, params, keep)
+        _lib.check_struct_layouts()
+        B, S, C = x.shape
+        M, dev = B * S, x.device
+        shapes = {"qkv": (M, 3 * C), "lse": (B, scalars["heads"], S), "h1": (M, scalars["inter"]), "a1": (M, scalars["inter"])}   # others: [M, C]
+        out = torch.empty((B, S, C), dtype=torch.bfloat16, device=dev)
+        saved = [torch.empty(shapes.get(n, (M, C)), dtype=torch.float32 if n == "lse" else torch.bfloat16, device=dev) for n in self.saved]
+        self._call(self.fwd, d, x, _lib.ptr(out), self._saved_table(saved))
+        return out, saved
+
+    def backward(self, scalars, x, saved, params, gout, need_x, need):
+        """-> (grad_x or None, the parameter gradients in ``self.params`` order: None where ``need`` is false or the layer has no such
+        parameter)."""
+        keep = []
+        d = self.desc(scalars, params, keep)
+        idx = {n: i for i, n in enumerate(self.params)}
+        ask = list(need)
+        for b, w in self._BIAS_RIDES_ON:   # a bias gradient rides on its weight's launch
+            ask[idx[w]] = ask[idx[w]] or (ask[idx[b]] and params[idx[b]] is not None)
+        g = _lib.aligned(gout.to(torch.bfloat16))
+        grads = [torch.empty(p.shape, dtype=torch.bfloat16, device=x.device) if (a and p is not None) else None for a, p in zip(ask, params)]
+        gx = torch.empty_like(x) if need_x else None
+        gs = self.grads_cls(**{n: (t.data_ptr() if t is not None else None) for n, t in zip(self.params, grads)})
+        self._call(self.bwd, d, x, _lib.ptr(g), self._saved_table(saved), _lib.ptr(gx), ctypes.byref(gs))
+        return gx, [t if n else None for t, n in zip(grads, need)]   # (a weight gradient computed only as its bias's carrier is dropped)
+
+
 def embed_pixels(pixel_values, conv, class_embedding, position_table):
     """InternVisionEmbeddings.forward (modeling_intern_vit.py:82-90) / HF CLIPVisionEmbeddings.forward on a CUDA tensor
     [n, 3, image, image] (bf16 or fp32; other floating dtypes are cast to bf16 as run_encoder does) -> [n, 1 + P, C] bf16.  One
