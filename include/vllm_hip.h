@@ -82,6 +82,9 @@ int vllm_device_info(char *name, int cap);
  * "msda_layer_value_bf16" (round 4; VLLM_MSDA_LAYER_VALUE_BF16): 1 (default) vllm_msda_layer_forward stores the projected value in
  * bf16 when the query set is not the value pyramid (decoder cross-attention: the gather kernel reads bf16 natively; the reference's
  * bf16 module rounds the value to bf16 too) and the streaming value GEMM serves the shape; 0 fp32 value everywhere.
+ * "deform_enc_ffn_slab_rows" (VLLM_DEFORM_ENC_FFN_SLAB_ROWS): rows of the FFN intermediate [B S, d_ffn] that vllm_deform_enc_layer_forward
+ * computes at a time (linear1 + activation, then linear2, slab by slab): 0 (default, the fastest measured) = the whole tensor in one pair
+ * of GEMMs; N > 0 = N rows, which shrinks the workspace to one slab of the intermediate at some cost in time; a negative value is rejected.  vllm_deform_enc_layer_workspace_bytes answers for the current value: query the size after setting it.
  * Environment variables VLLM_MSDA_TILED / VLLM_GEMM_VARIANT / VLLM_ATTN_VARIANT give the initial values.  Returns the
  * previous value or VLLM_EINVAL for an unknown name / value.  (Measured-slower experiments -- MSDA generations 3 and 5, the
  * 4-wave GEMM, the two-row-group attention kernel -- live under tools/experiments/ and are not part of the library.) */
@@ -319,6 +322,58 @@ int vllm_dcnv3_backward_f16(const uint16_t *input, const uint16_t *offset, const
                             int W, int G, int C, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, float offset_scale,
                             uint16_t *grad_input, uint16_t *grad_offset, uint16_t *grad_mask, void *workspace, long workspace_bytes,
                             vllm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * f2b. The whole deformable ENCODER layer around the attention layer above, bf16 modules (inference).
+ *
+ * Replaces the bodies of
+ *   DeformableTransformerEncoderLayer.forward   visionllmv2/model/unipose/modeling_unipose.py:3132-3186 (without channel attention)
+ *   GroundingDinoDeformableLayer.forward        visionllmv2/model/grounding_dino/modeling_ov_grounding_dino_mask_dn.py:1105-1180
+ * i.e.  q = src + pos;  x = norm1(src + self_attn(q, reference_points, src));  out = norm2(x + linear2(act(linear1(x))))
+ * (dropout is the identity at inference).  The launches: [q = src + pos,] the launches of vllm_msda_layer_forward with `src` added in
+ * output_proj's epilogue, LayerNorm, per slab of rows linear1 + activation and linear2 + residual, LayerNorm [+ pos].  Every tensor
+ * between two launches is bf16, as in the bf16 module; sums, statistics and activations are fp32 with one rounding per stored tensor.
+ * `attn.ref_dim` must be 2 (the encoder's reference points), d_model a multiple of 64 up to 512, d_ffn a multiple of 64.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct VllmDeformEncLayerDesc {
+    VllmMsdaLayerDesc attn;            /* ref_dim 2 */
+    int32_t d_ffn, act;                /* act: 0 = ReLU, VLLM_EPI_GELU = erf GELU */
+    float norm1_eps, norm2_eps;
+    const uint16_t *norm1_w, *norm1_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b, *norm2_w, *norm2_b;   /* [C] [C] [d_ffn, C] [d_ffn] [C, d_ffn] [C] [C] [C] */
+} VllmDeformEncLayerDesc;
+unsigned long vllm_deform_enc_layer_desc_sizeof(void);
+/* Bytes of device scratch vllm_deform_enc_layer_forward needs for B images of S tokens under the CURRENT value of the option
+ * "deform_enc_ffn_slab_rows"; host-only; 0 for B S == 0, negative for a refused descriptor or sizes. */
+long vllm_deform_enc_layer_workspace_bytes(const VllmDeformEncLayerDesc *desc, int B, int S);
+long vllm_deform_enc_layer_calls(void);   /* calls of vllm_deform_enc_layer_forward in this process that reached their launches (tests) */
+/* src, out [B, S, C] bf16; pos [B, S, C] bf16 or NULL (no position embedding); reference_points [B, S, L, 2] fp32; padding_mask [B, S]
+ * uint8 (non-zero = padded) or NULL; spatial_shapes [L, 2] / level_start_index [L] device int64.
+ * query_in [B, S, C] or NULL: the attention's query where the caller has it already (the `query_out` of the layer in front) -- else
+ *   the call computes src + pos itself (or uses src, without pos).
+ * query_out [B, S, C] or NULL: receives bf16(out + pos), the next layer's query, bit-identical to adding pos to `out` (needs pos).
+ * `out` may not overlap `src` or `pos`.  One stream, no allocation, no synchronisation.  A refused call (descriptor; NULL or misaligned
+ * operand; short or misaligned workspace: VLLM_EINVAL, reason in vllm_last_error()) has enqueued nothing; B S == 0 returns VLLM_OK. */
+/* Alignment: src, pos, query_in, out, query_out, every weight / bias of the descriptor and workspace 16 bytes; reference_points 8 bytes. */
+int vllm_deform_enc_layer_forward(const VllmDeformEncLayerDesc *desc, const uint16_t *src, const uint16_t *pos, const uint16_t *query_in,
+                                  const float *reference_points, const uint8_t *padding_mask, const int64_t *spatial_shapes,
+                                  const int64_t *level_start_index, int B, int S, uint16_t *out, uint16_t *query_out, void *workspace,
+                                  long workspace_bytes, vllm_stream_t stream);
+/* The kernels of the layer, exposed for the parity tests.
+ * vllm_add_layernorm_bf16: y [rows, C] = LayerNorm_C(x + res) * weight + bias; x, res bf16, the sum and the statistics fp32 (second moment
+ *   about the mean), one rounding.  res NULL: a plain LayerNorm.  y_pos non-NULL (then pos too): y_pos = bf16(bf16(y) + pos), the bits of
+ *   vllm_add_bf16 on the stored y.  Each of x, res, y, pos, y_pos has its own row stride (elements, a multiple of 8, at least C); y may be
+ *   x.  C a multiple of 64 in 64 .. 512.  Nothing is written outside the C columns of a row.
+ * vllm_add_bf16: out[i] = bf16(a[i] + b[i]), i < n (fp32 sum, round to nearest even); any alignment, 16-byte vectors where all three
+ *   pointers are 16-byte aligned.
+ * vllm_gemm_bf16_relu: vllm_gemm_bf16 (layouts, alignment) with the layer's ReLU epilogue y = v < 0 ? 0 : v, v = x W^T + bias (a NaN stays
+ *   a NaN); force_bits carries VLLM_GEMM_FORCE_128 / _256 / _192 / _MF32 only.  Always one workgroup per tile. */
+/* Alignment (vllm_add_layernorm_bf16): every pointer 16 bytes. */
+int vllm_add_layernorm_bf16(const uint16_t *x, int ldx, const uint16_t *res, int ldr, const uint16_t *weight, const uint16_t *bias,
+                            uint16_t *y, int ldy, const uint16_t *pos, int ldp, uint16_t *y_pos, int ldq, long rows, int C, float eps,
+                            vllm_stream_t stream);
+int vllm_add_bf16(const uint16_t *a, const uint16_t *b, uint16_t *out, long n, vllm_stream_t stream);
+int vllm_gemm_bf16_relu(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, int M, int N, int K, int ldx, int ldw,
+                        int ldy, int force_bits, vllm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * f3b. The whole DCNv3 layer, bf16 modules (inference).

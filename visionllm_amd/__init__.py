@@ -7,6 +7,8 @@ Host-side mirror of the reference's operator/module interfaces for that path onl
 * ``intern_vit`` / ``clip_vit`` -- drop-in ``vis_encoder`` modules (same parameter names as the reference).
 * ``bridge``          -- ``pixel_shuffle`` + ``vl_bridge`` projector.
 * ``dist``            -- data-parallel sharding of images and the RCCL all-gather of visual tokens.
+* ``deformable_encoder`` -- ``DeformableTransformerEncoderLayer`` (UniPose) and ``GroundingDinoDeformableLayer`` (HF) mirrors with the
+  one-call native forward, and ``encoder_layers_forward``; the three names are also attributes of this package.
 
 All compute goes through ``libvllm_hip.so`` (hand-written HIP, C ABI in ``include/vllm_hip.h``).  There is NO
 CPU fallback: calling an op without the built extension, or with CPU tensors, raises.
@@ -14,3 +16,14 @@ CPU fallback: calling an op without the built extension, or with CPU tensors, ra
 from ._lib import build, lib, lib_path  # noqa: F401
 
 __version__ = "0.1.0"
+
+_ENCODER_EXPORTS = ("DeformableTransformerEncoderLayer", "GroundingDinoDeformableLayer", "encoder_layers_forward")
+__all__ = ["build", "lib", "lib_path", *_ENCODER_EXPORTS]
+
+
+def __getattr__(name):
+    # resolved on first use: importing the package itself stays free of torch
+    if name in _ENCODER_EXPORTS:
+        from . import deformable_encoder
+        return getattr(deformable_encoder, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -160,6 +160,12 @@ class VllmMsdaLayerGrads(ctypes.Structure):
                                   "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
 
 
+class VllmDeformEncLayerDesc(ctypes.Structure):
+    _fields_ = [("attn", VllmMsdaLayerDesc), ("d_ffn", ctypes.c_int32), ("act", ctypes.c_int32), ("norm1_eps", ctypes.c_float),
+                ("norm2_eps", ctypes.c_float)] + \
+               [(n, _P) for n in ("norm1_w", "norm1_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "norm2_w", "norm2_b")]
+
+
 class VllmDcnv3LayerDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("channels", "group", "kernel_size", "dw_kernel_size", "dilation", "center_feature_scale",
                                               "n_proj")] + \
@@ -228,6 +234,7 @@ def check_struct_layouts():
     assert ctypes.sizeof(VllmMsdaLayerDesc) == L.vllm_msda_layer_desc_sizeof(), "VllmMsdaLayerDesc layout mismatch"
     assert ctypes.sizeof(VllmMsdaLayerGrads) == L.vllm_msda_layer_grads_sizeof(), "VllmMsdaLayerGrads layout mismatch"
     assert ctypes.sizeof(VllmDcnv3LayerDesc) == L.vllm_dcnv3_layer_desc_sizeof(), "VllmDcnv3LayerDesc layout mismatch"
+    assert ctypes.sizeof(VllmDeformEncLayerDesc) == L.vllm_deform_enc_layer_desc_sizeof(), "VllmDeformEncLayerDesc layout mismatch"
     assert ctypes.sizeof(VllmVitDesc) == L.vllm_vit_desc_sizeof(), "VllmVitDesc layout mismatch"
     assert ctypes.sizeof(VllmVitLayer) == L.vllm_vit_layer_sizeof(), "VllmVitLayer layout mismatch"
     assert ctypes.sizeof(VllmBridgeDesc) == L.vllm_bridge_desc_sizeof(), "VllmBridgeDesc layout mismatch"

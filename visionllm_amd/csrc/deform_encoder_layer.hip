@@ -1,0 +1,286 @@
+// The deformable ENCODER LAYER around the deformable-attention layer (msda_layer.hip) for bf16 modules at inference:
+//   query = src + pos -> self_attn(query, reference_points, src) -> src + attn -> norm1 -> linear1 -> act -> linear2 -> + -> norm2
+// Reference: DeformableTransformerEncoderLayer.forward  unipose/modeling_unipose.py:3132-3186;
+//            GroundingDinoDeformableLayer.forward       grounding_dino/modeling_ov_grounding_dino_mask_dn.py:1105-1180.
+//
+// One call, one stream, a caller workspace.  The launches, in order:
+//   add_bf16_kernel        query = src + pos            (only the first layer of a chain: the others get it from the layer in front)
+//   the attention layer    msda_layer_run, whose output_proj adds `src` in its epilogue (EPI_RESIDUAL)
+//   add_layernorm_kernel   norm1, in place
+//   per slab of rows:      linear1 + ReLU / GELU (EPI_RELU / EPI_GELU), linear2 + residual (EPI_RESIDUAL)
+//   add_layernorm_kernel   norm2 -> out, and out + pos -> query_out for the next layer
+// The FFN intermediate [rows, d_ffn] is the largest tensor of the call: with the option "deform_enc_ffn_slab_rows" it exists one slab
+// of rows at a time, so the workspace holds a slab of it and linear2 finds the slab linear1 has just written in the cache.
+#include "common.hpp"
+#include <stdlib.h>
+#include "orchestrate.hpp"
+#include "msda_layer.hpp"
+
+namespace vllm {
+namespace {
+
+__device__ __forceinline__ void unpack8(const uint4_t &q, float *v)
+{
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[2 * e] = bf16lo_to_f32(q[e]); v[2 * e + 1] = bf16hi_to_f32(q[e]); }
+}
+__device__ __forceinline__ uint4_t pack8(const float *v)
+{
+    return (uint4_t){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+}
+
+// y = LayerNorm(x + res) * w + b over rows of C <= 8 G elements; y_pos = bf16(bf16(y) + pos).  G lanes share a row (32: two rows per
+// wave, 64: one) and lane j of the group owns the 16-byte chunk j, so a row is one load per lane whatever C is; lanes behind the row's
+// last chunk carry zeros through the reductions.  A wave walks its rows with a grid stride and asks for the next row's x / res / pos
+// before it reduces the current one (the scheme of rms_bwd_kernel, norm.hip): the reductions of one row run under the loads of the
+// next.  fp32 from the sum to the one rounding of y; the second moment is taken about the mean (norm_bf16_kernel).  x and y may be
+// the same memory: a lane writes the chunk it has read and no other.
+constexpr int ALN_THREADS = 256;
+struct AlnRow { uint4_t x, r, p; };
+
+template <int G>
+__global__ __launch_bounds__(ALN_THREADS) void add_layernorm_kernel(const uint16_t *x, int ldx, const uint16_t *res, int ldr,
+                                                                    const uint16_t *__restrict__ w, const uint16_t *__restrict__ b, uint16_t *y,
+                                                                    int ldy, const uint16_t *pos, int ldp, uint16_t *y_pos, int ldq, long rows,
+                                                                    int C, float eps)
+{
+    constexpr int R = 64 / G;
+    const int lane = threadIdx.x & 63, j = lane % G, sub = lane / G;
+    const long nwaves = (long)gridDim.x * (ALN_THREADS / 64), wave0 = (long)blockIdx.x * (ALN_THREADS / 64) + (threadIdx.x >> 6);
+    const long ngroups = (rows + R - 1) / R;
+    const bool act = j < (C >> 3);
+    const int c0 = j * 8;
+    float gw[8], gb[8];
+    {
+        uint4_t wv = {0u, 0u, 0u, 0u}, bv = {0u, 0u, 0u, 0u};
+        if (act) { wv = *reinterpret_cast<const uint4_t *>(w + c0); bv = *reinterpret_cast<const uint4_t *>(b + c0); }
+        unpack8(wv, gw);
+        unpack8(bv, gb);
+    }
+    auto load = [&](long g) {
+        AlnRow t = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+        const long row = g * R + sub;
+        if (act && row < rows) {
+            t.x = *reinterpret_cast<const uint4_t *>(x + row * ldx + c0);
+            if (res) t.r = *reinterpret_cast<const uint4_t *>(res + row * ldr + c0);
+            if (y_pos) t.p = *reinterpret_cast<const uint4_t *>(pos + row * ldp + c0);
+        }
+        return t;
+    };
+    const float invC = 1.0f / (float)C;
+    long g = wave0;
+    AlnRow cur = load(g);   // (g >= ngroups: row >= rows, nothing is read)
+    for (; g < ngroups; g += nwaves) {
+        const AlnRow nxt = load(g + nwaves);
+        const long row = g * R + sub;
+        float v[8], rr[8];
+        unpack8(cur.x, v);
+        unpack8(cur.r, rr);
+        float s = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { v[e] += rr[e]; s += v[e]; }
+#pragma unroll
+        for (int o = G / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        const float mean = s * invC;
+        float m2 = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { v[e] = act ? v[e] - mean : 0.f; m2 += v[e] * v[e]; }
+#pragma unroll
+        for (int o = G / 2; o > 0; o >>= 1) m2 += __shfl_xor(m2, o);
+        const float rstd = 1.0f / sqrtf(m2 * invC + eps);
+        if (act && row < rows) {
+            float o8[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o8[e] = v[e] * rstd * gw[e] + gb[e];
+            const uint4_t yo = pack8(o8);
+            *reinterpret_cast<uint4_t *>(y + row * ldy + c0) = yo;
+            if (y_pos) {   // from the STORED y: the bits of adding pos to y afterwards
+                float ys[8], pp[8];
+                unpack8(yo, ys);
+                unpack8(cur.p, pp);
+#pragma unroll
+                for (int e = 0; e < 8; ++e) ys[e] += pp[e];
+                *reinterpret_cast<uint4_t *>(y_pos + row * ldq + c0) = pack8(ys);
+            }
+        }
+        cur = nxt;
+    }
+}
+
+// out = bf16(a + b): 16-byte vectors over the first n8 * 8 elements, the rest one by one (n8 = 0 for operands that are not 16-byte aligned)
+__global__ __launch_bounds__(256) void add_bf16_kernel(const uint16_t *__restrict__ a, const uint16_t *__restrict__ b, uint16_t *__restrict__ out,
+                                                       long n8, long n)
+{
+    const long t = (long)blockIdx.x * 256 + threadIdx.x, stride = (long)gridDim.x * 256;
+    for (long i = t; i < n8; i += stride) {
+        float fa[8], fb[8];
+        unpack8(reinterpret_cast<const uint4_t *>(a)[i], fa);
+        unpack8(reinterpret_cast<const uint4_t *>(b)[i], fb);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) fa[e] += fb[e];
+        reinterpret_cast<uint4_t *>(out)[i] = pack8(fa);
+    }
+    for (long k = n8 * 8 + t; k < n; k += stride) out[k] = f32_to_bf16(bf16_to_f32(a[k]) + bf16_to_f32(b[k]));
+}
+
+int add_layernorm_launch(const uint16_t *x, int ldx, const uint16_t *res, int ldr, const uint16_t *w, const uint16_t *b, uint16_t *y, int ldy,
+                         const uint16_t *pos, int ldp, uint16_t *y_pos, int ldq, long rows, int C, float eps, hipStream_t st)
+{
+    const int G = C <= 256 ? 32 : 64;
+    const long ngroups = (rows + 64 / G - 1) / (64 / G), want = (ngroups + 3) / 4, cap = (long)device_cus() * 8;
+    const dim3 grid((unsigned)(want < cap ? want : cap));
+    if (G == 32) VLLM_LAUNCH((add_layernorm_kernel<32>), grid, dim3(ALN_THREADS), 0, st, x, ldx, res, ldr, w, b, y, ldy, pos, ldp, y_pos, ldq, rows, C, eps);
+    else VLLM_LAUNCH((add_layernorm_kernel<64>), grid, dim3(ALN_THREADS), 0, st, x, ldx, res, ldr, w, b, y, ldy, pos, ldp, y_pos, ldq, rows, C, eps);
+    VLLM_CHECK_LAUNCH("add_layernorm_kernel");
+    return VLLM_OK;
+}
+
+int add_launch(const uint16_t *a, const uint16_t *b, uint16_t *out, long n, hipStream_t st)
+{
+    const long n8 = aligned16(a) && aligned16(b) && aligned16(out) ? n / 8 : 0;
+    const long work = n8 > 0 ? n8 : n, want = (work + 255) / 256, cap = (long)device_cus() * 16;
+    VLLM_LAUNCH(add_bf16_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, st, a, b, out, n8, n);
+    VLLM_CHECK_LAUNCH("add_bf16_kernel");
+    return VLLM_OK;
+}
+
+// what vllm_add_layernorm_bf16 and the layer's two norms ask of a row operand: 16-byte aligned base, row stride a multiple of 8 and >= C
+bool row_operand_ok(const void *p, int ld, int C) { return aligned16(p) && ld >= C && ld % 8 == 0; }
+
+// rows of the FFN intermediate per slab; 0 = the whole tensor at once, the default: measured at cfg 4, B = 8 the whole tensor is the
+// fastest of 0 / 65 536 / 16 384 rows (2191 / 2267 / 2360 us per layer, profiles/deform_encoder_layer.txt); a slab height is for
+// callers who want the smaller workspace
+int g_slab_rows = -1;
+constexpr int SLAB_DEFAULT = 0;
+
+struct EncWs {
+    long t0, x1, h, attn, total;   // t0: the query, later linear2's output; x1: src + attn, normalised in place; h: a slab of the intermediate
+    long slab;                     // rows per slab
+};
+EncWs enc_ws(const VllmDeformEncLayerDesc *d, long B, long S)
+{
+    const long R = B * S, C = d->attn.d_model, F = d->d_ffn;
+    EncWs w;
+    // a slab's bytes stay below 2^31 whatever the option says (the GEMMs' 32-bit byte offsets), in whole 256-row tiles
+    const long most = (((1L << 31) - 1) / (F * 2) - 256) & ~255L;
+    const long opt = deform_enc_ffn_slab_rows();
+    w.slab = opt > 0 && opt < R ? opt : R;
+    if (w.slab > most) w.slab = most;
+    Carver cv;
+    w.t0 = cv.take(R * C * 2);
+    w.x1 = cv.take(R * C * 2);
+    w.h = cv.take(w.slab * F * 2);
+    w.attn = cv.take(msda_layer_ws_bytes(&d->attn, (int)B, (int)S, (int)S));
+    w.total = cv.off;
+    return w;
+}
+
+int enc_check_desc(const VllmDeformEncLayerDesc *d)
+{
+    VLLM_REQUIRE(d, "deform_enc_layer: null descriptor");
+    TRY(msda_layer_check_desc(&d->attn));
+    VLLM_REQUIRE(d->attn.ref_dim == 2, "deform_enc_layer: ref_dim=%d, the encoder layer takes 2-d reference points", d->attn.ref_dim);
+    VLLM_REQUIRE(d->attn.d_model <= 512, "deform_enc_layer: d_model=%d above 512 (the LayerNorm kernel's rows)", d->attn.d_model);
+    VLLM_REQUIRE(d->d_ffn > 0 && d->d_ffn % 64 == 0, "deform_enc_layer: d_ffn=%d must be a positive multiple of 64", d->d_ffn);
+    VLLM_REQUIRE(d->act == 0 || d->act == VLLM_EPI_GELU, "deform_enc_layer: unknown act %d (0 = ReLU, VLLM_EPI_GELU = erf GELU)", d->act);
+    VLLM_REQUIRE(d->norm1_eps >= 0.f && d->norm2_eps >= 0.f, "deform_enc_layer: negative eps");
+    VLLM_REQUIRE(d->norm1_w && d->norm1_b && d->fc1_w && d->fc1_b && d->fc2_w && d->fc2_b && d->norm2_w && d->norm2_b && d->attn.value_proj_b &&
+                     d->attn.sampling_offsets_b && d->attn.attention_weights_b && d->attn.output_proj_b,
+                 "deform_enc_layer: missing weights");
+    return VLLM_OK;
+}
+
+long g_calls = 0;
+
+}  // namespace
+
+int deform_enc_ffn_slab_rows()
+{
+    if (g_slab_rows < 0) {
+        const char *e = getenv("VLLM_DEFORM_ENC_FFN_SLAB_ROWS");
+        g_slab_rows = e && atoi(e) >= 0 ? atoi(e) : SLAB_DEFAULT;
+    }
+    return g_slab_rows;
+}
+int deform_enc_ffn_slab_rows_set(int v) { const int old = deform_enc_ffn_slab_rows(); g_slab_rows = v; return old; }
+
+}  // namespace vllm
+
+using namespace vllm;
+
+extern "C" int vllm_add_layernorm_bf16(const uint16_t *x, int ldx, const uint16_t *res, int ldr, const uint16_t *weight, const uint16_t *bias,
+                                       uint16_t *y, int ldy, const uint16_t *pos, int ldp, uint16_t *y_pos, int ldq, long rows, int C, float eps,
+                                       vllm_stream_t stream)
+{
+    VLLM_REQUIRE(rows >= 0 && C >= 64 && C <= 512 && C % 64 == 0, "add_layernorm: rows=%ld C=%d (C a multiple of 64 in 64 .. 512)", rows, C);
+    if (rows == 0) return VLLM_OK;
+    VLLM_REQUIRE(x && weight && bias && y && (!y_pos || pos), "add_layernorm: null pointer");
+    VLLM_REQUIRE(row_operand_ok(x, ldx, C) && row_operand_ok(y, ldy, C) && (!res || row_operand_ok(res, ldr, C)) &&
+                     (!y_pos || (row_operand_ok(pos, ldp, C) && row_operand_ok(y_pos, ldq, C))) && aligned16(weight) && aligned16(bias),
+                 "add_layernorm: misaligned operand (16-byte aligned pointers, row strides multiples of 8 and at least C)");
+    return add_layernorm_launch(x, ldx, res, ldr, weight, bias, y, ldy, y_pos ? pos : nullptr, ldp, y_pos, ldq, rows, C, eps, (hipStream_t)stream);
+}
+
+extern "C" int vllm_add_bf16(const uint16_t *a, const uint16_t *b, uint16_t *out, long n, vllm_stream_t stream)
+{
+    VLLM_REQUIRE(n >= 0, "add_bf16: negative size");
+    if (n == 0) return VLLM_OK;
+    VLLM_REQUIRE(a && b && out, "add_bf16: null pointer");
+    return add_launch(a, b, out, n, (hipStream_t)stream);
+}
+
+extern "C" unsigned long vllm_deform_enc_layer_desc_sizeof(void) { return sizeof(VllmDeformEncLayerDesc); }
+extern "C" long vllm_deform_enc_layer_calls(void) { return g_calls; }
+
+extern "C" long vllm_deform_enc_layer_workspace_bytes(const VllmDeformEncLayerDesc *d, int B, int S)
+{
+    if (enc_check_desc(d) != VLLM_OK) return -1;
+    if (B < 0 || S < 0 || (long)B * S >= (1L << 31)) { set_error("deform_enc_layer: B=%d S=%d (0 <= B S < 2^31)", B, S); return -1; }
+    if ((long)B * S == 0) return 0;
+    return enc_ws(d, B, S).total;
+}
+
+extern "C" int vllm_deform_enc_layer_forward(const VllmDeformEncLayerDesc *d, const uint16_t *src, const uint16_t *pos, const uint16_t *query_in,
+                                             const float *reference_points, const uint8_t *padding_mask, const int64_t *spatial_shapes,
+                                             const int64_t *level_start_index, int B, int S, uint16_t *out, uint16_t *query_out, void *workspace,
+                                             long workspace_bytes, vllm_stream_t stream)
+{
+    TRY(enc_check_desc(d));
+    VLLM_REQUIRE(B >= 0 && S >= 0 && (long)B * S < (1L << 31), "deform_enc_layer: B=%d S=%d (0 <= B S < 2^31)", B, S);
+    if ((long)B * S == 0) return VLLM_OK;
+    VLLM_REQUIRE(src && reference_points && spatial_shapes && level_start_index && out, "deform_enc_layer: null pointer (src / reference_points / spatial_shapes / level_start_index / out)");
+    VLLM_REQUIRE(!query_out || pos, "deform_enc_layer: null pointer (query_out needs pos)");
+    const VllmMsdaLayerDesc &at = d->attn;
+    VLLM_REQUIRE(aligned16(src) && aligned16(pos) && aligned16(query_in) && aligned16(out) && aligned16(query_out) &&
+                     (reinterpret_cast<uintptr_t>(reference_points) & 7u) == 0,
+                 "deform_enc_layer: misaligned src / pos / query_in / out / query_out (16 bytes) or reference_points (8 bytes)");
+    for (const uint16_t *p : {d->norm1_w, d->norm1_b, d->fc1_w, d->fc1_b, d->fc2_w, d->fc2_b, d->norm2_w, d->norm2_b, at.value_proj_w, at.value_proj_b,
+                              at.sampling_offsets_w, at.sampling_offsets_b, at.attention_weights_w, at.attention_weights_b, at.output_proj_w,
+                              at.output_proj_b})
+        VLLM_REQUIRE(aligned16(p), "deform_enc_layer: misaligned weight or bias (16 bytes)");
+    const EncWs w = enc_ws(d, B, S);
+    VLLM_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= w.total,
+                 "deform_enc_layer: workspace too small (%ld < %ld bytes) or misaligned", workspace_bytes, w.total);
+    ++g_calls;
+    hipStream_t st = (hipStream_t)stream;
+    char *ws = (char *)workspace;
+    const long R = (long)B * S;
+    const int C = at.d_model, F = d->d_ffn;
+    uint16_t *t0 = (uint16_t *)(ws + w.t0), *x1 = (uint16_t *)(ws + w.x1), *h = (uint16_t *)(ws + w.h);
+    // 1. the query (modeling_unipose.py:3174 with_pos_embed; ...mask_dn.py:771-772)
+    const uint16_t *query = query_in ? query_in : src;
+    if (!query_in && pos) { TRY(add_launch(src, pos, t0, R * C, st)); query = t0; }
+    // 2. x1 = src + self_attn(query, reference_points, src) (:3174-3176; :1151-1164): the residual goes into output_proj's epilogue
+    TRY(msda_layer_run(&at, query, reference_points, src, padding_mask, spatial_shapes, level_start_index, B, S, S, x1,
+                       msda_layer_bufs(&at, ws + w.attn, B, S, S), nullptr, st, src));
+    // 3. norm1 (:3177; :1165), in place
+    TRY(add_layernorm_launch(x1, C, nullptr, 0, d->norm1_w, d->norm1_b, x1, C, nullptr, 0, nullptr, 0, R, C, d->norm1_eps, st));
+    // 4. / 5. t0 = x1 + linear2(act(linear1(x1))) (:3167-3168; :1167-1174), a slab of rows at a time.  (t0 held the query: the attention has read it.)
+    for (long r0 = 0; r0 < R; r0 += w.slab) {
+        const long m = R - r0 < w.slab ? R - r0 : w.slab;
+        TRY(gemm(st, d->act == 0 ? EPI_RELU : EPI_GELU, x1 + r0 * C, C, d->fc1_w, C, d->fc1_b, h, F, (int)m, F, C));
+        TRY(gemm(st, EPI_RESIDUAL, h, F, d->fc2_w, F, d->fc2_b, t0 + r0 * C, C, (int)m, C, F, nullptr, x1 + r0 * C, C));
+    }
+    // 6. norm2 (:3169; :1175) -> out, and the next layer's query out + pos
+    return add_layernorm_launch(t0, C, nullptr, 0, d->norm2_w, d->norm2_b, out, C, query_out ? pos : nullptr, C, query_out, C, R, C, d->norm2_eps, st);
+}

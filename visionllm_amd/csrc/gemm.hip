@@ -256,7 +256,7 @@ int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
     VLLM_REQUIRE(a.M >= 0 && a.N > 0 && a.K > 0, "gemm: bad dims M=%d N=%d K=%d", a.M, a.N, a.K);
     if (a.M == 0) return VLLM_OK;
     VLLM_REQUIRE((epi >= EPI_BIAS && epi <= EPI_GELU_BWD) || epi == EPI_MSDA || epi == EPI_GELU_SAVE || epi == EPI_RESIDUAL_SAVE ||
-                     epi == EPI_QUICK_GELU_SAVE || epi == EPI_QUICK_GELU_BWD,
+                     epi == EPI_QUICK_GELU_SAVE || epi == EPI_QUICK_GELU_BWD || epi == EPI_RELU,
                  "gemm: unknown epilogue %d", epi);
     VLLM_REQUIRE(a.K % BK == 0, "gemm: K=%d must be a multiple of %d", a.K, BK);
     VLLM_REQUIRE(a.N % 4 == 0, "gemm: N=%d must be a multiple of 4", a.N);
@@ -319,6 +319,7 @@ int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
     case EPI_RESIDUAL_SAVE: L(EPI_RESIDUAL_SAVE); break;
     case EPI_QUICK_GELU_SAVE: L(EPI_QUICK_GELU_SAVE); break;
     case EPI_QUICK_GELU_BWD: L(EPI_QUICK_GELU_BWD); break;
+    case EPI_RELU: L(EPI_RELU); break;
     default: set_error("gemm: unknown epilogue %d", epi); return VLLM_EINVAL;
     }
 #undef L
@@ -344,11 +345,15 @@ static void gemm_force_bits(GemmArgs &a, int epilogue, int accept)
     if (epilogue & VLLM_GEMM_FORCE_4W) a.variant = 3;   // every entry: the launcher refuses it (not built), no entry ignores it
 }
 
+// EPI_RELU is reached through vllm_gemm_bf16_relu and the encoder layer only: as an epilogue word of the public entries it stays unknown
+#define REFUSE_INTERNAL_RELU(epilogue) VLLM_REQUIRE(((epilogue) & 0xff) != EPI_RELU, "gemm: unknown epilogue %d", (epilogue) & 0xff)
+
 extern "C" int vllm_gemm_bf16(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, int M, int N,
                               int K, int ldx, int ldw, int ldy, int epilogue, const uint16_t *scale,
                               const uint16_t *res, int ldr, int P, vllm_stream_t stream)
 {
     VLLM_REQUIRE(X && W && Y, "vllm_gemm_bf16: null pointer");
+    REFUSE_INTERNAL_RELU(epilogue);
     GemmArgs a = gemm_args(X, ldx, W, ldw, bias, Y, ldy, M, N, K);
     a.scale = scale; a.res = res; a.ldr = ldr; a.P = P;
     gemm_force_bits(a, epilogue, FORCE_TILE | VLLM_GEMM_FORCE_MF32 | VLLM_GEMM_FORCE_TILEWISE);
@@ -390,12 +395,24 @@ extern "C" int vllm_gemm_bf16_quick_gelu_bwd(const uint16_t *X, const uint16_t *
     return gemm_bf16_launch(EPI_QUICK_GELU_BWD, a, (hipStream_t)stream);
 }
 
+// The deformable encoder layer's ReLU epilogue for the tests: `force_bits` carries VLLM_GEMM_FORCE_* only (its low byte is not an epilogue).
+extern "C" int vllm_gemm_bf16_relu(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, int M, int N, int K, int ldx,
+                                   int ldw, int ldy, int force_bits, vllm_stream_t stream)
+{
+    VLLM_REQUIRE(X && W && Y, "vllm_gemm_bf16_relu: null pointer");
+    VLLM_REQUIRE((force_bits & 0xff) == 0, "vllm_gemm_bf16_relu: force_bits holds VLLM_GEMM_FORCE_* bits only");
+    GemmArgs a = gemm_args(X, ldx, W, ldw, bias, Y, ldy, M, N, K);
+    gemm_force_bits(a, force_bits, FORCE_TILE | VLLM_GEMM_FORCE_MF32);   // (never persistent: VLLM_GEMM_FORCE_TILEWISE is not read here)
+    return gemm_bf16_launch(EPI_RELU, a, (hipStream_t)stream);
+}
+
 extern "C" int vllm_gemm_bf16_ln(const uint16_t *X, const uint16_t *W, const uint16_t *bias, uint16_t *Y, int M, int N, int K, int ldx,
                                  int ldw, int ldy, int epilogue, const uint16_t *scale, const uint16_t *res, int ldr, float *ln_out,
                                  const float *ln_in, int ln_slots, int ln_rms, float ln_eps, const float *ln_colsum,
                                  const float *ln_bias, vllm_stream_t stream)
 {
     VLLM_REQUIRE(X && W && Y, "vllm_gemm_bf16_ln: null pointer");
+    REFUSE_INTERNAL_RELU(epilogue);
     GemmArgs a = gemm_args(X, ldx, W, ldw, bias, Y, ldy, M, N, K);
     a.scale = scale; a.res = res; a.ldr = ldr;
     a.variant = 0;   // only the 8-phase kernel folds a norm: the process-wide variant override does not apply ...
@@ -420,6 +437,7 @@ extern "C" int vllm_gemm_bf16_sk(const uint16_t *X, const uint16_t *W, const uin
                                  const uint16_t *res, int ldr, int P, void *scratch, long scratch_bytes, vllm_stream_t stream)
 {
     VLLM_REQUIRE(X && W && Y, "vllm_gemm_bf16_sk: null pointer");
+    REFUSE_INTERNAL_RELU(epilogue);
     VLLM_REQUIRE(!scratch || (scratch_bytes >= SK_FLAG_BYTES + SK_SLOT_BYTES && aligned16(scratch)), "vllm_gemm_bf16_sk: scratch workspace too small (%ld < %ld bytes) or misaligned", scratch_bytes, SK_FLAG_BYTES + SK_SLOT_BYTES);
     // the flags are reset in front of every call of THIS entry (a memset node of 4 KB: a call that died half way, or a caller that
     // never zeroed its scratch, must not hand a stale "slot ready" to the next one); the orchestrators reset theirs once per forward

@@ -915,7 +915,7 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256_bf16_kernel<E, 3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
                    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm256_bf16_kernel<E, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
         SETATTR(EPI_BIAS); SETATTR(EPI_GELU); SETATTR(EPI_QUICK_GELU); SETATTR(EPI_RESIDUAL); SETATTR(EPI_EMBED); SETATTR(EPI_F32);
-        SETATTR(EPI_GELU_BWD); SETATTR(EPI_GELU_SAVE); SETATTR(EPI_RESIDUAL_SAVE); SETATTR(EPI_QUICK_GELU_SAVE); SETATTR(EPI_QUICK_GELU_BWD);
+        SETATTR(EPI_GELU_BWD); SETATTR(EPI_GELU_SAVE); SETATTR(EPI_RESIDUAL_SAVE); SETATTR(EPI_QUICK_GELU_SAVE); SETATTR(EPI_QUICK_GELU_BWD); SETATTR(EPI_RELU);
 #undef SETATTR
     }
 #define L(E) do { if (mf32) VLLM_LAUNCH((gemm256_bf16_kernel<E, 4, true>), grid, block, lds, st, a); \
@@ -942,6 +942,7 @@ int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st)
     case EPI_RESIDUAL_SAVE: L(EPI_RESIDUAL_SAVE); break;
     case EPI_QUICK_GELU_SAVE: L(EPI_QUICK_GELU_SAVE); break;
     case EPI_QUICK_GELU_BWD: L(EPI_QUICK_GELU_BWD); break;
+    case EPI_RELU: L(EPI_RELU); break;
     default: set_error("gemm256: unknown epilogue %d", epi); return VLLM_EINVAL;
     }
 #undef L

@@ -72,6 +72,10 @@ __device__ __forceinline__ void epi_value(const GemmArgs &a, int m, int n, const
     if (EPI == EPI_GELU) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+    } else if (EPI == EPI_RELU) {
+        // a comparison, not fmaxf: fmaxf(NaN, 0) is 0, torch.relu(NaN) is NaN
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = v[r] < 0.f ? 0.f : v[r];
     } else if (EPI == EPI_GELU_SAVE) {
         // training forward: EPI_GELU's arithmetic, and the pre-activation leaves too (bf16, row stride ldy) for the backward's gelu'
         uint2_t h;

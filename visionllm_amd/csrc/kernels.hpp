@@ -18,6 +18,7 @@ enum GemmEpilogue : int {
     // internal (layer_train.cpp): EPI_QUICK_GELU that also stores bf16(x W^T + b), the pre-activation, to GemmArgs::pre (EPI_GELU_SAVE's rule:
     // one workgroup per tile without a stream-K tail where the persistent schedule would take EPI_QUICK_GELU, so Y keeps the inference bits)
     EPI_QUICK_GELU_SAVE = 103,
+    EPI_RELU = 105,   // internal (deform_encoder_layer.hip: the FFN's linear1): y = v < 0 ? 0 : v with v = x W^T + b, so a NaN stays a NaN as in torch.relu; tile kernels only, never persistent
     EPI_QUICK_GELU_BWD = 104,   // internal (layer_train.cpp): y = (x W^T) * q'(res[m, n]), q(h) = h sigmoid(1.702 h), res = the saved pre-activation; no bias
     // internal (gemm256p.hip): the instantiation of EPI_RESIDUAL whose residual comes in through the operand ring.  A value of its
     // own and no further template flag, for two reasons: the kernel's name tells the two routes apart in a profile
@@ -116,6 +117,8 @@ long gemm256p_half_launches();
 int msda_layer_value_bf16_set(int v);   // VLLM_MSDA_LAYER_VALUE_BF16 / vllm_set_option("msda_layer_value_bf16")
 int msda_layer_fused();        // VLLM_MSDA_LAYER_FUSED / vllm_set_option("msda_layer_fused")
 int msda_tiled_enabled();      // VLLM_MSDA_TILED / vllm_set_option("msda_tiled")
+int deform_enc_ffn_slab_rows();        // VLLM_DEFORM_ENC_FFN_SLAB_ROWS / vllm_set_option("deform_enc_ffn_slab_rows"): rows of the FFN intermediate per slab, 0 = all
+int deform_enc_ffn_slab_rows_set(int v);
 
 int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st);
 

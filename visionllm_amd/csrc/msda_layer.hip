@@ -203,6 +203,14 @@ int vllm::msda_layer_check_desc(const VllmMsdaLayerDesc *d)
     return VLLM_OK;
 }
 
+long vllm::msda_layer_ws_bytes(const VllmMsdaLayerDesc *d, int B, int Lq, int S) { return layer_ws(d, B, Lq, S).total; }
+MsdaLayerBufs vllm::msda_layer_bufs(const VllmMsdaLayerDesc *d, void *workspace, int B, int Lq, int S)
+{
+    const LayerWs w = layer_ws(d, B, Lq, S);
+    char *ws = (char *)workspace;
+    return {(float *)(ws + w.value), (float *)(ws + w.off), (float *)(ws + w.logit), (float *)(ws + w.opout), (uint16_t *)(ws + w.opout_bf16)};
+}
+
 extern "C" long vllm_msda_layer_workspace_bytes(const VllmMsdaLayerDesc *d, int B, int Lq, int S)
 {
     if (msda_layer_check_desc(d) != VLLM_OK || B < 0 || Lq < 0 || S < 0) return -1;
@@ -235,9 +243,7 @@ extern "C" int vllm_msda_layer_forward(const VllmMsdaLayerDesc *d, const uint16_
     const LayerWs w = layer_ws(d, B, Lq, S);
     VLLM_REQUIRE(workspace && aligned16(workspace) && ws_bytes >= w.total, "msda_layer: workspace too small (%ld < %ld bytes) or misaligned", ws_bytes,
                  w.total);
-    char *ws = (char *)workspace;
-    const MsdaLayerBufs b = {(float *)(ws + w.value), (float *)(ws + w.off), (float *)(ws + w.logit), (float *)(ws + w.opout),
-                             (uint16_t *)(ws + w.opout_bf16)};
+    const MsdaLayerBufs b = msda_layer_bufs(d, workspace, B, Lq, S);
     return msda_layer_run(d, query, ref, input_flatten, padding_mask, shapes, lsi, B, Lq, S, out, b, nullptr, (hipStream_t)stream);
 }
 
@@ -252,7 +258,7 @@ bool vllm::msda_layer_value_may_be_bf16(const VllmMsdaLayerDesc *d, int Lq, int 
 // Every launch of the layer, behind the entries' argument gates (descriptor checked, B, Lq > 0, buffers sized and 16-byte aligned).
 int vllm::msda_layer_run(const VllmMsdaLayerDesc *d, const uint16_t *query, const float *ref, const uint16_t *input_flatten,
                          const uint8_t *padding_mask, const int64_t *shapes, const int64_t *lsi, int B, int Lq, int S, uint16_t *out,
-                         const MsdaLayerBufs &b, int *value_is_bf16, hipStream_t st)
+                         const MsdaLayerBufs &b, int *value_is_bf16, hipStream_t st, const uint16_t *residual)
 {
     VLLM_REQUIRE(S > 0, "msda_layer: empty value");
     VLLM_REQUIRE(query && ref && input_flatten && shapes && lsi && out, "msda_layer: null pointer");
@@ -308,6 +314,8 @@ int vllm::msda_layer_run(const VllmMsdaLayerDesc *d, const uint16_t *query, cons
     // unknown geometry it is enqueued and tests the device-side predicate itself.
     if (!v16 && !(where && (d->geometry == VLLM_GEO_PYRAMID || d->geometry == VLLM_GEO_NESTED)))
         TRY(cvt_launch(opout, opb, (long)B * Lq * C, st, where ? shapes : nullptr, L, Lq));
+    if (residual) TRY(gemm(st, EPI_RESIDUAL, opb, C, d->output_proj_w, C, d->output_proj_b, out, C, B * Lq, C, C, nullptr, residual, C));
+    else
     TRY(gemm(st, EPI_BIAS, opb, C, d->output_proj_w, C, d->output_proj_b, out, C, B * Lq, C, C));
     prof_mark(PT_END, st);
     return VLLM_OK;

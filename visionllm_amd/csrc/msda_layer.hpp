@@ -16,10 +16,15 @@ struct MsdaLayerBufs {
 };
 
 int msda_layer_check_desc(const VllmMsdaLayerDesc *d);
+// vllm_msda_layer_forward's workspace for a checked descriptor: its size, and its pieces in `workspace` (16-byte aligned)
+long msda_layer_ws_bytes(const VllmMsdaLayerDesc *d, int B, int Lq, int S);
+MsdaLayerBufs msda_layer_bufs(const VllmMsdaLayerDesc *d, void *workspace, int B, int Lq, int S);
 // The forward pass behind both entries: every launch, in order.  *value_is_bf16 (host memory, may be null) tells how the value was stored.
+// `residual` [B*Lq, C] bf16 (16-byte aligned, dense rows; null = none): out = residual + output_proj(...), added in output_proj's epilogue
+// (deform_encoder_layer.hip); without it the launches and the bits are what they were.
 int msda_layer_run(const VllmMsdaLayerDesc *d, const uint16_t *query, const float *ref, const uint16_t *input_flatten,
                    const uint8_t *padding_mask, const int64_t *shapes, const int64_t *lsi, int B, int Lq, int S, uint16_t *out,
-                   const MsdaLayerBufs &b, int *value_is_bf16, hipStream_t st);
+                   const MsdaLayerBufs &b, int *value_is_bf16, hipStream_t st, const uint16_t *residual = nullptr);
 // true where msda_layer_run MAY store the value as bf16 for these sizes (the sizes' part of its decision)
 bool msda_layer_value_may_be_bf16(const VllmMsdaLayerDesc *d, int Lq, int S);
 

@@ -99,6 +99,10 @@ extern "C" int vllm_set_option(const char *name, int value)
     if (!strcmp(name, "gemm_res_ring")) return vllm::gemm_res_ring_set(value);
     if (!strcmp(name, "msda_layer_value_bf16")) return vllm::msda_layer_value_bf16_set(value);
     if (!strcmp(name, "gemm_skinny")) return vllm::gemm_skinny_set(value);
+    if (!strcmp(name, "deform_enc_ffn_slab_rows")) {
+        if (value < 0) { vllm::set_error("deform_enc_ffn_slab_rows must be >= 0 (got %d)", value); return VLLM_EINVAL; }
+        return vllm::deform_enc_ffn_slab_rows_set(value);
+    }
     if (!strcmp(name, "msda_layer_fused")) { const int old = vllm::msda_layer_fused(); vllm::g_layer_fused = value != 0; return old; }
     if (!strcmp(name, "gemm_direct_store")) { const int old = vllm::gemm_direct_store(); vllm::g_gemm_direct = (value < 0 || value > 2) ? 2 : value; return old; }
     if (!strcmp(name, "attn_variant")) { const int old = vllm::attn_variant(); vllm::g_attn_variant = value & 0xffff; return old; }
