@@ -276,12 +276,24 @@ def test_backward_windowed_kernel_agrees_with_gather_kernel():
 
 @pytest.mark.parametrize("scale", [1.0, 1.7])
 def test_locations_on_and_next_to_integers_land_in_the_same_cell_in_every_kernel(scale):
+    _on_and_next_to_integers(scale, 32)
+
+
+@pytest.mark.parametrize("C", [16, 64, 20, 7])
+@pytest.mark.parametrize("scale", [1.0, 1.7])
+def test_locations_on_and_next_to_integers_other_group_channels(scale, C):
+    """the same construction and bounds over the backward kernels the other group channels select (four channels per lane with 16, 64 and
+    20 -- five lanes, no power of two --, the scalar kernel with 7), under both dcnv3_bwd_tiled values; the tiled forward takes 16 too"""
+    _on_and_next_to_integers(scale, C)
+
+
+def _on_and_next_to_integers(scale, C):
     """a location within an ulp of an integer must fall into the SAME cell in the gather backward, the windowed matrix-core
     backward and the oracle (the reference's operation order: every product rounded on its own, `dcn_loc`): grad_offset is
     discontinuous there, so one fused multiply-add in one kernel shows as an O(1) difference.  Offsets are constructed so that
     p0 + (i d + offset) scale is an integer, or its fp32 neighbour above / below, for every point."""
     from visionllm_amd import _lib
-    N, H, W, G, C, k = 1, 24, 40, 2, 32, 3
+    N, H, W, G, k = 1, 24, 40, 2, 3
     rng = np.random.default_rng(5)
     inp = rng.standard_normal((N, H, W, G * C)).astype(np.float32)
     msk = rng.random((N, H, W, G * k * k)).astype(np.float32)

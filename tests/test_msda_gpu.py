@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+import lattice_inputs as LI
 from conftest import load_golden
 from msda_inputs import CFG4_SHAPES, make_inputs
 from oracle import msda as O
@@ -417,7 +418,7 @@ def test_backward_f32_vectorised_vs_oracle(D, M, P):
     rv, rl, rw = O.backward(g["value"].astype(np.float64), g["shapes"], g["lsi"], g["loc"].astype(np.float64),
                             g["attw"].astype(np.float64), go.astype(np.float64))
     # d/dloc is discontinuous at exact pixel borders, which the stress fixture contains (0.0 / 0.5 / 1.0): the fp32 and
-    # fp64 evaluations may pick different sides there -> compare away from those points
+    # fp64 evaluations may pick different sides there -> the fp64 oracle is the reference away from those points only
     sel = np.ones(g["loc"].shape[:-1], dtype=bool)
     for l, (H, W) in enumerate(shapes):
         fy = g["loc"][:, :, :, l, :, 1].astype(np.float64) * H - 0.5
@@ -425,6 +426,12 @@ def test_backward_f32_vectorised_vs_oracle(D, M, P):
         sel[:, :, :, l] &= ~((np.abs(fy - np.round(fy)) < 1e-4) | (np.abs(fx - np.round(fx)) < 1e-4))
     np.testing.assert_allclose(gw.cpu().numpy()[sel], rw[sel], rtol=1e-4, atol=1e-4)
     np.testing.assert_allclose(gl.cpu().numpy()[sel], rl[sel], rtol=2e-3, atol=2e-3)
+    # the border points: against the one-sided derivative of the cell the index-exact contract puts them in (lattice_inputs.py), at
+    # the same bounds -- no point is skipped
+    fl, fw, _ = LI.fixed_cell_point_gradients(g["value"], shapes, g["lsi"], g["loc"], g["attw"], go, ~sel)
+    assert (~sel).sum() > 0
+    np.testing.assert_allclose(gw.cpu().numpy()[~sel], fw[~sel], **LI.GW_TOL)
+    np.testing.assert_allclose(gl.cpu().numpy()[~sel], fl[~sel], **LI.GL_TOL)
     # grad_value: PER ELEMENT against the fp32 oracle (same integer parts by the index-exact contract, so no border flips):
     # only the order of the fp32 sums differs -> 2^-18 of the summed |terms| (oracle on |grad_out|; the weights are >= 0)
     rv32, _, _ = O.backward(g["value"], g["shapes"], g["lsi"], g["loc"], g["attw"], go)
@@ -503,6 +510,11 @@ def test_backward_f32_encoder_shape_tiled_vs_plain_vs_oracle(shapes, B, M, sprea
         fy = np.nan_to_num(loc[:, :, :, l, :, 1].astype(np.float64)) * H - 0.5
         fx = np.nan_to_num(loc[:, :, :, l, :, 0].astype(np.float64)) * W - 0.5
         sel[:, :, :, l] &= ~((np.abs(fy - np.round(fy)) < 1e-4) | (np.abs(fx - np.round(fx)) < 1e-4))
+    # the finite points within 1e-4 px of a border: the fixed-cell reference (lattice_inputs.py) at the same bounds; the non-finite
+    # ones: exact zeros -- no point is skipped
+    finite = np.isfinite(loc).all(-1)
+    drop = finite & ~sel
+    fl, fw, _ = LI.fixed_cell_point_gradients(g["value"], shapes, g["lsi"], loc, g["attw"], go, drop)
     old = _lib.set_option("msda_tiled", 1)
     try:
         res = {}
@@ -514,6 +526,9 @@ def test_backward_f32_encoder_shape_tiled_vs_plain_vs_oracle(shapes, B, M, sprea
             assert np.isfinite(res[mode][0]).all() and np.isfinite(res[mode][1]).all() and np.isfinite(res[mode][2]).all()
             np.testing.assert_allclose(res[mode][2][sel], rw[sel], rtol=1e-4, atol=1e-4)
             np.testing.assert_allclose(res[mode][1][sel], rl[sel], rtol=2e-3, atol=2e-3)
+            np.testing.assert_allclose(res[mode][2][drop], fw[drop], **LI.GW_TOL)
+            np.testing.assert_allclose(res[mode][1][drop], fl[drop], **LI.GL_TOL)
+            assert (res[mode][1][~finite] == 0).all() and (res[mode][2][~finite] == 0).all()
             assert (np.abs(res[mode][0] - rv32) <= 2.0 ** -18 * mag + 1e-7).all(), mode   # per element vs the fp32 oracle
         # the windowed kernel sums over the channels first (four dot products per point, then the bilinear weights), the plain one
         # weights per channel and sums then: the per-point gradients agree to fp32 rounding of sums of ~32 terms, grad_value differs
