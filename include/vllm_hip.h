@@ -376,6 +376,69 @@ int vllm_gemm_bf16_relu(const uint16_t *X, const uint16_t *W, const uint16_t *bi
                         int ldy, int force_bits, vllm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * f2c. The whole deformable DECODER layer, bf16 modules (inference).
+ *
+ * Replaces the bodies of
+ *   DeformableTransformerDecoderLayer.forward   visionllmv2/model/unipose/modeling_unipose.py:3250-3323
+ *   GroundingDinoDecoderLayer.forward           visionllmv2/model/grounding_dino/modeling_ov_grounding_dino_mask_dn.py:1332-1407
+ * i.e., batch-first and with dropout the identity,
+ *   1. q = tgt + pos;  x = LN_sa(tgt + out_proj(MHA(q Wq, q Wk, tgt Wv, self_attn_mask)))                       (has_self_attn)
+ *   2. x = LN_text(x + out_proj_t(MHA((x + pos) Wq, text Wk, text Wv, text_key_padding_mask)))                  (has_text_attn)
+ *   3. x = LN_ca(x + cross_attn(x + pos, reference_points, memory, ...))          (the attention layer of section f2, ref_dim 2 or 4)
+ *   4. out = LN_ffn(x + fc2(act(fc1(x))))
+ * The launches: vllm_add_bf16 forms tgt + pos once, every later x + pos is the y_pos output of the vllm_add_layernorm_bf16 in front of its
+ * reader; per attention block two projection GEMMs on pointer-offset slices of the module's own in_proj parameter (self: N = 2C on q
+ * and N = C on tgt; text: N = C on x + pos and N = 2C on memory_text), vllm_mha_fwd_bf16 on column slices of their outputs, out_proj with
+ * the residual in its epilogue, LayerNorm; the launches of vllm_msda_layer_forward with the residual in output_proj's epilogue,
+ * LayerNorm; fc1 + ReLU / GELU, fc2 + residual, LayerNorm.  No weight is copied or repacked.  Every tensor between two launches is
+ * bf16, as in the bf16 module; sums, scores, statistics and activations are fp32 with one rounding per stored tensor.
+ * d_model a multiple of 64 up to 512, d_ffn a multiple of 64, d_model / n_heads_sa 32 or 64.  No runtime option.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct VllmDeformDecLayerDesc {
+    VllmMsdaLayerDesc cross_attn;          /* ref_dim 2 or 4, use_4d_normalizer as given */
+    int32_t d_ffn, act;                    /* act: 0 = ReLU, VLLM_EPI_GELU = erf GELU */
+    int32_t n_heads_sa;                    /* heads of self_attn and of the text attention */
+    int32_t has_self_attn, has_text_attn;  /* UniPose: 0 after rm_self_attn_modules() / without use_text_cross_attention */
+    float   sa_norm_eps, text_norm_eps, ca_norm_eps, ffn_norm_eps;
+    const uint16_t *sa_in_proj_w, *sa_in_proj_b, *sa_out_proj_w, *sa_out_proj_b, *sa_norm_w, *sa_norm_b;         /* [3C, C] [3C] [C, C] [C] [C] [C] */
+    const uint16_t *text_in_proj_w, *text_in_proj_b, *text_out_proj_w, *text_out_proj_b, *text_norm_w, *text_norm_b;
+    const uint16_t *ca_norm_w, *ca_norm_b, *fc1_w, *fc1_b, *fc2_w, *fc2_b, *ffn_norm_w, *ffn_norm_b;   /* [C] [C] [d_ffn, C] [d_ffn] [C, d_ffn] [C] [C] [C] */
+} VllmDeformDecLayerDesc;
+unsigned long vllm_deform_dec_layer_desc_sizeof(void);
+/* Bytes of device scratch vllm_deform_dec_layer_forward needs for B images of Lq queries, Lt text tokens and S memory tokens; host-only;
+ * 0 for B Lq == 0, negative for a refused descriptor or sizes. */
+long vllm_deform_dec_layer_workspace_bytes(const VllmDeformDecLayerDesc *desc, int B, int Lq, int Lt, int S);
+long vllm_deform_dec_layer_calls(void);   /* calls of vllm_deform_dec_layer_forward in this process that reached their launches (tests) */
+/* tgt, out [B, Lq, C] bf16; query_pos [B, Lq, C] bf16 or NULL; reference_points [B, Lq, L, ref_dim] fp32; self_attn_mask [Lq, Lq] uint8
+ * (non-zero = may NOT attend) or NULL; memory_text [B, Lt, C] bf16 (read with has_text_attn only); text_key_padding_mask [B, Lt] uint8
+ * (non-zero = ignore this token) or NULL; memory [B, S, C] bf16; memory_padding_mask [B, S] uint8 (non-zero = padded) or NULL;
+ * spatial_shapes [L, 2] / level_start_index [L] device int64.  A query row whose keys are all masked is NaN, as in the modules.
+ * One stream, no allocation, no synchronisation.  A refused call (descriptor; d_model not a multiple of 64 in 64 .. 512; d_ffn not a
+ * multiple of 64; head dim not 32 / 64; NULL or misaligned operand; `out` overlapping tgt / query_pos / memory_text / memory; short or
+ * misaligned workspace: VLLM_EINVAL, reason in vllm_last_error()) has enqueued nothing; B Lq == 0 returns VLLM_OK. */
+/* Alignment: tgt, query_pos, memory_text, memory, out, every weight / bias of the descriptor and workspace 16 bytes; reference_points
+ * 8 bytes, 16 with ref_dim 4; the masks: element alignment. */
+int vllm_deform_dec_layer_forward(const VllmDeformDecLayerDesc *desc, const uint16_t *tgt, const uint16_t *query_pos,
+                                  const float *reference_points, const uint8_t *self_attn_mask, const uint16_t *memory_text,
+                                  const uint8_t *text_key_padding_mask, const uint16_t *memory, const uint8_t *memory_padding_mask,
+                                  const int64_t *spatial_shapes, const int64_t *level_start_index, int B, int Lq, int Lt, int S,
+                                  uint16_t *out, void *workspace, long workspace_bytes, vllm_stream_t stream);
+/* The attention kernel of blocks 1 and 2, exposed for the parity tests: masked multi-head attention for short sequences.
+ * Head h of token (b, i) of an operand is D contiguous bf16 at ptr + b * batch_stride + i * ld + h * D (strides in elements), so q, k
+ * and v are read in place from column slices of packed projection outputs.  D 32 or 64; Lq, Lk >= 1, neither bounded by a tile; H >= 1.
+ *   out[b, i, h, :] = softmax_j(softmax_scale * q . k_j, masked keys at -inf) V
+ * attn_mask [Lq, Lk] (non-zero = may NOT attend) or NULL; key_padding_mask [B, Lk] (non-zero = ignore this key) or NULL.  Scores,
+ * softmax and accumulation fp32, P rounded to bf16 before P V, one rounding of the result.  A row with EVERY key masked is NaN in all D
+ * outputs of that head (softmax of an all -inf row, as in nn.MultiheadAttention).  Nothing is written outside the H D columns of an
+ * output row.  No atomics: the same bits on every run.  A refused call (D; a NULL operand; a misaligned pointer or stride; a row stride
+ * below H D: VLLM_EINVAL, reason in vllm_last_error()) has enqueued nothing; B Lq == 0 returns VLLM_OK. */
+/* Alignment: q, k, v, out 16 bytes, their row and batch strides multiples of 8 elements; the masks: element alignment. */
+int vllm_mha_fwd_bf16(const uint16_t *q, long q_batch_stride, int ldq, const uint16_t *k, long k_batch_stride, int ldk,
+                      const uint16_t *v, long v_batch_stride, int ldv, uint16_t *out, long o_batch_stride, int ldo,
+                      const uint8_t *attn_mask, const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D,
+                      float softmax_scale, vllm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * f3b. The whole DCNv3 layer, bf16 modules (inference).
  *
  * Replaces the body of DCNv3.forward, visionllmv2/model/ops_dcnv3/modules/dcnv3.py:313-351, with the CenterFeatureScaleModule

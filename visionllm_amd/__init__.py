@@ -9,6 +9,8 @@ Host-side mirror of the reference's operator/module interfaces for that path onl
 * ``dist``            -- data-parallel sharding of images and the RCCL all-gather of visual tokens.
 * ``deformable_encoder`` -- ``DeformableTransformerEncoderLayer`` (UniPose) and ``GroundingDinoDeformableLayer`` (HF) mirrors with the
   one-call native forward, and ``encoder_layers_forward``; the three names are also attributes of this package.
+* ``deformable_decoder`` -- ``DeformableTransformerDecoderLayer`` (UniPose) and ``GroundingDinoDecoderLayer`` (HF) mirrors with the
+  one-call native forward; the two names are also attributes of this package.
 
 All compute goes through ``libvllm_hip.so`` (hand-written HIP, C ABI in ``include/vllm_hip.h``).  There is NO
 CPU fallback: calling an op without the built extension, or with CPU tensors, raises.
@@ -18,7 +20,8 @@ from ._lib import build, lib, lib_path  # noqa: F401
 __version__ = "0.1.0"
 
 _ENCODER_EXPORTS = ("DeformableTransformerEncoderLayer", "GroundingDinoDeformableLayer", "encoder_layers_forward")
-__all__ = ["build", "lib", "lib_path", *_ENCODER_EXPORTS]
+_DECODER_EXPORTS = ("DeformableTransformerDecoderLayer", "GroundingDinoDecoderLayer")
+__all__ = ["build", "lib", "lib_path", *_ENCODER_EXPORTS, *_DECODER_EXPORTS]
 
 
 def __getattr__(name):
@@ -26,4 +29,7 @@ def __getattr__(name):
     if name in _ENCODER_EXPORTS:
         from . import deformable_encoder
         return getattr(deformable_encoder, name)
+    if name in _DECODER_EXPORTS:
+        from . import deformable_decoder
+        return getattr(deformable_decoder, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -166,6 +166,15 @@ class VllmDeformEncLayerDesc(ctypes.Structure):
                [(n, _P) for n in ("norm1_w", "norm1_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "norm2_w", "norm2_b")]
 
 
+class VllmDeformDecLayerDesc(ctypes.Structure):
+    _fields_ = [("cross_attn", VllmMsdaLayerDesc)] + \
+               [(n, ctypes.c_int32) for n in ("d_ffn", "act", "n_heads_sa", "has_self_attn", "has_text_attn")] + \
+               [(n, ctypes.c_float) for n in ("sa_norm_eps", "text_norm_eps", "ca_norm_eps", "ffn_norm_eps")] + \
+               [(n, _P) for n in ("sa_in_proj_w", "sa_in_proj_b", "sa_out_proj_w", "sa_out_proj_b", "sa_norm_w", "sa_norm_b",
+                                  "text_in_proj_w", "text_in_proj_b", "text_out_proj_w", "text_out_proj_b", "text_norm_w", "text_norm_b",
+                                  "ca_norm_w", "ca_norm_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ffn_norm_w", "ffn_norm_b")]
+
+
 class VllmDcnv3LayerDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("channels", "group", "kernel_size", "dw_kernel_size", "dilation", "center_feature_scale",
                                               "n_proj")] + \
@@ -235,6 +244,7 @@ def check_struct_layouts():
     assert ctypes.sizeof(VllmMsdaLayerGrads) == L.vllm_msda_layer_grads_sizeof(), "VllmMsdaLayerGrads layout mismatch"
     assert ctypes.sizeof(VllmDcnv3LayerDesc) == L.vllm_dcnv3_layer_desc_sizeof(), "VllmDcnv3LayerDesc layout mismatch"
     assert ctypes.sizeof(VllmDeformEncLayerDesc) == L.vllm_deform_enc_layer_desc_sizeof(), "VllmDeformEncLayerDesc layout mismatch"
+    assert ctypes.sizeof(VllmDeformDecLayerDesc) == L.vllm_deform_dec_layer_desc_sizeof(), "VllmDeformDecLayerDesc layout mismatch"
     assert ctypes.sizeof(VllmVitDesc) == L.vllm_vit_desc_sizeof(), "VllmVitDesc layout mismatch"
     assert ctypes.sizeof(VllmVitLayer) == L.vllm_vit_layer_sizeof(), "VllmVitLayer layout mismatch"
     assert ctypes.sizeof(VllmBridgeDesc) == L.vllm_bridge_desc_sizeof(), "VllmBridgeDesc layout mismatch"

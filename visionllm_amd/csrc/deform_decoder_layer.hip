@@ -1,0 +1,195 @@
+// The deformable DECODER LAYER of the detection and pose heads for bf16 modules at inference, as one call:
+//   1. q = tgt + pos;  x = LN_sa(tgt + out_proj(MHA(q Wq, q Wk, tgt Wv, self_attn_mask)))
+//   2. x = LN_text(x + out_proj_t(MHA((x + pos) Wq, text Wk, text Wv, text_key_padding_mask)))
+//   3. x = LN_ca(x + cross_attn(x + pos, reference_points, memory, ...))
+//   4. out = LN_ffn(x + fc2(act(fc1(x))))
+// Reference: DeformableTransformerDecoderLayer.forward  unipose/modeling_unipose.py:3250-3323;
+//            GroundingDinoDecoderLayer.forward          grounding_dino/modeling_ov_grounding_dino_mask_dn.py:1332-1407.
+//
+// One call, one stream, a caller workspace.  The launches, in order (blocks 1 and 2 only where the descriptor has them):
+//   vllm_add_bf16            xp = tgt + pos, once: every later `x + pos` is the y_pos output of the LayerNorm in front of its reader
+//   1. GEMM N = 2C on q with in_proj_w[0:2C] -> [q | k];  GEMM N = C on tgt with in_proj_w[2C:3C] -> v;  mha (mha.hip) on the slices;
+//      out_proj with `tgt` added in its epilogue (EPI_RESIDUAL);  add_layernorm in place, y_pos -> xp
+//   2. GEMM N = C on xp with in_proj_w[0:C] -> q;  GEMM N = 2C on memory_text with in_proj_w[C:3C] -> [k | v];  mha;  out_proj + residual;
+//      add_layernorm in place, y_pos -> xp
+//   3. the attention layer (msda_layer_run), whose output_proj adds x in its epilogue;  add_layernorm in place
+//   4. fc1 + ReLU / GELU (EPI_RELU / EPI_GELU);  fc2 + residual;  add_layernorm -> out
+// Weight slices are pointer offsets into the module's own in_proj parameter: nothing is copied or repacked per call.
+#include "common.hpp"
+#include "orchestrate.hpp"
+#include "msda_layer.hpp"
+
+namespace vllm {
+namespace {
+
+struct DecWs {
+    long xp, a, b, qk, v, ctx, tkv, h, attn, total;   // xp: x + pos; a, b: the running x, ping-pong; qk [R, 2C]; v [R, C] (block 2: its q);
+};                                                    // ctx [R, C]; tkv [B Lt, 2C]; h [R, d_ffn]; attn: the attention layer's own
+DecWs dec_ws(const VllmDeformDecLayerDesc *d, long B, long Lq, long Lt, long S)
+{
+    const long R = B * Lq, C = d->cross_attn.d_model, F = d->d_ffn;
+    const bool mha = d->has_self_attn || d->has_text_attn;
+    DecWs w;
+    Carver cv;
+    w.xp = cv.take(R * C * 2);
+    w.a = cv.take(R * C * 2);
+    w.b = cv.take(R * C * 2);
+    w.qk = cv.take(d->has_self_attn ? R * 2 * C * 2 : 0);
+    w.v = cv.take(mha ? R * C * 2 : 0);
+    w.ctx = cv.take(mha ? R * C * 2 : 0);
+    w.tkv = cv.take(d->has_text_attn ? B * Lt * 2 * C * 2 : 0);
+    w.h = cv.take(R * F * 2);
+    w.attn = cv.take(msda_layer_ws_bytes(&d->cross_attn, (int)B, (int)Lq, (int)S));
+    w.total = cv.off;
+    return w;
+}
+
+int dec_check_desc(const VllmDeformDecLayerDesc *d)
+{
+    VLLM_REQUIRE(d, "deform_dec_layer: null descriptor");
+    TRY(msda_layer_check_desc(&d->cross_attn));
+    const VllmMsdaLayerDesc &at = d->cross_attn;
+    const int C = at.d_model;
+    VLLM_REQUIRE(C >= 64 && C <= 512 && C % 64 == 0, "deform_dec_layer: d_model=%d must be a multiple of 64 in 64 .. 512 (the LayerNorm kernel's rows)", C);
+    VLLM_REQUIRE(d->d_ffn > 0 && d->d_ffn % 64 == 0, "deform_dec_layer: d_ffn=%d must be a positive multiple of 64", d->d_ffn);
+    VLLM_REQUIRE(d->act == 0 || d->act == VLLM_EPI_GELU, "deform_dec_layer: unknown act %d (0 = ReLU, VLLM_EPI_GELU = erf GELU)", d->act);
+    if (d->has_self_attn || d->has_text_attn)
+        VLLM_REQUIRE(d->n_heads_sa >= 1 && C % d->n_heads_sa == 0 && (C / d->n_heads_sa == 32 || C / d->n_heads_sa == 64),
+                     "deform_dec_layer: n_heads_sa=%d with d_model=%d (head dim 32 or 64)", d->n_heads_sa, C);
+    VLLM_REQUIRE(d->sa_norm_eps >= 0.f && d->text_norm_eps >= 0.f && d->ca_norm_eps >= 0.f && d->ffn_norm_eps >= 0.f, "deform_dec_layer: negative eps");
+    VLLM_REQUIRE(!d->has_self_attn || (d->sa_in_proj_w && d->sa_in_proj_b && d->sa_out_proj_w && d->sa_out_proj_b && d->sa_norm_w && d->sa_norm_b),
+                 "deform_dec_layer: missing weights (self-attention)");
+    VLLM_REQUIRE(!d->has_text_attn || (d->text_in_proj_w && d->text_in_proj_b && d->text_out_proj_w && d->text_out_proj_b && d->text_norm_w && d->text_norm_b),
+                 "deform_dec_layer: missing weights (text attention)");
+    VLLM_REQUIRE(d->ca_norm_w && d->ca_norm_b && d->fc1_w && d->fc1_b && d->fc2_w && d->fc2_b && d->ffn_norm_w && d->ffn_norm_b && at.value_proj_b &&
+                     at.sampling_offsets_b && at.attention_weights_b && at.output_proj_b,
+                 "deform_dec_layer: missing weights");
+    return VLLM_OK;
+}
+
+int dec_check_sizes(const VllmDeformDecLayerDesc *d, int B, int Lq, int Lt, int S)
+{
+    VLLM_REQUIRE(B >= 0 && Lq >= 0 && Lt >= 0 && S >= 0 && (long)B * Lq < (1L << 31) && (long)B * S < (1L << 31) && (long)B * Lt < (1L << 31),
+                 "deform_dec_layer: B=%d Lq=%d Lt=%d S=%d (non-negative, B Lq, B Lt and B S below 2^31)", B, Lq, Lt, S);
+    // (the GEMMs address an operand with 32-bit byte offsets)
+    VLLM_REQUIRE((long)B * Lq * (d->d_ffn > 2 * d->cross_attn.d_model ? d->d_ffn : 2 * d->cross_attn.d_model) * 2 < (1L << 31),
+                 "deform_dec_layer: B Lq=%ld rows of the widest intermediate reach 2^31 bytes", (long)B * Lq);
+    VLLM_REQUIRE(!d->has_text_attn || (long)B * Lt * 2 * d->cross_attn.d_model * 2 < (1L << 31),
+                 "deform_dec_layer: B Lt=%ld rows of the text's [k | v] reach 2^31 bytes", (long)B * Lt);
+    return VLLM_OK;
+}
+
+bool overlaps(const void *a, long abytes, const void *b, long bbytes)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
+}
+
+long g_calls = 0;
+
+}  // namespace
+}  // namespace vllm
+
+using namespace vllm;
+
+extern "C" unsigned long vllm_deform_dec_layer_desc_sizeof(void) { return sizeof(VllmDeformDecLayerDesc); }
+extern "C" long vllm_deform_dec_layer_calls(void) { return g_calls; }
+
+extern "C" long vllm_deform_dec_layer_workspace_bytes(const VllmDeformDecLayerDesc *d, int B, int Lq, int Lt, int S)
+{
+    if (dec_check_desc(d) != VLLM_OK || dec_check_sizes(d, B, Lq, Lt, S) != VLLM_OK) return -1;
+    if ((long)B * Lq == 0) return 0;
+    return dec_ws(d, B, Lq, Lt, S).total;
+}
+
+extern "C" int vllm_deform_dec_layer_forward(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, const uint16_t *query_pos,
+                                             const float *reference_points, const uint8_t *self_attn_mask, const uint16_t *memory_text,
+                                             const uint8_t *text_key_padding_mask, const uint16_t *memory, const uint8_t *memory_padding_mask,
+                                             const int64_t *spatial_shapes, const int64_t *level_start_index, int B, int Lq, int Lt, int S,
+                                             uint16_t *out, void *workspace, long workspace_bytes, vllm_stream_t stream)
+{
+    TRY(dec_check_desc(d));
+    TRY(dec_check_sizes(d, B, Lq, Lt, S));
+    if ((long)B * Lq == 0) return VLLM_OK;
+    const VllmMsdaLayerDesc &at = d->cross_attn;
+    const bool sa = d->has_self_attn != 0, ta = d->has_text_attn != 0;
+    VLLM_REQUIRE(S > 0 && (!ta || Lt > 0), "deform_dec_layer: S=%d Lt=%d (an empty memory or text)", S, Lt);
+    VLLM_REQUIRE(tgt && reference_points && memory && spatial_shapes && level_start_index && out && (!ta || memory_text),
+                 "deform_dec_layer: null pointer (tgt / reference_points / memory_text / memory / spatial_shapes / level_start_index / out)");
+    VLLM_REQUIRE(aligned16(tgt) && aligned16(query_pos) && aligned16(memory_text) && aligned16(memory) && aligned16(out) &&
+                     (reinterpret_cast<uintptr_t>(reference_points) & (at.ref_dim == 4 ? 15u : 7u)) == 0,
+                 "deform_dec_layer: misaligned tgt / query_pos / memory_text / memory / out (16 bytes) or reference_points (8 bytes, 16 with ref_dim 4)");
+    for (const uint16_t *p : {d->sa_in_proj_w, d->sa_in_proj_b, d->sa_out_proj_w, d->sa_out_proj_b, d->sa_norm_w, d->sa_norm_b, d->text_in_proj_w,
+                              d->text_in_proj_b, d->text_out_proj_w, d->text_out_proj_b, d->text_norm_w, d->text_norm_b, d->ca_norm_w, d->ca_norm_b,
+                              d->fc1_w, d->fc1_b, d->fc2_w, d->fc2_b, d->ffn_norm_w, d->ffn_norm_b, at.value_proj_w, at.value_proj_b,
+                              at.sampling_offsets_w, at.sampling_offsets_b, at.attention_weights_w, at.attention_weights_b, at.output_proj_w,
+                              at.output_proj_b})
+        VLLM_REQUIRE(aligned16(p), "deform_dec_layer: misaligned weight or bias (16 bytes)");
+    const long R = (long)B * Lq;
+    const int C = at.d_model, F = d->d_ffn;
+    const long obytes = R * C * 2;
+    VLLM_REQUIRE(!overlaps(out, obytes, tgt, obytes) && !overlaps(out, obytes, query_pos, obytes) &&
+                     !overlaps(out, obytes, memory, (long)B * S * C * 2) && !(ta && overlaps(out, obytes, memory_text, (long)B * Lt * C * 2)),
+                 "deform_dec_layer: out overlaps an input (tgt / query_pos / memory_text / memory)");
+    const DecWs w = dec_ws(d, B, Lq, Lt, S);
+    VLLM_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= w.total,
+                 "deform_dec_layer: workspace too small (%ld < %ld bytes) or misaligned", workspace_bytes, w.total);
+    char *ws = (char *)workspace;
+    uint16_t *xp = (uint16_t *)(ws + w.xp), *bufa = (uint16_t *)(ws + w.a), *bufb = (uint16_t *)(ws + w.b), *qk = (uint16_t *)(ws + w.qk),
+             *vb = (uint16_t *)(ws + w.v), *ctx = (uint16_t *)(ws + w.ctx), *tkv = (uint16_t *)(ws + w.tkv), *h = (uint16_t *)(ws + w.h);
+    const int H = d->n_heads_sa, D = sa || ta ? C / H : 32;
+    const float scale = 1.0f / sqrtf((float)D);
+    // the attention kernel's own gate, asked before anything is enqueued (dense slices of the buffers above: it cannot refuse them)
+    if (sa) TRY(mha_fwd_check(qk, (long)Lq * 2 * C, 2 * C, qk + C, (long)Lq * 2 * C, 2 * C, vb, (long)Lq * C, C, ctx, (long)Lq * C, C, B, Lq, Lq, H, D));
+    if (ta) TRY(mha_fwd_check(vb, (long)Lq * C, C, tkv, (long)Lt * 2 * C, 2 * C, tkv + C, (long)Lt * 2 * C, 2 * C, ctx, (long)Lq * C, C, B, Lq, Lt, H, D));
+    ++g_calls;
+    hipStream_t st = (hipStream_t)stream;
+
+    const uint16_t *cur = tgt;          // the running x
+    const uint16_t *curp = tgt;         // x + pos
+    if (query_pos) { TRY(vllm_add_bf16(tgt, query_pos, xp, R * C, stream)); curp = xp; }
+    auto other = [&]() { return cur == bufa ? bufb : bufa; };
+    // the LayerNorm behind a block, in place, with the next block's x + pos
+    auto norm = [&](uint16_t *x, const uint16_t *nw, const uint16_t *nb, float eps, bool want_pos) {
+        const bool yp = want_pos && query_pos;
+        return vllm_add_layernorm_bf16(x, C, nullptr, 0, nw, nb, x, C, yp ? query_pos : nullptr, C, yp ? xp : nullptr, C, R, C, eps, stream);
+    };
+
+    // 1. self-attention of the queries (modeling_unipose.py:3280-3284; ...mask_dn.py:1349-1356)
+    if (sa) {
+        TRY(gemm(st, EPI_BIAS, curp, C, d->sa_in_proj_w, C, d->sa_in_proj_b, qk, 2 * C, (int)R, 2 * C, C));
+        TRY(gemm(st, EPI_BIAS, tgt, C, d->sa_in_proj_w + 2L * C * C, C, d->sa_in_proj_b + 2 * C, vb, C, (int)R, C, C));
+        TRY(mha_fwd_launch(qk, (long)Lq * 2 * C, 2 * C, qk + C, (long)Lq * 2 * C, 2 * C, vb, (long)Lq * C, C, ctx, (long)Lq * C, C, self_attn_mask,
+                           nullptr, B, Lq, Lq, H, D, scale, st));
+        uint16_t *y = other();
+        TRY(gemm(st, EPI_RESIDUAL, ctx, C, d->sa_out_proj_w, C, d->sa_out_proj_b, y, C, (int)R, C, C, nullptr, cur, C));
+        TRY(norm(y, d->sa_norm_w, d->sa_norm_b, d->sa_norm_eps, true));
+        cur = y;
+        if (query_pos) curp = xp; else curp = y;
+    }
+    // 2. text cross-attention (:3290-3294; :1361-1371)
+    if (ta) {
+        TRY(gemm(st, EPI_BIAS, curp, C, d->text_in_proj_w, C, d->text_in_proj_b, vb, C, (int)R, C, C));
+        TRY(gemm(st, EPI_BIAS, memory_text, C, d->text_in_proj_w + (long)C * C, C, d->text_in_proj_b + C, tkv, 2 * C, B * Lt, 2 * C, C));
+        TRY(mha_fwd_launch(vb, (long)Lq * C, C, tkv, (long)Lt * 2 * C, 2 * C, tkv + C, (long)Lt * 2 * C, 2 * C, ctx, (long)Lq * C, C, nullptr,
+                           text_key_padding_mask, B, Lq, Lt, H, D, scale, st));
+        uint16_t *y = other();
+        TRY(gemm(st, EPI_RESIDUAL, ctx, C, d->text_out_proj_w, C, d->text_out_proj_b, y, C, (int)R, C, C, nullptr, cur, C));
+        TRY(norm(y, d->text_norm_w, d->text_norm_b, d->text_norm_eps, true));
+        cur = y;
+        if (query_pos) curp = xp; else curp = y;
+    }
+    // 3. deformable cross-attention over the memory (:3303-3309; :1377-1391): the residual goes into output_proj's epilogue
+    {
+        uint16_t *y = other();
+        TRY(msda_layer_run(&at, curp, reference_points, memory, memory_padding_mask, spatial_shapes, level_start_index, B, Lq, S, y,
+                           msda_layer_bufs(&at, ws + w.attn, B, Lq, S), nullptr, st, cur));
+        TRY(norm(y, d->ca_norm_w, d->ca_norm_b, d->ca_norm_eps, false));
+        cur = y;
+    }
+    // 4. FFN (:3241-3248; :1394-1400)
+    uint16_t *y = other();
+    TRY(gemm(st, d->act == 0 ? EPI_RELU : EPI_GELU, cur, C, d->fc1_w, C, d->fc1_b, h, F, (int)R, F, C));
+    TRY(gemm(st, EPI_RESIDUAL, h, F, d->fc2_w, F, d->fc2_b, y, C, (int)R, C, F, nullptr, cur, C));
+    return vllm_add_layernorm_bf16(y, C, nullptr, 0, d->ffn_norm_w, d->ffn_norm_b, out, C, nullptr, 0, nullptr, 0, R, C, d->ffn_norm_eps, stream);
+}

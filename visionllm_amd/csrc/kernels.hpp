@@ -229,6 +229,14 @@ int attn_fwd_launch(AttnArgs a, int D, hipStream_t st);
 int attn_bwd_launch(const uint16_t *qkv, const uint16_t *out, const float *lse, const uint16_t *grad_out, int B, int S, int H, int D,
                     float softmax_scale, uint16_t *grad_qkv, void *workspace, long workspace_bytes, bool f16, hipStream_t st);
 
+// mha.hip: masked attention for short sequences (the decoder layers' self- and text attention); the arguments of vllm_mha_fwd_bf16.
+// mha_fwd_check is the launch's own gate, host-only: an orchestrator asks it before it enqueues anything.
+int mha_fwd_check(const uint16_t *q, long q_bs, int ldq, const uint16_t *k, long k_bs, int ldk, const uint16_t *v, long v_bs, int ldv,
+                  const uint16_t *out, long o_bs, int ldo, int B, int Lq, int Lk, int H, int D);
+int mha_fwd_launch(const uint16_t *q, long q_bs, int ldq, const uint16_t *k, long k_bs, int ldk, const uint16_t *v, long v_bs, int ldv,
+                   uint16_t *out, long o_bs, int ldo, const uint8_t *attn_mask, const uint8_t *key_padding_mask, int B, int Lq, int Lk,
+                   int H, int D, float softmax_scale, hipStream_t st);
+
 // embed_train.hip: a Conv2d weight [C, K] as the module stores it <-> its K-padded copy [C, kpad] (16-byte aligned kpad rows; [C, K] 4-byte)
 int pad_weight_launch(const uint16_t *w, uint16_t *wp, int C, int K, int kpad, hipStream_t st);
 int unpad_weight_launch(const uint16_t *wp, uint16_t *w, int C, int K, int kpad, hipStream_t st);

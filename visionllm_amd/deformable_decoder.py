@@ -1,0 +1,488 @@
+"""The deformable DECODER layers of the detection and pose heads: module mirrors and the one-call native forward.
+
+Same constructor arguments, parameter names and ``forward`` signatures as
+
+* ``DeformableTransformerDecoderLayer`` -- visionllmv2/model/unipose/modeling_unipose.py:3188-3323;
+* ``GroundingDinoDecoderLayer``         -- visionllmv2/model/grounding_dino/modeling_ov_grounding_dino_mask_dn.py:1292-1407,
+
+with ``self_attn`` / ``ca_text`` / ``encoder_attn_text`` torch's own ``nn.MultiheadAttention`` (state-dicts load) and ``cross_attn`` /
+``encoder_attn`` this package's ``MSDeformAttn`` / ``GroundingDinoMultiscaleDeformableAttention``.  With the class attribute
+``native_layer = False`` (the default) ``forward`` is the reference's statements, line for line.  With ``native_layer = True`` the
+inference forward of a bf16 module is ONE native call (``vllm_deform_dec_layer_forward``, csrc/deform_decoder_layer.hip; conditions:
+``native_layer_applies``); every other call runs the composed statements unchanged.
+
+The UniPose layer is sequence-first (``tgt`` [nq, bs, C]) and the native entry batch-first: its mirror transposes ``tgt``,
+``tgt_query_pos``, the reference points and ``memory`` on entry and the result on exit -- views where bs == 1, copies otherwise (the
+composed path's attention module makes the same copy of ``memory``).
+"""
+import ctypes
+
+import torch
+from torch import nn
+
+from . import _lib
+from .deformable_encoder import _act2fn, _get_activation_fn, _native_act
+from .ms_deform_attn import (GroundingDinoMultiscaleDeformableAttention, MSDeformAttn, known_geometry, level_pixels,
+                             msda_layer_fused_ok)
+
+_ATTN_LINEARS = ("value_proj", "sampling_offsets", "attention_weights", "output_proj")
+
+
+def _is_gpu_bf16(t, dims=3):
+    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == dims
+
+
+def _mha_reasons(name, mha, d_model):
+    """why the native attention kernel cannot stand in for this nn.MultiheadAttention (empty: it can)"""
+    out = []
+    if not getattr(mha, "_qkv_same_embed_dim", False) or mha.in_proj_weight is None:
+        out.append(f"{name}: separate q / k / v projection weights")
+        return out
+    if mha.in_proj_bias is None or mha.out_proj.bias is None:
+        out.append(f"{name}: no bias")
+    if mha.bias_k is not None or mha.bias_v is not None or mha.add_zero_attn:
+        out.append(f"{name}: bias_k / add_zero_attn")
+    if mha.embed_dim != d_model or mha.head_dim not in (32, 64):
+        out.append(f"{name}: head dim {mha.head_dim} (32 or 64)")
+    return out
+
+
+def native_layer_reasons(layer, parts, tgt, pos, reference_points, memory_text, text_mask, memory, self_attn_mask, batch_first):
+    """Every reason why ``vllm_deform_dec_layer_forward`` does not serve this call, as a list of strings (empty: it does).  ``parts`` is
+    the layer's ``_parts()``; tensors as the layer's ``forward`` receives them (``batch_first`` tells the layout of tgt / pos / memory)."""
+    why = []
+    if not (_is_gpu_bf16(tgt) and _is_gpu_bf16(memory)):
+        why.append("tgt / memory: bf16 CUDA tensors [., ., C]")
+        if not (torch.is_tensor(tgt) and tgt.dim() == 3 and torch.is_tensor(memory) and memory.dim() == 3):
+            return why
+    if pos is not None and not (_is_gpu_bf16(pos) and pos.shape == tgt.shape):
+        why.append("query_pos: a bf16 CUDA tensor of tgt's shape")
+    bdim, qdim = (0, 1) if batch_first else (1, 0)
+    B, Lq, C = tgt.shape[bdim], tgt.shape[qdim], tgt.shape[2]
+    sa, ta = parts["self_attn"], parts["text_attn"]
+    mods = [parts["ca_norm"], parts["fc1"], parts["fc2"], parts["ffn_norm"]] + [getattr(parts["cross_attn"], n) for n in _ATTN_LINEARS]
+    if sa is not None:
+        mods += [sa, parts["sa_norm"]]
+    if ta is not None:
+        mods += [ta, parts["text_norm"]]
+    params = [p for m in mods for p in m.parameters()]
+    if any(p.dtype != torch.bfloat16 or not p.is_cuda for p in params):
+        why.append("parameters: bf16 on the GPU")
+    if any(getattr(m, "bias", 0) is None for m in mods if not isinstance(m, nn.MultiheadAttention)):
+        why.append("parameters: a Linear / LayerNorm without bias")
+    if torch.is_grad_enabled() and (any(p.requires_grad for p in params) or
+                                    any(torch.is_tensor(t) and t.requires_grad for t in (tgt, pos, memory, memory_text, reference_points))):
+        why.append("requires_grad under grad mode: there is no native backward")
+    if layer.training and any(p > 0 for p in parts["dropouts"]):
+        why.append("active dropout")
+    if parts["act"] is None:
+        why.append("activation: relu or gelu")
+    if reference_points is None or not torch.is_tensor(reference_points) or reference_points.shape[-1] not in (2, 4):
+        why.append("reference_points: last dim 2 or 4")
+    elif not (_is_gpu_bf16(tgt) and _is_gpu_bf16(memory)) or not msda_layer_fused_ok(
+            tgt, memory, *(getattr(parts["cross_attn"], n) for n in _ATTN_LINEARS), reference_points=reference_points):
+        why.append("cross-attention: msda_layer_fused_ok")
+    if sa is not None:
+        why += _mha_reasons("self_attn", sa, C)
+        if self_attn_mask is not None and not (torch.is_tensor(self_attn_mask) and self_attn_mask.dtype == torch.bool and
+                                               tuple(self_attn_mask.shape) == (Lq, Lq)):
+            why.append("self_attn_mask: None or a 2-d bool [Lq, Lq] (float and per-head masks keep the composed path)")
+    if ta is not None:
+        why += _mha_reasons("text attention", ta, C)
+        if not (torch.is_tensor(memory_text) and memory_text.dim() == 3 and memory_text.shape[0] == B and memory_text.shape[2] == C and
+                memory_text.shape[1] > 0 and memory_text.dtype == torch.bfloat16 and memory_text.is_cuda):
+            why.append("memory_text: a bf16 CUDA tensor [B, Lt, C]")
+        if text_mask is not None and not (torch.is_tensor(text_mask) and text_mask.dtype == torch.bool and torch.is_tensor(memory_text) and
+                                          memory_text.dim() == 3 and tuple(text_mask.shape) == (B, memory_text.shape[1])):
+            why.append("text mask: None or bool [B, Lt]")
+    d_ffn = parts["fc1"].out_features
+    if not (C % 64 == 0 and C <= 512 and d_ffn % 64 == 0 and getattr(parts["cross_attn"], "d_model", C) == C):
+        why.append("d_model a multiple of 64 up to 512, d_ffn a multiple of 64")
+    return why
+
+
+def deform_dec_layer_forward(parts, tgt, pos, reference_points, self_attn_mask, memory_text, text_mask, memory, memory_padding_mask,
+                             spatial_shapes, level_start_index):
+    """One ``vllm_deform_dec_layer_forward`` call -> out [B, Lq, C].  Batch-first: ``tgt`` [B, Lq, C] bf16 on the GPU, ``pos`` the same or
+    None, ``reference_points`` [B, Lq, L, 2 | 4], ``self_attn_mask`` bool [Lq, Lq] (True = may not attend) or None, ``memory_text``
+    [B, Lt, C], ``text_mask`` bool [B, Lt] (True = ignore) or None, ``memory`` [B, S, C], ``memory_padding_mask`` bool [B, S] (True =
+    padded) or None."""
+    attn = parts["cross_attn"]
+    B, Lq, C = tgt.shape
+    S = memory.shape[1]
+    n_levels, ref_dim = attn.n_levels, reference_points.shape[-1]
+    if reference_points.dim() != 4 or reference_points.shape[0] not in (1, B) or reference_points.shape[1] not in (1, Lq) or \
+            reference_points.shape[2] not in (1, n_levels):
+        raise RuntimeError(f"deform_dec_layer_forward: reference_points {tuple(reference_points.shape)} does not broadcast to "
+                           f"({B}, {Lq}, {n_levels}, 2|4)")
+    if tuple(memory.shape) != (B, S, C):
+        raise RuntimeError(f"deform_dec_layer_forward: memory {tuple(memory.shape)} vs tgt {tuple(tgt.shape)}")
+    if tuple(spatial_shapes.shape) != (n_levels, 2) or level_start_index.numel() != n_levels:
+        raise RuntimeError(f"deform_dec_layer_forward: spatial_shapes {tuple(spatial_shapes.shape)} / level_start_index "
+                           f"({level_start_index.numel()}) do not describe {n_levels} levels")
+    if memory_padding_mask is not None and tuple(memory_padding_mask.shape) != (B, S):
+        raise RuntimeError(f"deform_dec_layer_forward: padding mask {tuple(memory_padding_mask.shape)} must be ({B}, {S})")
+    L = _lib.lib()
+    desc = _lib.VllmDeformDecLayerDesc()
+    a = desc.cross_attn
+    a.d_model, a.n_heads, a.n_levels, a.n_points, a.ref_dim = C, attn.n_heads, n_levels, attn.n_points, ref_dim
+    a.use_4d_normalizer = int(bool(getattr(attn, "use_4D_normalizer", False)))
+    sa, ta = parts["self_attn"], parts["text_attn"]
+    desc.d_ffn, desc.act = parts["fc1"].out_features, parts["act"]
+    desc.has_self_attn, desc.has_text_attn = int(sa is not None), int(ta is not None)
+    desc.n_heads_sa = sa.num_heads if sa is not None else ta.num_heads if ta is not None else 0
+    desc.ca_norm_eps, desc.ffn_norm_eps = parts["ca_norm"].eps, parts["ffn_norm"].eps
+    keep = []
+
+    def put(struct, name, weight, bias):
+        w, b = _lib.aligned(weight.detach()), _lib.aligned(bias.detach())
+        keep.extend((w, b))
+        setattr(struct, name + "_w", w.data_ptr())
+        setattr(struct, name + "_b", b.data_ptr())
+    for name in _ATTN_LINEARS:
+        put(a, name, getattr(attn, name).weight, getattr(attn, name).bias)
+    for name, mod in (("ca_norm", parts["ca_norm"]), ("fc1", parts["fc1"]), ("fc2", parts["fc2"]), ("ffn_norm", parts["ffn_norm"])):
+        put(desc, name, mod.weight, mod.bias)
+    for pre, mha, norm in (("sa", sa, parts["sa_norm"]), ("text", ta, parts["text_norm"])):
+        if mha is not None:
+            put(desc, pre + "_in_proj", mha.in_proj_weight, mha.in_proj_bias)
+            put(desc, pre + "_out_proj", mha.out_proj.weight, mha.out_proj.bias)
+            put(desc, pre + "_norm", norm.weight, norm.bias)
+            setattr(desc, pre + "_norm_eps", norm.eps)
+    x = _lib.aligned(tgt)
+    p = None if pos is None else _lib.aligned(pos)
+    mem = _lib.aligned(memory)
+    ref = _lib.aligned(reference_points.to(torch.float32).expand(B, Lq, n_levels, ref_dim), 16 if ref_dim == 4 else 8)
+    shapes = spatial_shapes.to(device=x.device, dtype=torch.int64).contiguous()
+    lsi = level_start_index.to(device=x.device, dtype=torch.int64).contiguous()
+    u8 = lambda m: None if m is None else m.to(device=x.device).to(torch.uint8).contiguous()
+    sam = u8(self_attn_mask) if sa is not None else None
+    text, tmask, Lt = None, None, 0
+    if ta is not None:
+        text, tmask, Lt = _lib.aligned(memory_text), u8(text_mask), memory_text.shape[1]
+    pmask = u8(memory_padding_mask)
+    a.geometry = known_geometry(spatial_shapes, Lq)
+    ws, wsb = _lib.sized_workspace(x.device, L.vllm_deform_dec_layer_workspace_bytes(ctypes.byref(desc), B, Lq, Lt, S),
+                                   "vllm_deform_dec_layer_workspace_bytes")
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _lib.check(L.vllm_deform_dec_layer_forward(ctypes.byref(desc), _lib.ptr(x), _lib.ptr(p), _lib.ptr(ref), _lib.ptr(sam), _lib.ptr(text),
+                                                   _lib.ptr(tmask), _lib.ptr(mem), _lib.ptr(pmask), _lib.ptr(shapes), _lib.ptr(lsi), B, Lq, Lt, S,
+                                                   _lib.ptr(out), _lib.ptr(ws), wsb, _lib.current_stream(x.device)),
+                   "vllm_deform_dec_layer_forward")
+    del keep
+    return out
+
+
+class DeformableTransformerDecoderLayer(nn.Module):
+    """UniPose / DINO decoder layer (unipose/modeling_unipose.py:3188-3323)."""
+
+    native_layer = False   # True: bf16 inference runs vllm_deform_dec_layer_forward where native_layer_applies() holds
+
+    def __init__(self, d_model=256, d_ffn=1024,
+                 dropout=0.1, activation="relu",
+                 n_levels=4, n_heads=8, n_points=4,
+                 use_text_feat_guide=False,
+                 use_text_cross_attention=False,
+                 ffn_extra_layernorm=False
+                 ):
+        super().__init__()
+
+        # cross attention
+        self.cross_attn = MSDeformAttn(d_model, n_levels, n_heads, n_points)
+        self.dropout1 = nn.Dropout(dropout) if dropout > 0 else nn.Identity()
+        self.norm1 = nn.LayerNorm(d_model)
+
+        # cross attention text
+        if use_text_cross_attention:
+            self.ca_text = nn.MultiheadAttention(d_model, n_heads, dropout=dropout)
+            self.catext_dropout = nn.Dropout(dropout) if dropout > 0 else nn.Identity()
+            self.catext_norm = nn.LayerNorm(d_model)
+
+        # self attention
+        self.self_attn = nn.MultiheadAttention(d_model, n_heads, dropout=dropout)
+        self.dropout2 = nn.Dropout(dropout) if dropout > 0 else nn.Identity()
+        self.norm2 = nn.LayerNorm(d_model)
+
+        # ffn
+        self.linear1 = nn.Linear(d_model, d_ffn)
+        self.activation = _get_activation_fn(activation, d_model=d_ffn, batch_dim=1)
+        self.dropout3 = nn.Dropout(dropout) if dropout > 0 else nn.Identity()
+        self.linear2 = nn.Linear(d_ffn, d_model)
+        self.dropout4 = nn.Dropout(dropout) if dropout > 0 else nn.Identity()
+        self.norm3 = nn.LayerNorm(d_model)
+        if ffn_extra_layernorm:
+            raise NotImplementedError('ffn_extra_layernorm not implemented')
+        else:
+            self.norm_ext = None
+
+        self.key_aware_proj = None
+        self.use_text_feat_guide = use_text_feat_guide
+        assert not use_text_feat_guide
+        self.use_text_cross_attention = use_text_cross_attention
+
+    def rm_self_attn_modules(self):
+        self.self_attn = None
+        self.dropout2 = None
+        self.norm2 = None
+
+    @staticmethod
+    def with_pos_embed(tensor, pos):
+        return tensor if pos is None else tensor + pos
+
+    def forward_ffn(self, tgt, ipdb_flag=False):
+
+        with torch.amp.autocast("cuda", enabled=False):   # (the reference spells it torch.cuda.amp.autocast, which newer torch deprecates)
+            tgt2 = self.linear2(self.dropout3(self.activation(self.linear1(tgt))))
+
+        tgt = tgt + self.dropout4(tgt2)
+        tgt = self.norm3(tgt)
+        return tgt
+
+    def _parts(self):
+        text = self.ca_text if self.use_text_cross_attention else None
+        drops = [getattr(m, "p", 0.0) for m in (self.dropout1, self.dropout3, self.dropout4)]
+        if self.self_attn is not None:
+            drops += [getattr(self.dropout2, "p", 0.0), self.self_attn.dropout]
+        if text is not None:
+            drops += [getattr(self.catext_dropout, "p", 0.0), text.dropout]
+        return dict(cross_attn=self.cross_attn, self_attn=self.self_attn, sa_norm=self.norm2, text_attn=text,
+                    text_norm=self.catext_norm if text is not None else None, ca_norm=self.norm1, fc1=self.linear1, fc2=self.linear2,
+                    ffn_norm=self.norm3, act=_native_act(self.activation), dropouts=drops)
+
+    def native_layer_reasons(self, tgt, tgt_query_pos=None, tgt_reference_points=None, memory_text=None, text_attention_mask=None,
+                             memory=None, self_attn_mask=None, cross_attn_mask=None):
+        """why this call keeps the composed path, as a list of strings (empty: the native call serves it)"""
+        why = native_layer_reasons(self, self._parts(), tgt, tgt_query_pos, tgt_reference_points, memory_text, text_attention_mask, memory,
+                                   self_attn_mask, batch_first=False)
+        if cross_attn_mask is not None:
+            why.append("cross_attn_mask")
+        return why
+
+    def native_layer_applies(self, *args, **kwargs):
+        """What vllm_deform_dec_layer_forward serves: bf16 CUDA inputs; every parameter bf16, with biases; nothing that needs a gradient
+        under grad mode; no active dropout (the attention modules' own included); a relu / gelu activation; the fused cross-attention's
+        conditions (msda_layer_fused_ok); packed in_proj weights, no bias_k / add_zero_attn, head dim 32 or 64; ``self_attn_mask`` None or
+        a 2-d bool [Lq, Lq]; the text mask None or bool [B, Lt]; no ``cross_attn_mask``; d_model (at most 512) and d_ffn multiples of 64."""
+        return not self.native_layer_reasons(*args, **kwargs)
+
+    def _native_forward(self, tgt, tgt_query_pos, tgt_reference_points, memory_text, text_attention_mask, memory, memory_key_padding_mask,
+                        memory_level_start_index, memory_spatial_shapes, self_attn_mask):
+        assert level_pixels(memory_spatial_shapes) == memory.shape[0]   # MSDeformAttn.forward's own check (ms_deform_attn.py:100)
+        out = deform_dec_layer_forward(self._parts(), tgt.transpose(0, 1), None if tgt_query_pos is None else tgt_query_pos.transpose(0, 1),
+                                       tgt_reference_points.transpose(0, 1), self_attn_mask, memory_text, text_attention_mask,
+                                       memory.transpose(0, 1), memory_key_padding_mask, memory_spatial_shapes, memory_level_start_index)
+        return out.transpose(0, 1)
+
+    def forward(self,
+                # for tgt
+                tgt,  # nq, bs, d_model
+                tgt_query_pos=None,  # pos for query. MLP(Sine(pos))
+                tgt_query_sine_embed=None,  # pos for query. Sine(pos)
+                tgt_key_padding_mask=None,
+                tgt_reference_points=None,  # nq, bs, 4
+
+                memory_text=None,  # bs, num_token, d_model
+                text_attention_mask=None,  # bs, num_token
+
+                # for memory
+                memory=None,  # hw, bs, d_model
+                memory_key_padding_mask=None,
+                memory_level_start_index=None,  # num_levels
+                memory_spatial_shapes=None,  # bs, num_levels, 2
+                memory_pos=None,  # pos for memory
+
+                # sa
+                self_attn_mask=None,  # mask used for self-attention
+                cross_attn_mask=None,  # mask used for cross-attention
+                ):
+        """
+        Input:
+            - tgt/tgt_query_pos: nq, bs, d_model
+            -
+        """
+        assert cross_attn_mask is None
+
+        if self.native_layer and self.native_layer_applies(tgt, tgt_query_pos, tgt_reference_points, memory_text, text_attention_mask, memory,
+                                                           self_attn_mask, cross_attn_mask):
+            return self._native_forward(tgt, tgt_query_pos, tgt_reference_points, memory_text, text_attention_mask, memory,
+                                        memory_key_padding_mask, memory_level_start_index, memory_spatial_shapes, self_attn_mask)
+
+        # self attention
+        if self.self_attn is not None:
+            q = k = self.with_pos_embed(tgt, tgt_query_pos)
+            tgt2 = self.self_attn(q, k, tgt, attn_mask=self_attn_mask)[0]
+            tgt = tgt + self.dropout2(tgt2)
+            tgt = self.norm2(tgt)
+
+        if self.use_text_cross_attention:
+            tgt2 = self.ca_text(self.with_pos_embed(tgt, tgt_query_pos), memory_text.transpose(0, 1),
+                                memory_text.transpose(0, 1), key_padding_mask=text_attention_mask)[0]
+            tgt = tgt + self.catext_dropout(tgt2)
+            tgt = self.catext_norm(tgt)
+
+        tgt2 = self.cross_attn(self.with_pos_embed(tgt, tgt_query_pos).transpose(0, 1),
+                               tgt_reference_points.transpose(0, 1).contiguous(),
+                               memory.transpose(0, 1),
+                               memory_spatial_shapes, memory_level_start_index,
+                               memory_key_padding_mask).transpose(0, 1)
+        tgt = tgt + self.dropout1(tgt2)
+        tgt = self.norm1(tgt)
+
+        # ffn
+        tgt = self.forward_ffn(tgt)
+
+        return tgt
+
+
+class GroundingDinoDecoderLayer(nn.Module):
+    """HF / Grounding-DINO decoder layer (modeling_ov_grounding_dino_mask_dn.py:1292-1407).  ``config`` needs ``d_model``,
+    ``num_feature_levels``, ``decoder_attention_heads``, ``decoder_n_points``, ``decoder_ffn_dim``, ``dropout``, ``attention_dropout``,
+    ``activation_function`` and ``activation_dropout``."""
+
+    native_layer = False   # as DeformableTransformerDecoderLayer.native_layer
+
+    def __init__(self, config):
+        super().__init__()
+        self.embed_dim = config.d_model
+
+        # self-attention
+        self.self_attn = nn.MultiheadAttention(
+            embed_dim=self.embed_dim,
+            num_heads=config.decoder_attention_heads,
+            dropout=config.attention_dropout,
+            batch_first=True,
+        )
+        self.dropout = config.dropout
+        self.activation_fn = _act2fn(config.activation_function)
+        self.activation_dropout = config.activation_dropout
+
+        self.self_attn_layer_norm = nn.LayerNorm(self.embed_dim)
+        # cross-attention text
+        self.encoder_attn_text = nn.MultiheadAttention(
+            embed_dim=self.embed_dim,
+            num_heads=config.decoder_attention_heads,
+            dropout=config.attention_dropout,
+            batch_first=True,
+        )
+        self.encoder_attn_text_layer_norm = nn.LayerNorm(self.embed_dim)
+        # cross-attention
+        self.encoder_attn = GroundingDinoMultiscaleDeformableAttention(
+            config,
+            num_heads=config.decoder_attention_heads,
+            n_points=config.decoder_n_points,
+        )
+        self.encoder_attn_layer_norm = nn.LayerNorm(self.embed_dim)
+        # feedforward neural networks
+        self.fc1 = nn.Linear(self.embed_dim, config.decoder_ffn_dim)
+        self.fc2 = nn.Linear(config.decoder_ffn_dim, self.embed_dim)
+        self.final_layer_norm = nn.LayerNorm(self.embed_dim)
+
+    def with_pos_embed(self, tensor, position_embeddings):
+        return tensor if position_embeddings is None else tensor + position_embeddings
+
+    def _parts(self):
+        return dict(cross_attn=self.encoder_attn, self_attn=self.self_attn, sa_norm=self.self_attn_layer_norm,
+                    text_attn=self.encoder_attn_text, text_norm=self.encoder_attn_text_layer_norm, ca_norm=self.encoder_attn_layer_norm,
+                    fc1=self.fc1, fc2=self.fc2, ffn_norm=self.final_layer_norm, act=_native_act(self.activation_fn),
+                    dropouts=[self.dropout, self.activation_dropout, self.self_attn.dropout, self.encoder_attn_text.dropout])
+
+    def native_layer_reasons(self, hidden_states, position_embeddings=None, reference_points=None, vision_encoder_hidden_states=None,
+                             text_encoder_hidden_states=None, text_encoder_attention_mask=None, self_attn_mask=None,
+                             output_attentions=False):
+        """why this call keeps the composed path, as a list of strings (empty: the native call serves it)"""
+        why = native_layer_reasons(self, self._parts(), hidden_states, position_embeddings, reference_points, text_encoder_hidden_states,
+                                   text_encoder_attention_mask, vision_encoder_hidden_states, self_attn_mask, batch_first=True)
+        if output_attentions:
+            why.append("output_attentions: the attention weights stay inside the native call")
+        return why
+
+    def native_layer_applies(self, *args, **kwargs):
+        """As DeformableTransformerDecoderLayer.native_layer_applies; a call with ``output_attentions`` keeps the composed path."""
+        return not self.native_layer_reasons(*args, **kwargs)
+
+    def forward(
+        self,
+        hidden_states: torch.Tensor,
+        position_embeddings=None,
+        reference_points=None,
+        spatial_shapes=None,
+        level_start_index=None,
+        vision_encoder_hidden_states=None,
+        vision_encoder_attention_mask=None,
+        text_encoder_hidden_states=None,
+        text_encoder_attention_mask=None,
+        self_attn_mask=None,
+        output_attentions=False,
+    ):
+        if self.native_layer and self.native_layer_applies(hidden_states, position_embeddings, reference_points, vision_encoder_hidden_states,
+                                                           text_encoder_hidden_states, text_encoder_attention_mask, self_attn_mask,
+                                                           output_attentions):
+            if level_pixels(spatial_shapes) != vision_encoder_hidden_states.shape[1]:   # the attention module's own check (...mask_dn.py:741)
+                raise ValueError("Make sure to align the spatial shapes with the sequence length of the encoder hidden states")
+            return (deform_dec_layer_forward(self._parts(), hidden_states, position_embeddings, reference_points, self_attn_mask,
+                                             text_encoder_hidden_states, text_encoder_attention_mask, vision_encoder_hidden_states,
+                                             None if vision_encoder_attention_mask is None else ~vision_encoder_attention_mask,
+                                             spatial_shapes, level_start_index),)
+        residual = hidden_states
+
+        # Self Attention
+        q = k = self.with_pos_embed(hidden_states, position_embeddings)
+        hidden_states, self_attn_weights = self.self_attn(
+            query=q, key=k, value=hidden_states, attn_mask=self_attn_mask, average_attn_weights=False
+        )
+
+        hidden_states = nn.functional.dropout(hidden_states, p=self.dropout, training=self.training)
+        hidden_states = residual + hidden_states
+        hidden_states = self.self_attn_layer_norm(hidden_states)
+
+        second_residual = hidden_states
+
+        # Cross-Attention Text
+        hidden_states, text_cross_attn_weights = self.encoder_attn_text(
+            query=self.with_pos_embed(hidden_states, position_embeddings),
+            key=text_encoder_hidden_states,
+            value=text_encoder_hidden_states,
+            key_padding_mask=text_encoder_attention_mask,
+            average_attn_weights=False,
+        )
+
+        hidden_states = nn.functional.dropout(hidden_states, p=self.dropout, training=self.training)
+        hidden_states = second_residual + hidden_states
+        hidden_states = self.encoder_attn_text_layer_norm(hidden_states)
+
+        third_residual = hidden_states
+
+        # Cross-Attention
+        cross_attn_weights = None
+        hidden_states, cross_attn_weights = self.encoder_attn(
+            hidden_states=hidden_states,
+            attention_mask=vision_encoder_attention_mask,
+            encoder_hidden_states=vision_encoder_hidden_states,
+            encoder_attention_mask=vision_encoder_attention_mask,
+            position_embeddings=position_embeddings,
+            reference_points=reference_points,
+            spatial_shapes=spatial_shapes,
+            level_start_index=level_start_index,
+            output_attentions=output_attentions,
+        )
+
+        hidden_states = nn.functional.dropout(hidden_states, p=self.dropout, training=self.training)
+        hidden_states = third_residual + hidden_states
+        hidden_states = self.encoder_attn_layer_norm(hidden_states)
+
+        # Fully Connected
+        residual = hidden_states
+        hidden_states = self.activation_fn(self.fc1(hidden_states))
+        hidden_states = nn.functional.dropout(hidden_states, p=self.activation_dropout, training=self.training)
+        hidden_states = self.fc2(hidden_states)
+        hidden_states = nn.functional.dropout(hidden_states, p=self.dropout, training=self.training)
+        hidden_states = residual + hidden_states
+        hidden_states = self.final_layer_norm(hidden_states)
+
+        outputs = (hidden_states,)
+
+        if output_attentions:
+            outputs += (self_attn_weights, text_cross_attn_weights, cross_attn_weights)
+
+        return outputs
