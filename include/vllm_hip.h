@@ -439,6 +439,69 @@ int vllm_mha_fwd_bf16(const uint16_t *q, long q_batch_stride, int ldq, const uin
                       float softmax_scale, vllm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * f2d. The whole Grounding-DINO DECODER around the layer above, bf16 modules (inference), 4-d reference points.
+ *
+ * Replaces the body of
+ *   GroundingDinoDecoder.forward   visionllmv2/model/grounding_dino/modeling_ov_grounding_dino_mask_dn.py:1792-1981
+ * without output_attentions / output_hidden_states.  Per layer l, in this order:
+ *   1. vllm_refpoint_embed_bf16: reference_points_input = ref * valid_ratios (fp32) and the sine embedding of its level 0 (bf16)
+ *   2. reference_points_head: two GEMMs (ReLU, bias) -> query_pos, bf16
+ *   3. the launches of vllm_deform_dec_layer_forward for layers[l] on the running hidden state (the un-normed output of layer l - 1)
+ *   4. vllm_add_layernorm_bf16 (no residual) -> intermediate[l]
+ *   5. with a box head: two ReLU GEMMs and vllm_box_refine_f32 -> intermediate_reference_points[l], the next layer's `ref`;
+ *      without one (box_heads NULL) the reference points never change and intermediate_reference_points[l] is a copy of the input.
+ * Both outputs are LAYER-MAJOR ([n_layers, B, Lq, .]; the module stacks along dim 1): every launch writes one dense block, nothing is
+ * stacked or copied afterwards.  Reference points are fp32 from entry to exit; the box delta is never rounded to bf16.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct VllmBoxHead {
+    const uint16_t *w0, *b0, *w1, *b1, *w2, *b2;   /* [C, C] [C] [C, C] [C] [4, C] [4]  (device, bf16) */
+} VllmBoxHead;
+typedef struct VllmDeformDecoderDesc {
+    int32_t n_layers;                        /* 1 .. 64 */
+    int32_t n_pos_feats;                     /* P: sine features per coordinate; a multiple of 16 (4 P is a GEMM's K) */
+    float   layer_norm_eps;
+    float   inverse_sigmoid_eps;             /* 1e-5 in the reference (:401) */
+    const VllmDeformDecLayerDesc *layers;    /* HOST array [n_layers]; one d_model, n_levels; cross_attn.ref_dim 4 */
+    const uint16_t *ref_head_w0, *ref_head_b0, *ref_head_w1, *ref_head_b1;   /* reference_points_head: [C, 4P] [C] [C, C] [C] */
+    const uint16_t *layer_norm_w, *layer_norm_b;                             /* [C] [C] */
+    const float    *dim_t;                   /* [P] fp32, device: the module's own temperature table (:1761-1762) */
+    const VllmBoxHead *box_heads;            /* HOST array [n_layers] (entries may repeat: a shared head) or NULL: no refinement */
+} VllmDeformDecoderDesc;
+unsigned long vllm_deform_decoder_desc_sizeof(void);
+/* Bytes of device scratch vllm_deform_decoder_forward needs; host-only; 0 for B Lq == 0, negative for a refused descriptor or sizes. */
+long vllm_deform_decoder_workspace_bytes(const VllmDeformDecoderDesc *desc, int B, int Lq, int Lt, int S);
+long vllm_deform_decoder_calls(void);   /* calls of vllm_deform_decoder_forward in this process that reached their launches (tests) */
+/* tgt [B, Lq, C] bf16; reference_points [B, Lq, 4] fp32; valid_ratios [B, L, 2] fp32; the masks, memory_text, memory, spatial_shapes and
+ * level_start_index as vllm_deform_dec_layer_forward takes them; intermediate [n_layers, B, Lq, C] bf16;
+ * intermediate_reference_points [n_layers, B, Lq, 4] fp32.  One stream, no allocation, no synchronisation.  A refused call (NULL or
+ * misaligned operand; ref_dim != 4; a layer descriptor its own entry refuses; layers of differing d_model / n_levels; n_pos_feats;
+ * an output overlapping an input or the other output; short or misaligned workspace: VLLM_EINVAL, reason in vllm_last_error()) has
+ * enqueued nothing; B Lq == 0 returns VLLM_OK.  vllm_deform_dec_layer_calls() is not touched. */
+/* Alignment: tgt, memory_text, memory, reference_points, dim_t, both outputs, every weight / bias and workspace 16 bytes; valid_ratios
+ * 8 bytes; the masks: element alignment. */
+int vllm_deform_decoder_forward(const VllmDeformDecoderDesc *desc, const uint16_t *tgt, const float *reference_points,
+                                const float *valid_ratios, const uint8_t *self_attn_mask, const uint16_t *memory_text,
+                                const uint8_t *text_key_padding_mask, const uint16_t *memory, const uint8_t *memory_padding_mask,
+                                const int64_t *spatial_shapes, const int64_t *level_start_index, int B, int Lq, int Lt, int S,
+                                uint16_t *intermediate, float *intermediate_reference_points, void *workspace, long workspace_bytes,
+                                vllm_stream_t stream);
+/* The two row kernels of the loop, exposed for the parity tests (and for other decoder flavours: the sine formula is DINO's, eps a
+ * parameter).  No atomics: the same bits on every run.
+ * vllm_refpoint_embed_bf16: rows = B Lq.  reference_points_input [B, Lq, L, 4] fp32 = ref[b, q, k] * valid_ratios[b, l, k & 1], one fp32
+ *   product.  sine [B Lq, 4 P] bf16 with row stride ld_sine (elements, a multiple of 8, at least 4 P), from level 0 of that product in
+ *   the order (y, x, w, h): element i of a group is sin (i even) or cos (i odd) of (v * 2 pi) / dim_t[i] -- fp32, a true division, the
+ *   accurate sinf / cosf, one rounding.  Nothing is written outside the 4 P columns of a row.  ref_dim must be 4, P a multiple of 8.
+ * vllm_box_refine_f32: new_ref[r, k] = sigmoid(sum_c h[r, c] W[k, c] + b[k] + log(max(x, eps) / max(1 - x, eps))), x = ref[r, k]
+ *   clamped to [0, 1]; h [R, C] bf16 with row stride ldh (a multiple of 8, at least C), W [4, C], b [4] bf16; everything fp32 in a fixed
+ *   order, new_ref [R, 4] fp32, which may be `ref` itself.  C a multiple of 64 in 64 .. 512.
+ * A refused call (VLLM_EINVAL) has enqueued nothing; no rows returns VLLM_OK. */
+/* Alignment: reference_points, dim_t, reference_points_input, sine, h, W, ref, new_ref 16 bytes; valid_ratios, b 8 bytes. */
+int vllm_refpoint_embed_bf16(const float *reference_points, const float *valid_ratios, const float *dim_t, int B, int Lq, int L, int ref_dim,
+                             int P, float *reference_points_input, uint16_t *sine, int ld_sine, vllm_stream_t stream);
+int vllm_box_refine_f32(const uint16_t *h, int ldh, const uint16_t *W, const uint16_t *b, const float *ref, float *new_ref, long R, int C,
+                        float eps, vllm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * f3b. The whole DCNv3 layer, bf16 modules (inference).
  *
  * Replaces the body of DCNv3.forward, visionllmv2/model/ops_dcnv3/modules/dcnv3.py:313-351, with the CenterFeatureScaleModule

@@ -10,7 +10,8 @@ Host-side mirror of the reference's operator/module interfaces for that path onl
 * ``deformable_encoder`` -- ``DeformableTransformerEncoderLayer`` (UniPose) and ``GroundingDinoDeformableLayer`` (HF) mirrors with the
   one-call native forward, and ``encoder_layers_forward``; the three names are also attributes of this package.
 * ``deformable_decoder`` -- ``DeformableTransformerDecoderLayer`` (UniPose) and ``GroundingDinoDecoderLayer`` (HF) mirrors with the
-  one-call native forward; the two names are also attributes of this package.
+  one-call native forward, and ``GroundingDinoDecoder`` (with ``GroundingDinoMLPPredictionHead``), the whole decoder loop as one native
+  call; the four names are also attributes of this package.
 
 All compute goes through ``libvllm_hip.so`` (hand-written HIP, C ABI in ``include/vllm_hip.h``).  There is NO
 CPU fallback: calling an op without the built extension, or with CPU tensors, raises.
@@ -20,7 +21,7 @@ from ._lib import build, lib, lib_path  # noqa: F401
 __version__ = "0.1.0"
 
 _ENCODER_EXPORTS = ("DeformableTransformerEncoderLayer", "GroundingDinoDeformableLayer", "encoder_layers_forward")
-_DECODER_EXPORTS = ("DeformableTransformerDecoderLayer", "GroundingDinoDecoderLayer")
+_DECODER_EXPORTS = ("DeformableTransformerDecoderLayer", "GroundingDinoDecoderLayer", "GroundingDinoDecoder", "GroundingDinoMLPPredictionHead")
 __all__ = ["build", "lib", "lib_path", *_ENCODER_EXPORTS, *_DECODER_EXPORTS]
 
 

@@ -175,6 +175,17 @@ class VllmDeformDecLayerDesc(ctypes.Structure):
                                   "ca_norm_w", "ca_norm_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ffn_norm_w", "ffn_norm_b")]
 
 
+class VllmBoxHead(ctypes.Structure):
+    _fields_ = [(n, _P) for n in ("w0", "b0", "w1", "b1", "w2", "b2")]
+
+
+class VllmDeformDecoderDesc(ctypes.Structure):
+    _fields_ = [("n_layers", ctypes.c_int32), ("n_pos_feats", ctypes.c_int32), ("layer_norm_eps", ctypes.c_float),
+                ("inverse_sigmoid_eps", ctypes.c_float), ("layers", ctypes.POINTER(VllmDeformDecLayerDesc))] + \
+               [(n, _P) for n in ("ref_head_w0", "ref_head_b0", "ref_head_w1", "ref_head_b1", "layer_norm_w", "layer_norm_b", "dim_t")] + \
+               [("box_heads", ctypes.POINTER(VllmBoxHead))]
+
+
 class VllmDcnv3LayerDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("channels", "group", "kernel_size", "dw_kernel_size", "dilation", "center_feature_scale",
                                               "n_proj")] + \
@@ -245,6 +256,7 @@ def check_struct_layouts():
     assert ctypes.sizeof(VllmDcnv3LayerDesc) == L.vllm_dcnv3_layer_desc_sizeof(), "VllmDcnv3LayerDesc layout mismatch"
     assert ctypes.sizeof(VllmDeformEncLayerDesc) == L.vllm_deform_enc_layer_desc_sizeof(), "VllmDeformEncLayerDesc layout mismatch"
     assert ctypes.sizeof(VllmDeformDecLayerDesc) == L.vllm_deform_dec_layer_desc_sizeof(), "VllmDeformDecLayerDesc layout mismatch"
+    assert ctypes.sizeof(VllmDeformDecoderDesc) == L.vllm_deform_decoder_desc_sizeof(), "VllmDeformDecoderDesc layout mismatch"
     assert ctypes.sizeof(VllmVitDesc) == L.vllm_vit_desc_sizeof(), "VllmVitDesc layout mismatch"
     assert ctypes.sizeof(VllmVitLayer) == L.vllm_vit_layer_sizeof(), "VllmVitLayer layout mismatch"
     assert ctypes.sizeof(VllmBridgeDesc) == L.vllm_bridge_desc_sizeof(), "VllmBridgeDesc layout mismatch"

@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "orchestrate.hpp"
 #include "msda_layer.hpp"
+#include "deform_decoder_layer.hpp"
 
 namespace vllm {
 namespace {
@@ -44,7 +45,11 @@ DecWs dec_ws(const VllmDeformDecLayerDesc *d, long B, long Lq, long Lt, long S)
     return w;
 }
 
-int dec_check_desc(const VllmDeformDecLayerDesc *d)
+long g_calls = 0;
+
+}  // namespace
+
+int dec_layer_check_desc(const VllmDeformDecLayerDesc *d)
 {
     VLLM_REQUIRE(d, "deform_dec_layer: null descriptor");
     TRY(msda_layer_check_desc(&d->cross_attn));
@@ -67,7 +72,7 @@ int dec_check_desc(const VllmDeformDecLayerDesc *d)
     return VLLM_OK;
 }
 
-int dec_check_sizes(const VllmDeformDecLayerDesc *d, int B, int Lq, int Lt, int S)
+int dec_layer_check_sizes(const VllmDeformDecLayerDesc *d, int B, int Lq, int Lt, int S)
 {
     VLLM_REQUIRE(B >= 0 && Lq >= 0 && Lt >= 0 && S >= 0 && (long)B * Lq < (1L << 31) && (long)B * S < (1L << 31) && (long)B * Lt < (1L << 31),
                  "deform_dec_layer: B=%d Lq=%d Lt=%d S=%d (non-negative, B Lq, B Lt and B S below 2^31)", B, Lq, Lt, S);
@@ -79,38 +84,36 @@ int dec_check_sizes(const VllmDeformDecLayerDesc *d, int B, int Lq, int Lt, int 
     return VLLM_OK;
 }
 
-bool overlaps(const void *a, long abytes, const void *b, long bbytes)
+bool ranges_overlap(const void *a, long abytes, const void *b, long bbytes)
 {
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
     return a && b && a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
 }
 
-long g_calls = 0;
+long dec_layer_ws_bytes(const VllmDeformDecLayerDesc *d, int B, int Lq, int Lt, int S) { return dec_ws(d, B, Lq, Lt, S).total; }
 
-}  // namespace
-}  // namespace vllm
-
-using namespace vllm;
-
-extern "C" unsigned long vllm_deform_dec_layer_desc_sizeof(void) { return sizeof(VllmDeformDecLayerDesc); }
-extern "C" long vllm_deform_dec_layer_calls(void) { return g_calls; }
-
-extern "C" long vllm_deform_dec_layer_workspace_bytes(const VllmDeformDecLayerDesc *d, int B, int Lq, int Lt, int S)
+// the pieces of the workspace and the attention blocks' shape, as the checks and the launches both see them
+struct DecCall {
+    uint16_t *xp, *bufa, *bufb, *qk, *vb, *ctx, *tkv, *h;
+    char *attn;
+    int H, D;
+};
+static DecCall dec_call(const VllmDeformDecLayerDesc *d, const DecWs &w, void *workspace)
 {
-    if (dec_check_desc(d) != VLLM_OK || dec_check_sizes(d, B, Lq, Lt, S) != VLLM_OK) return -1;
-    if ((long)B * Lq == 0) return 0;
-    return dec_ws(d, B, Lq, Lt, S).total;
+    char *ws = (char *)workspace;
+    DecCall c;
+    c.xp = (uint16_t *)(ws + w.xp); c.bufa = (uint16_t *)(ws + w.a); c.bufb = (uint16_t *)(ws + w.b); c.qk = (uint16_t *)(ws + w.qk);
+    c.vb = (uint16_t *)(ws + w.v); c.ctx = (uint16_t *)(ws + w.ctx); c.tkv = (uint16_t *)(ws + w.tkv); c.h = (uint16_t *)(ws + w.h);
+    c.attn = ws + w.attn;
+    c.H = d->n_heads_sa;
+    c.D = d->has_self_attn || d->has_text_attn ? d->cross_attn.d_model / c.H : 32;
+    return c;
 }
 
-extern "C" int vllm_deform_dec_layer_forward(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, const uint16_t *query_pos,
-                                             const float *reference_points, const uint8_t *self_attn_mask, const uint16_t *memory_text,
-                                             const uint8_t *text_key_padding_mask, const uint16_t *memory, const uint8_t *memory_padding_mask,
-                                             const int64_t *spatial_shapes, const int64_t *level_start_index, int B, int Lq, int Lt, int S,
-                                             uint16_t *out, void *workspace, long workspace_bytes, vllm_stream_t stream)
+int dec_layer_check_call(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, const uint16_t *query_pos, const float *reference_points,
+                         const uint16_t *memory_text, const uint16_t *memory, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                         int B, int Lq, int Lt, int S, const uint16_t *out, const void *workspace, long workspace_bytes)
 {
-    TRY(dec_check_desc(d));
-    TRY(dec_check_sizes(d, B, Lq, Lt, S));
-    if ((long)B * Lq == 0) return VLLM_OK;
     const VllmMsdaLayerDesc &at = d->cross_attn;
     const bool sa = d->has_self_attn != 0, ta = d->has_text_attn != 0;
     VLLM_REQUIRE(S > 0 && (!ta || Lt > 0), "deform_dec_layer: S=%d Lt=%d (an empty memory or text)", S, Lt);
@@ -126,24 +129,37 @@ extern "C" int vllm_deform_dec_layer_forward(const VllmDeformDecLayerDesc *d, co
                               at.output_proj_b})
         VLLM_REQUIRE(aligned16(p), "deform_dec_layer: misaligned weight or bias (16 bytes)");
     const long R = (long)B * Lq;
-    const int C = at.d_model, F = d->d_ffn;
+    const int C = at.d_model;
     const long obytes = R * C * 2;
-    VLLM_REQUIRE(!overlaps(out, obytes, tgt, obytes) && !overlaps(out, obytes, query_pos, obytes) &&
-                     !overlaps(out, obytes, memory, (long)B * S * C * 2) && !(ta && overlaps(out, obytes, memory_text, (long)B * Lt * C * 2)),
+    VLLM_REQUIRE(!ranges_overlap(out, obytes, tgt, obytes) && !ranges_overlap(out, obytes, query_pos, obytes) &&
+                     !ranges_overlap(out, obytes, memory, (long)B * S * C * 2) && !(ta && ranges_overlap(out, obytes, memory_text, (long)B * Lt * C * 2)),
                  "deform_dec_layer: out overlaps an input (tgt / query_pos / memory_text / memory)");
     const DecWs w = dec_ws(d, B, Lq, Lt, S);
     VLLM_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= w.total,
                  "deform_dec_layer: workspace too small (%ld < %ld bytes) or misaligned", workspace_bytes, w.total);
-    char *ws = (char *)workspace;
-    uint16_t *xp = (uint16_t *)(ws + w.xp), *bufa = (uint16_t *)(ws + w.a), *bufb = (uint16_t *)(ws + w.b), *qk = (uint16_t *)(ws + w.qk),
-             *vb = (uint16_t *)(ws + w.v), *ctx = (uint16_t *)(ws + w.ctx), *tkv = (uint16_t *)(ws + w.tkv), *h = (uint16_t *)(ws + w.h);
-    const int H = d->n_heads_sa, D = sa || ta ? C / H : 32;
-    const float scale = 1.0f / sqrtf((float)D);
+    const DecCall c = dec_call(d, w, const_cast<void *>(workspace));
+    const uint16_t *qk = c.qk, *vb = c.vb, *ctx = c.ctx, *tkv = c.tkv;
+    const int H = c.H, D = c.D;
     // the attention kernel's own gate, asked before anything is enqueued (dense slices of the buffers above: it cannot refuse them)
     if (sa) TRY(mha_fwd_check(qk, (long)Lq * 2 * C, 2 * C, qk + C, (long)Lq * 2 * C, 2 * C, vb, (long)Lq * C, C, ctx, (long)Lq * C, C, B, Lq, Lq, H, D));
     if (ta) TRY(mha_fwd_check(vb, (long)Lq * C, C, tkv, (long)Lt * 2 * C, 2 * C, tkv + C, (long)Lt * 2 * C, 2 * C, ctx, (long)Lq * C, C, B, Lq, Lt, H, D));
-    ++g_calls;
-    hipStream_t st = (hipStream_t)stream;
+    return VLLM_OK;
+}
+
+int dec_layer_run(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, const uint16_t *query_pos, const float *reference_points,
+                  const uint8_t *self_attn_mask, const uint16_t *memory_text, const uint8_t *text_key_padding_mask, const uint16_t *memory,
+                  const uint8_t *memory_padding_mask, const int64_t *spatial_shapes, const int64_t *level_start_index, int B, int Lq, int Lt,
+                  int S, uint16_t *out, void *workspace, hipStream_t st)
+{
+    const VllmMsdaLayerDesc &at = d->cross_attn;
+    const bool sa = d->has_self_attn != 0, ta = d->has_text_attn != 0;
+    const long R = (long)B * Lq;
+    const int C = at.d_model, F = d->d_ffn;
+    const DecCall c = dec_call(d, dec_ws(d, B, Lq, Lt, S), workspace);
+    uint16_t *xp = c.xp, *bufa = c.bufa, *bufb = c.bufb, *qk = c.qk, *vb = c.vb, *ctx = c.ctx, *tkv = c.tkv, *h = c.h;
+    const int H = c.H, D = c.D;
+    const float scale = 1.0f / sqrtf((float)D);
+    vllm_stream_t stream = (vllm_stream_t)st;
 
     const uint16_t *cur = tgt;          // the running x
     const uint16_t *curp = tgt;         // x + pos
@@ -183,7 +199,7 @@ extern "C" int vllm_deform_dec_layer_forward(const VllmDeformDecLayerDesc *d, co
     {
         uint16_t *y = other();
         TRY(msda_layer_run(&at, curp, reference_points, memory, memory_padding_mask, spatial_shapes, level_start_index, B, Lq, S, y,
-                           msda_layer_bufs(&at, ws + w.attn, B, Lq, S), nullptr, st, cur));
+                           msda_layer_bufs(&at, c.attn, B, Lq, S), nullptr, st, cur));
         TRY(norm(y, d->ca_norm_w, d->ca_norm_b, d->ca_norm_eps, false));
         cur = y;
     }
@@ -192,4 +208,34 @@ extern "C" int vllm_deform_dec_layer_forward(const VllmDeformDecLayerDesc *d, co
     TRY(gemm(st, d->act == 0 ? EPI_RELU : EPI_GELU, cur, C, d->fc1_w, C, d->fc1_b, h, F, (int)R, F, C));
     TRY(gemm(st, EPI_RESIDUAL, h, F, d->fc2_w, F, d->fc2_b, y, C, (int)R, C, F, nullptr, cur, C));
     return vllm_add_layernorm_bf16(y, C, nullptr, 0, d->ffn_norm_w, d->ffn_norm_b, out, C, nullptr, 0, nullptr, 0, R, C, d->ffn_norm_eps, stream);
+}
+
+}  // namespace vllm
+
+using namespace vllm;
+
+extern "C" unsigned long vllm_deform_dec_layer_desc_sizeof(void) { return sizeof(VllmDeformDecLayerDesc); }
+extern "C" long vllm_deform_dec_layer_calls(void) { return g_calls; }
+
+extern "C" long vllm_deform_dec_layer_workspace_bytes(const VllmDeformDecLayerDesc *d, int B, int Lq, int Lt, int S)
+{
+    if (dec_layer_check_desc(d) != VLLM_OK || dec_layer_check_sizes(d, B, Lq, Lt, S) != VLLM_OK) return -1;
+    if ((long)B * Lq == 0) return 0;
+    return dec_layer_ws_bytes(d, B, Lq, Lt, S);
+}
+
+extern "C" int vllm_deform_dec_layer_forward(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, const uint16_t *query_pos,
+                                             const float *reference_points, const uint8_t *self_attn_mask, const uint16_t *memory_text,
+                                             const uint8_t *text_key_padding_mask, const uint16_t *memory, const uint8_t *memory_padding_mask,
+                                             const int64_t *spatial_shapes, const int64_t *level_start_index, int B, int Lq, int Lt, int S,
+                                             uint16_t *out, void *workspace, long workspace_bytes, vllm_stream_t stream)
+{
+    TRY(dec_layer_check_desc(d));
+    TRY(dec_layer_check_sizes(d, B, Lq, Lt, S));
+    if ((long)B * Lq == 0) return VLLM_OK;
+    TRY(dec_layer_check_call(d, tgt, query_pos, reference_points, memory_text, memory, spatial_shapes, level_start_index, B, Lq, Lt, S, out,
+                             workspace, workspace_bytes));
+    ++g_calls;
+    return dec_layer_run(d, tgt, query_pos, reference_points, self_attn_mask, memory_text, text_key_padding_mask, memory, memory_padding_mask,
+                         spatial_shapes, level_start_index, B, Lq, Lt, S, out, workspace, (hipStream_t)stream);
 }

@@ -14,8 +14,17 @@ inference forward of a bf16 module is ONE native call (``vllm_deform_dec_layer_f
 The UniPose layer is sequence-first (``tgt`` [nq, bs, C]) and the native entry batch-first: its mirror transposes ``tgt``,
 ``tgt_query_pos``, the reference points and ``memory`` on entry and the result on exit -- views where bs == 1, copies otherwise (the
 composed path's attention module makes the same copy of ``memory``).
+
+``GroundingDinoDecoder`` (...mask_dn.py:1725-1981) is the loop around the Grounding-DINO layers -- reference points times
+``valid_ratios``, the sine embedding and its MLP, ``layer_norm``, ``bbox_embed`` and the iterative box refinement -- with the same
+arrangement one level up: ``native_decoder = False`` (the default) runs the reference's statements, ``native_decoder = True`` makes the
+inference forward of a bf16 module ONE native call (``vllm_deform_decoder_forward``, csrc/deform_decoder.hip) wherever
+``native_decoder_reasons`` is empty.
 """
 import ctypes
+import dataclasses
+import math
+import weakref
 
 import torch
 from torch import nn
@@ -101,6 +110,36 @@ def native_layer_reasons(layer, parts, tgt, pos, reference_points, memory_text, 
     return why
 
 
+def _fill_layer_desc(desc, parts, C, ref_dim, keep):
+    """``desc`` (a VllmDeformDecLayerDesc) from a layer's ``_parts()``, everything but ``cross_attn.geometry``; the tensors whose
+    pointers it holds are appended to ``keep``"""
+    attn = parts["cross_attn"]
+    a = desc.cross_attn
+    a.d_model, a.n_heads, a.n_levels, a.n_points, a.ref_dim = C, attn.n_heads, attn.n_levels, attn.n_points, ref_dim
+    a.use_4d_normalizer = int(bool(getattr(attn, "use_4D_normalizer", False)))
+    sa, ta = parts["self_attn"], parts["text_attn"]
+    desc.d_ffn, desc.act = parts["fc1"].out_features, parts["act"]
+    desc.has_self_attn, desc.has_text_attn = int(sa is not None), int(ta is not None)
+    desc.n_heads_sa = sa.num_heads if sa is not None else ta.num_heads if ta is not None else 0
+    desc.ca_norm_eps, desc.ffn_norm_eps = parts["ca_norm"].eps, parts["ffn_norm"].eps
+
+    def put(struct, name, weight, bias):
+        w, b = _lib.aligned(weight.detach()), _lib.aligned(bias.detach())
+        keep.extend((w, b))
+        setattr(struct, name + "_w", w.data_ptr())
+        setattr(struct, name + "_b", b.data_ptr())
+    for name in _ATTN_LINEARS:
+        put(a, name, getattr(attn, name).weight, getattr(attn, name).bias)
+    for name, mod in (("ca_norm", parts["ca_norm"]), ("fc1", parts["fc1"]), ("fc2", parts["fc2"]), ("ffn_norm", parts["ffn_norm"])):
+        put(desc, name, mod.weight, mod.bias)
+    for pre, mha, norm in (("sa", sa, parts["sa_norm"]), ("text", ta, parts["text_norm"])):
+        if mha is not None:
+            put(desc, pre + "_in_proj", mha.in_proj_weight, mha.in_proj_bias)
+            put(desc, pre + "_out_proj", mha.out_proj.weight, mha.out_proj.bias)
+            put(desc, pre + "_norm", norm.weight, norm.bias)
+            setattr(desc, pre + "_norm_eps", norm.eps)
+
+
 def deform_dec_layer_forward(parts, tgt, pos, reference_points, self_attn_mask, memory_text, text_mask, memory, memory_padding_mask,
                              spatial_shapes, level_start_index):
     """One ``vllm_deform_dec_layer_forward`` call -> out [B, Lq, C].  Batch-first: ``tgt`` [B, Lq, C] bf16 on the GPU, ``pos`` the same or
@@ -124,31 +163,9 @@ def deform_dec_layer_forward(parts, tgt, pos, reference_points, self_attn_mask, 
         raise RuntimeError(f"deform_dec_layer_forward: padding mask {tuple(memory_padding_mask.shape)} must be ({B}, {S})")
     L = _lib.lib()
     desc = _lib.VllmDeformDecLayerDesc()
-    a = desc.cross_attn
-    a.d_model, a.n_heads, a.n_levels, a.n_points, a.ref_dim = C, attn.n_heads, n_levels, attn.n_points, ref_dim
-    a.use_4d_normalizer = int(bool(getattr(attn, "use_4D_normalizer", False)))
-    sa, ta = parts["self_attn"], parts["text_attn"]
-    desc.d_ffn, desc.act = parts["fc1"].out_features, parts["act"]
-    desc.has_self_attn, desc.has_text_attn = int(sa is not None), int(ta is not None)
-    desc.n_heads_sa = sa.num_heads if sa is not None else ta.num_heads if ta is not None else 0
-    desc.ca_norm_eps, desc.ffn_norm_eps = parts["ca_norm"].eps, parts["ffn_norm"].eps
     keep = []
-
-    def put(struct, name, weight, bias):
-        w, b = _lib.aligned(weight.detach()), _lib.aligned(bias.detach())
-        keep.extend((w, b))
-        setattr(struct, name + "_w", w.data_ptr())
-        setattr(struct, name + "_b", b.data_ptr())
-    for name in _ATTN_LINEARS:
-        put(a, name, getattr(attn, name).weight, getattr(attn, name).bias)
-    for name, mod in (("ca_norm", parts["ca_norm"]), ("fc1", parts["fc1"]), ("fc2", parts["fc2"]), ("ffn_norm", parts["ffn_norm"])):
-        put(desc, name, mod.weight, mod.bias)
-    for pre, mha, norm in (("sa", sa, parts["sa_norm"]), ("text", ta, parts["text_norm"])):
-        if mha is not None:
-            put(desc, pre + "_in_proj", mha.in_proj_weight, mha.in_proj_bias)
-            put(desc, pre + "_out_proj", mha.out_proj.weight, mha.out_proj.bias)
-            put(desc, pre + "_norm", norm.weight, norm.bias)
-            setattr(desc, pre + "_norm_eps", norm.eps)
+    _fill_layer_desc(desc, parts, C, ref_dim, keep)
+    a, sa, ta = desc.cross_attn, parts["self_attn"], parts["text_attn"]
     x = _lib.aligned(tgt)
     p = None if pos is None else _lib.aligned(pos)
     mem = _lib.aligned(memory)
@@ -486,3 +503,413 @@ class GroundingDinoDecoderLayer(nn.Module):
             outputs += (self_attn_weights, text_cross_attn_weights, cross_attn_weights)
 
         return outputs
+
+
+# ---- the Grounding-DINO decoder around the layer (modeling_ov_grounding_dino_mask_dn.py:1725-1981) ---------------------------------------
+def inverse_sigmoid(x, eps=1e-5):
+    """modeling_ov_grounding_dino_mask_dn.py:401-405"""
+    x = x.clamp(min=0, max=1)
+    x1 = x.clamp(min=eps)
+    x2 = (1 - x).clamp(min=eps)
+    return torch.log(x1 / x2)
+
+
+class GroundingDinoMLPPredictionHead(nn.Module):
+    """The DETR MLP head (modeling_ov_grounding_dino_mask_dn.py:3704-3720): ``layers.N`` are Linears, ReLU between them."""
+
+    def __init__(self, input_dim, hidden_dim, output_dim, num_layers):
+        super().__init__()
+        self.num_layers = num_layers
+        h = [hidden_dim] * (num_layers - 1)
+        self.layers = nn.ModuleList(nn.Linear(n, k) for n, k in zip([input_dim] + h, h + [output_dim]))
+
+    def forward(self, x):
+        for i, layer in enumerate(self.layers):
+            x = nn.functional.relu(layer(x)) if i < self.num_layers - 1 else layer(x)
+        return x
+
+
+@dataclasses.dataclass
+class GroundingDinoDecoderOutput:
+    """The fields of the reference's ModelOutput of the same name (:183-211), as a plain dataclass."""
+    last_hidden_state: torch.Tensor = None
+    intermediate_hidden_states: torch.Tensor = None
+    intermediate_reference_points: torch.Tensor = None
+    hidden_states: tuple = None
+    attentions: tuple = None
+
+
+def _box_heads(bbox_embed, n_layers, d_model):
+    """``bbox_embed`` as a list of n_layers three-layer heads of width d_model (entries may be one shared module), or None where it is
+    anything else"""
+    try:
+        heads = list(bbox_embed)
+    except TypeError:
+        return None
+    if len(heads) != n_layers:
+        return None
+    for h in heads:
+        lin = list(getattr(h, "layers", ()))
+        if getattr(h, "num_layers", None) != 3 or len(lin) != 3 or not all(isinstance(m, nn.Linear) and m.bias is not None for m in lin):
+            return None
+        if [tuple(m.weight.shape) for m in lin] != [(d_model, d_model), (d_model, d_model), (4, d_model)]:
+            return None
+    return heads
+
+
+_NATIVE_STATE = weakref.WeakKeyDictionary()   # GroundingDinoDecoder -> {device: (signature, descriptors and what they point to)}
+
+
+class GroundingDinoDecoder(nn.Module):
+    """The Grounding-DINO decoder (modeling_ov_grounding_dino_mask_dn.py:1725-1981): parameter names ``layer_norm``, ``layers.N.*`` and
+    ``reference_points_head.layers.{0,1}``; ``bbox_embed``, ``class_embed`` and ``query_scale`` are assigned from outside, as there.
+    ``config`` needs what GroundingDinoDecoderLayer needs, and ``decoder_layers`` and ``query_dim``; ``output_attentions``,
+    ``output_hidden_states`` and ``use_return_dict`` are read where ``forward`` is not told (defaults False, False, True).
+
+    With the class attribute ``native_decoder = False`` (the default) ``forward`` is the reference's statements, line for line, and every
+    layer honours its own ``native_layer``.  With ``native_decoder = True`` a call for which ``native_decoder_reasons`` is empty is ONE
+    ``vllm_deform_decoder_forward`` (csrc/deform_decoder.hip); every other call runs the composed statements unchanged.
+
+    The native call writes layer-major buffers, so ``intermediate_hidden_states`` [B, n_layers, Lq, C] and
+    ``intermediate_reference_points`` [B, n_layers, Lq, 4] come back as ``.transpose(0, 1)`` VIEWS of them: the shapes and values of the
+    reference's ``torch.stack(dim=1)``, but not contiguous.  ``last_hidden_state`` is ``intermediate_hidden_states[:, -1]``.  Reference
+    points may be fp32 or bf16: they are widened once on entry, kept fp32 through every layer and returned in the caller's dtype.
+    Descriptors and the ``dim_t`` table are remembered per device (and rebuilt when a parameter's storage changes); no weight is copied."""
+
+    native_decoder = False   # True: bf16 inference runs vllm_deform_decoder_forward where native_decoder_reasons() is empty
+
+    def __init__(self, config):
+        super().__init__()
+        self.config = config
+
+        self.dropout = config.dropout
+        self.layer_norm = nn.LayerNorm(config.d_model)
+        self.layers = nn.ModuleList([GroundingDinoDecoderLayer(config) for _ in range(config.decoder_layers)])
+        self.reference_points_head = GroundingDinoMLPPredictionHead(
+            config.query_dim // 2 * config.d_model, config.d_model, config.d_model, 2
+        )
+        self.gradient_checkpointing = False
+
+        # hack implementation for iterative bounding box refinement and two-stage Deformable DETR
+        self.bbox_embed = None
+        self.class_embed = None
+        self.query_scale = None
+
+    @staticmethod
+    def _dim_t(num_pos_feats, device):
+        temperature = 10000
+        dim_t = torch.arange(num_pos_feats, dtype=torch.float32, device=device)
+        dim_t = temperature ** (2 * torch.div(dim_t, 2, rounding_mode="floor") / num_pos_feats)
+        return dim_t
+
+    def get_proposal_pos_embed(self, proposals):
+        """Get the position embedding of the proposals."""
+        num_pos_feats = self.config.d_model // 2
+        scale = 2 * math.pi
+
+        dim_t = self._dim_t(num_pos_feats, proposals.device)
+        # batch_size, num_queries
+        pos_x = proposals[:, :, 0] * scale
+        pos_y = proposals[:, :, 1] * scale
+        # batch_size, num_queries, num_pos_feats
+        pos_x = pos_x[:, :, None] / dim_t
+        pos_y = pos_y[:, :, None] / dim_t
+        # batch_size, num_queries, num_pos_feats
+        pos_x = torch.stack((pos_x[:, :, 0::2].sin(), pos_x[:, :, 1::2].cos()), dim=3).flatten(2)
+        pos_y = torch.stack((pos_y[:, :, 0::2].sin(), pos_y[:, :, 1::2].cos()), dim=3).flatten(2)
+
+        if proposals.size(-1) == 2:
+            # batch_size, num_queries, num_pos_feats * 2
+            pos = torch.cat((pos_y, pos_x), dim=2)
+        elif proposals.size(-1) == 4:
+            w_embed = proposals[:, :, 2] * scale
+            pos_w = w_embed[:, :, None] / dim_t
+            # batch_size, num_queries, num_pos_feats
+            pos_w = torch.stack((pos_w[:, :, 0::2].sin(), pos_w[:, :, 1::2].cos()), dim=3).flatten(2)
+
+            h_embed = proposals[:, :, 3] * scale
+            pos_h = h_embed[:, :, None] / dim_t
+            # batch_size, num_queries, num_pos_feats
+            pos_h = torch.stack((pos_h[:, :, 0::2].sin(), pos_h[:, :, 1::2].cos()), dim=3).flatten(2)
+            # batch_size, num_queries, num_pos_feats * 4
+            pos = torch.cat((pos_y, pos_x, pos_w, pos_h), dim=2)
+        else:
+            raise ValueError("Unknown proposals shape(-1):{}".format(proposals.size(-1)))
+        return pos
+
+    def _own_params(self):
+        heads = _box_heads(self.bbox_embed, len(self.layers), self.config.d_model) if self.bbox_embed is not None else None
+        mods = [self.layer_norm] + list(self.reference_points_head.layers) + [m for h in (heads or ()) for m in h.layers]
+        return heads, [p for m in mods for p in m.parameters()]
+
+    def native_decoder_reasons(self, inputs_embeds, vision_encoder_hidden_states, vision_encoder_attention_mask=None,
+                               text_encoder_hidden_states=None, text_encoder_attention_mask=None, reference_points=None, spatial_shapes=None,
+                               level_start_index=None, valid_ratios=None, self_attn_mask=None, output_attentions=False,
+                               output_hidden_states=False):
+        """Every reason why ``vllm_deform_decoder_forward`` does not serve this call, as a list of strings (empty: it does): training mode;
+        something that requires grad under grad mode; ``output_attentions`` / ``output_hidden_states``; reference points that are not 4-d
+        (2-d ones turn 4-d after the first refinement: that loop stays composed); non-bf16 parameters or inputs, or CPU tensors;
+        ``query_scale``; a ``bbox_embed`` that is not None and not n_layers three-layer heads of width d_model; ``query_dim`` other than 4
+        or d_model / 2 not a multiple of 16; and, prefixed with the layer's name, every reason a layer gives."""
+        why = []
+        x, mem, ref, vr = inputs_embeds, vision_encoder_hidden_states, reference_points, valid_ratios
+        C, n_layers = self.config.d_model, len(self.layers)
+        if self.training:
+            why.append("training mode")
+        if output_attentions:
+            why.append("output_attentions: the attention weights stay inside the native call")
+        if output_hidden_states:
+            why.append("output_hidden_states: the un-normed hidden states stay inside the native call")
+        if self.query_scale is not None:
+            why.append("query_scale")
+        heads, params = self._own_params()
+        if self.bbox_embed is not None and heads is None:
+            why.append(f"bbox_embed: None or {n_layers} three-layer heads of width d_model")
+        if n_layers < 1 or self.config.query_dim != 4 or (C // 2) % 16 or C % 2:
+            why.append("query_dim 4, d_model / 2 a multiple of 16, at least one layer")
+        if any(p.dtype != torch.bfloat16 or not p.is_cuda for p in params):
+            why.append("parameters: bf16 on the GPU")
+        elif any(p.data_ptr() % 16 for p in params if p.numel() > 4) or any(p.data_ptr() % 16 for l in self.layers for p in l.parameters()):
+            why.append("parameters: 16-byte aligned storage")
+        if any(m.bias is None for m in self.reference_points_head.layers):
+            why.append("parameters: a Linear without bias")
+        if not (_is_gpu_bf16(x) and _is_gpu_bf16(mem)):
+            why.append("inputs_embeds / vision_encoder_hidden_states: bf16 CUDA tensors [B, ., C]")
+        if not (torch.is_tensor(ref) and ref.dim() == 3 and ref.shape[-1] == 4):
+            why.append("reference_points: [B, Lq, 4] (2-d reference points keep the composed path)")
+        elif not (ref.is_cuda and ref.dtype in (torch.float32, torch.bfloat16) and torch.is_tensor(x) and ref.shape[:2] == x.shape[:2]):
+            why.append("reference_points: an fp32 or bf16 CUDA tensor [B, Lq, 4]")
+        n_levels = getattr(self.layers[0].encoder_attn, "n_levels", 0) if n_layers else 0
+        if not (torch.is_tensor(vr) and vr.is_cuda and vr.dtype in (torch.float32, torch.bfloat16) and torch.is_tensor(x) and
+                tuple(vr.shape) == (x.shape[0], n_levels, 2)):
+            why.append("valid_ratios: an fp32 or bf16 CUDA tensor [B, n_levels, 2]")
+        if vision_encoder_attention_mask is not None and not (torch.is_tensor(vision_encoder_attention_mask) and
+                                                              vision_encoder_attention_mask.dtype == torch.bool):
+            why.append("vision_encoder_attention_mask: None or bool [B, S]")
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in params) or
+                                        any(torch.is_tensor(t) and t.requires_grad for t in (x, mem, ref, vr, text_encoder_hidden_states))):
+            why.append("requires_grad under grad mode: there is no native backward")
+        if torch.is_tensor(x) and x.dim() == 3 and torch.is_tensor(mem) and mem.dim() == 3 and torch.is_tensor(ref) and ref.dim() == 3:
+            ref_in = ref[:, :, None].expand(-1, -1, max(n_levels, 1), -1)
+            for i, layer in enumerate(self.layers):   # (query_pos has inputs_embeds' shape and dtype)
+                why += [f"layers.{i}: {r}" for r in layer.native_layer_reasons(x, x, ref_in, mem, text_encoder_hidden_states,
+                                                                                text_encoder_attention_mask, self_attn_mask, False)]
+        return why
+
+    def _native_state(self, device, heads, params):
+        """descriptors of this module on ``device``: built once, rebuilt when a parameter's storage has moved"""
+        sig = (tuple(p.data_ptr() for p in params), tuple(p.data_ptr() for l in self.layers for p in l.parameters()))
+        cache = _NATIVE_STATE.setdefault(self, {})
+        ent = cache.get(device)
+        if ent is not None and ent[0] == sig:
+            return ent[1]
+        C, n = self.config.d_model, len(self.layers)
+        keep = []
+        descs = (_lib.VllmDeformDecLayerDesc * n)()
+        for i, layer in enumerate(self.layers):
+            _fill_layer_desc(descs[i], layer._parts(), C, 4, keep)
+        d = _lib.VllmDeformDecoderDesc()
+        d.n_layers, d.n_pos_feats = n, C // 2
+        d.layer_norm_eps, d.inverse_sigmoid_eps = self.layer_norm.eps, 1e-5
+        d.layers = descs
+        l0, l1 = self.reference_points_head.layers
+        dim_t = self._dim_t(C // 2, device).contiguous()
+        d.ref_head_w0, d.ref_head_b0, d.ref_head_w1, d.ref_head_b1 = (t.data_ptr() for t in (l0.weight, l0.bias, l1.weight, l1.bias))
+        d.layer_norm_w, d.layer_norm_b, d.dim_t = self.layer_norm.weight.data_ptr(), self.layer_norm.bias.data_ptr(), dim_t.data_ptr()
+        boxes = None
+        if heads is not None:
+            boxes = (_lib.VllmBoxHead * n)()
+            for i, h in enumerate(heads):
+                (boxes[i].w0, boxes[i].b0, boxes[i].w1, boxes[i].b1, boxes[i].w2, boxes[i].b2) = (
+                    t.data_ptr() for m in h.layers for t in (m.weight, m.bias))
+            d.box_heads = boxes
+        state = dict(desc=d, layers=descs, boxes=boxes, dim_t=dim_t, keep=keep)
+        cache[device] = (sig, state)
+        return state
+
+    def _native_forward(self, x, mem, attention_mask, text, text_mask, reference_points, spatial_shapes, level_start_index, valid_ratios,
+                        self_attn_mask):
+        if level_pixels(spatial_shapes) != mem.shape[1]:   # the attention module's own check (...mask_dn.py:741)
+            raise ValueError("Make sure to align the spatial shapes with the sequence length of the encoder hidden states")
+        B, Lq, C = x.shape
+        S, Lt, n = mem.shape[1], text.shape[1], len(self.layers)
+        if tuple(mem.shape) != (B, S, C) or tuple(spatial_shapes.shape) != (valid_ratios.shape[1], 2) or \
+                level_start_index.numel() != valid_ratios.shape[1]:
+            raise RuntimeError(f"GroundingDinoDecoder: memory {tuple(mem.shape)} / spatial_shapes {tuple(spatial_shapes.shape)} / "
+                               f"level_start_index ({level_start_index.numel()}) vs inputs_embeds {tuple(x.shape)}")
+        if attention_mask is not None and tuple(attention_mask.shape) != (B, S):
+            raise RuntimeError(f"GroundingDinoDecoder: vision_encoder_attention_mask {tuple(attention_mask.shape)} must be ({B}, {S})")
+        L = _lib.lib()
+        heads, params = self._own_params()
+        st = self._native_state(x.device, heads, params)
+        geo = known_geometry(spatial_shapes, Lq)
+        for ld in st["layers"]:
+            ld.cross_attn.geometry = geo
+        xa, mema, texta = _lib.aligned(x), _lib.aligned(mem), _lib.aligned(text)
+        ref = _lib.aligned(reference_points.to(torch.float32))
+        vr = _lib.aligned(valid_ratios.to(torch.float32))
+        shapes = spatial_shapes.to(device=x.device, dtype=torch.int64).contiguous()
+        lsi = level_start_index.to(device=x.device, dtype=torch.int64).contiguous()
+        u8 = lambda m: None if m is None else m.to(device=x.device).to(torch.uint8).contiguous()
+        sam, tmask, pmask = u8(self_attn_mask), u8(text_mask), u8(None if attention_mask is None else ~attention_mask)
+        ws, wsb = _lib.sized_workspace(x.device, L.vllm_deform_decoder_workspace_bytes(ctypes.byref(st["desc"]), B, Lq, Lt, S),
+                                       "vllm_deform_decoder_workspace_bytes")
+        inter = torch.empty((n, B, Lq, C), dtype=torch.bfloat16, device=x.device)
+        irp = torch.empty((n, B, Lq, 4), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(L.vllm_deform_decoder_forward(ctypes.byref(st["desc"]), _lib.ptr(xa), _lib.ptr(ref), _lib.ptr(vr), _lib.ptr(sam),
+                                                     _lib.ptr(texta), _lib.ptr(tmask), _lib.ptr(mema), _lib.ptr(pmask), _lib.ptr(shapes),
+                                                     _lib.ptr(lsi), B, Lq, Lt, S, _lib.ptr(inter), _lib.ptr(irp), _lib.ptr(ws), wsb,
+                                                     _lib.current_stream(x.device)),
+                       "vllm_deform_decoder_forward")
+        return inter[-1], inter.transpose(0, 1), irp.to(reference_points.dtype).transpose(0, 1)
+
+    def forward(
+        self,
+        inputs_embeds,
+        vision_encoder_hidden_states,
+        mask_features,
+        vision_encoder_attention_mask=None,
+        text_encoder_hidden_states=None,
+        text_encoder_attention_mask=None,
+        reference_points=None,
+        spatial_shapes=None,
+        level_start_index=None,
+        valid_ratios=None,
+        self_attn_mask=None,
+        output_attentions=None,
+        output_hidden_states=None,
+        return_dict=None,
+    ):
+        """The reference's ``forward`` (:1792-1981; ``mask_features`` is not read there either).  Returns the reference's tuple
+        (last_hidden_state, intermediate_hidden_states, intermediate_reference_points[, hidden_states][, attentions]) or, with
+        ``return_dict``, a GroundingDinoDecoderOutput.  On the native route the two stacked tensors are non-contiguous views (class
+        docstring)."""
+        output_attentions = output_attentions if output_attentions is not None else getattr(self.config, "output_attentions", False)
+        output_hidden_states = (
+            output_hidden_states if output_hidden_states is not None else getattr(self.config, "output_hidden_states", False)
+        )
+        return_dict = return_dict if return_dict is not None else getattr(self.config, "use_return_dict", True)
+
+        if inputs_embeds is not None:
+            hidden_states = inputs_embeds
+
+        if self.native_decoder and not self.native_decoder_reasons(
+                inputs_embeds, vision_encoder_hidden_states, vision_encoder_attention_mask, text_encoder_hidden_states,
+                text_encoder_attention_mask, reference_points, spatial_shapes, level_start_index, valid_ratios, self_attn_mask,
+                output_attentions, output_hidden_states):
+            hidden_states, intermediate, intermediate_reference_points = self._native_forward(
+                inputs_embeds, vision_encoder_hidden_states, vision_encoder_attention_mask, text_encoder_hidden_states,
+                text_encoder_attention_mask, reference_points, spatial_shapes, level_start_index, valid_ratios, self_attn_mask)
+            if not return_dict:
+                return (hidden_states, intermediate, intermediate_reference_points)
+            return GroundingDinoDecoderOutput(
+                last_hidden_state=hidden_states,
+                intermediate_hidden_states=intermediate,
+                intermediate_reference_points=intermediate_reference_points,
+                hidden_states=None,
+                attentions=None,
+            )
+
+        # decoder layers
+        all_hidden_states = () if output_hidden_states else None
+        all_self_attns = () if output_attentions else None
+        all_attns = () if output_attentions else None
+        all_cross_attns_vision = () if (output_attentions and vision_encoder_hidden_states is not None) else None
+        all_cross_attns_text = () if (output_attentions and text_encoder_hidden_states is not None) else None
+        intermediate = ()
+        intermediate_reference_points = ()
+
+        for idx, decoder_layer in enumerate(self.layers):
+            if reference_points.shape[-1] == 4:
+                reference_points_input = (
+                    reference_points[:, :, None] * torch.cat([valid_ratios, valid_ratios], -1)[:, None]
+                )
+            else:
+                if reference_points.shape[-1] != 2:
+                    raise ValueError("Reference points' last dimension must be of size 2")
+                reference_points_input = reference_points[:, :, None] * valid_ratios[:, None]
+            query_pos = self.get_proposal_pos_embed(reference_points_input[:, :, 0, :]).to(hidden_states.dtype)
+            query_pos = self.reference_points_head(query_pos)
+
+            # In original implementation they apply layer norm before outputting intermediate hidden states
+            # Though that's not through between layers so the layers use as input the output of the previous layer
+            # withtout layer norm
+            if output_hidden_states:
+                all_hidden_states += (self.layer_norm(hidden_states),)
+
+            layer_outputs = decoder_layer(
+                hidden_states=hidden_states,
+                position_embeddings=query_pos,
+                reference_points=reference_points_input,
+                spatial_shapes=spatial_shapes,
+                level_start_index=level_start_index,
+                vision_encoder_hidden_states=vision_encoder_hidden_states,
+                vision_encoder_attention_mask=vision_encoder_attention_mask,
+                text_encoder_hidden_states=text_encoder_hidden_states,
+                text_encoder_attention_mask=text_encoder_attention_mask,
+                self_attn_mask=self_attn_mask,
+                output_attentions=output_attentions,
+            )
+
+            hidden_states = layer_outputs[0]
+
+            # hack implementation for iterative bounding box refinement
+            if self.bbox_embed is not None:
+                tmp = self.bbox_embed[idx](hidden_states)
+                if reference_points.shape[-1] == 4:
+                    new_reference_points = tmp + inverse_sigmoid(reference_points)
+                    new_reference_points = new_reference_points.sigmoid()
+                else:
+                    if reference_points.shape[-1] != 2:
+                        raise ValueError(
+                            f"Reference points' last dimension must be of size 2, but is {reference_points.shape[-1]}"
+                        )
+                    new_reference_points = tmp
+                    new_reference_points[..., :2] = tmp[..., :2] + inverse_sigmoid(reference_points)
+                    new_reference_points = new_reference_points.sigmoid()
+                reference_points = new_reference_points.detach()
+
+            intermediate += (self.layer_norm(hidden_states),)
+            intermediate_reference_points += (reference_points,)
+
+            if output_attentions:
+                all_self_attns += (layer_outputs[1],)
+
+                if text_encoder_hidden_states is not None:
+                    all_cross_attns_text += (layer_outputs[2],)
+
+                if vision_encoder_hidden_states is not None:
+                    all_cross_attns_vision += (layer_outputs[3],)
+
+        # Keep batch_size as first dimension
+        intermediate = torch.stack(intermediate, dim=1)
+        intermediate_reference_points = torch.stack(intermediate_reference_points, dim=1)
+        hidden_states = self.layer_norm(hidden_states)
+
+        # add hidden states from the last decoder layer
+        if output_hidden_states:
+            all_hidden_states += (hidden_states,)
+
+        if output_attentions:
+            all_attns += (all_self_attns, all_cross_attns_text, all_cross_attns_vision)
+
+        if not return_dict:
+            return tuple(
+                v
+                for v in [
+                    hidden_states,
+                    intermediate,
+                    intermediate_reference_points,
+                    all_hidden_states,
+                    all_attns,
+                ]
+                if v is not None
+            )
+        return GroundingDinoDecoderOutput(
+            last_hidden_state=hidden_states,
+            intermediate_hidden_states=intermediate,
+            intermediate_reference_points=intermediate_reference_points,
+            hidden_states=all_hidden_states,
+            attentions=all_attns,
+        )
