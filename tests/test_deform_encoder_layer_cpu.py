@@ -1,6 +1,7 @@
 """CPU: the boundary of the native deformable encoder layer (include/vllm_hip.h, section f2b) -- symbols, descriptor layout, the size
 query, the argument gates (refused calls only, fake pointers: nothing is dereferenced, no device is touched), and the module mirrors
-where no GPU is needed: the cases' own conditions, the switch on CPU tensors, the layer chain with the switch off."""
+where no GPU is needed: the cases' own conditions, the switch on CPU tensors, the layer chain with the switch off, and every reason
+``native_layer_reasons`` has to say no (in the decoder layers' words where the condition is shared)."""
 import ctypes
 import re
 import subprocess
@@ -264,3 +265,118 @@ def test_encoder_layers_forward_with_the_switch_off_is_the_plain_loop(flavour, w
         one = E.encoder_layers_forward(layers[:1], t["src"], t["pos"], t["reference_points"], t["spatial_shapes"], t["level_start_index"],
                                        t["padding_mask"])
     assert (one.double() - ref).abs().max().item() <= 1e-4 * ref.abs().max().item()          # fp32 against the fp64 yardstick
+
+
+def reasons(flavour, m, t, **kw):
+    return m.native_layer_reasons(t["src"], t["pos"], t["reference_points"], **kw)
+
+
+DEVICE_ONLY = ["src: a bf16 CUDA tensor [B, S, C]", "pos / query_in: bf16 CUDA tensors of src's shape", "parameters: bf16 on the GPU",
+               "self-attention: msda_layer_fused_ok"]
+
+
+@pytest.mark.parametrize("flavour", I.FLAVOURS)
+def test_every_reason_to_keep_the_composed_path(flavour):
+    """CPU tensors: a frozen bf16 module on bf16 inputs has the device reasons and no other; every other condition adds its own reason
+    when, and only when, it is broken; ``native_layer_applies`` is ``not native_layer_reasons`` throughout."""
+    def frozen(**kw):
+        mod = I.as_bf16(I.make_layer(flavour, "small", **kw), "cpu")
+        for p in mod.parameters():
+            p.requires_grad_(False)
+        return mod
+
+    m = frozen()
+    t = I.to(I.make_inputs("small"), "cpu")
+    assert reasons(flavour, m, t) == DEVICE_ONLY
+    assert reasons(flavour, m, dict(t, pos=None)) == [r for r in DEVICE_ONLY if not r.startswith("pos")]
+
+    def extra(mod=m, tt=t, **kw):
+        got = reasons(flavour, mod, tt, **kw)
+        assert got and not mod.native_layer_applies(tt["src"], tt["pos"], tt["reference_points"], **kw)
+        return [r for r in got if r not in DEVICE_ONLY]
+
+    assert extra() == []
+    # the switch test's case (fp32 tensors on the CPU, an fp32 module): the input's own reason comes first
+    f32, t32 = I.make_layer(flavour, "small"), I.to(I.make_inputs("small"), "cpu", torch.float32)
+    assert not f32.native_layer_applies(t32["src"], t32["pos"], t32["reference_points"])
+    assert reasons(flavour, f32, t32)[0] == DEVICE_ONLY[0] and "parameters: bf16 on the GPU" in reasons(flavour, f32, t32)
+    grad = "requires_grad under grad mode: there is no native backward"
+    for p in m.parameters():
+        p.requires_grad_(True)
+    with torch.enable_grad():
+        assert extra() == [grad]
+    with torch.no_grad():
+        assert extra() == []
+    for p in m.parameters():
+        p.requires_grad_(False)
+    with torch.enable_grad():
+        assert extra(tt=dict(t, src=t["src"].clone().requires_grad_(True))) == [grad]
+        assert extra(tt=dict(t, pos=t["pos"].clone().requires_grad_(True))) == [grad]
+    m.train()
+    assert extra() == ["active dropout"]
+    m.eval()
+    assert extra(frozen(dropout=0.0).train()) == []
+    assert extra(frozen(activation="prelu" if flavour == "unipose" else "silu")) == ["activation: relu or gelu"]
+    ref4 = torch.cat([t["reference_points"], torch.full_like(t["reference_points"], 0.2)], -1)
+    assert extra(tt=dict(t, reference_points=ref4)) == ["reference_points: last dim 2"]
+    assert extra(tt=dict(t, reference_points=None)) == ["reference_points: last dim 2"]
+    assert extra(tt=dict(t, pos=t["pos"][:, :-1])) == []          # (the pos reason is among the device ones already)
+    assert extra(tt=dict(t, src=t["src"][0])) == [] and reasons(flavour, m, dict(t, src=t["src"][0])) == DEVICE_ONLY[:1]
+    broken = frozen()
+    (broken.linear1 if flavour == "unipose" else broken.fc1).bias = None
+    assert extra(broken) == ["parameters: a Linear / LayerNorm without bias"]
+    if flavour == "gdino":
+        assert extra(output_attentions=True) == ["output_attentions: the attention weights stay inside the native call"]
+    meta = I.to(t, "meta")                                         # decided without touching data
+    assert reasons(flavour, m, meta)[0] == DEVICE_ONLY[0]
+
+
+def test_d_model_and_d_ffn_conditions():
+    t = I.to(I.make_inputs("small"), "cpu")
+    m = E.DeformableTransformerEncoderLayer(d_model=t["src"].shape[-1], d_ffn=100, n_levels=t["reference_points"].shape[2])
+    assert "d_model a multiple of 64 up to 512, d_ffn a multiple of 64" in reasons("unipose", m, t)
+
+
+class FakeCuda(torch.Tensor):
+    """a CPU tensor that says it is on the GPU: the reasons are decided from dtypes, shapes and flags alone"""
+    @property
+    def is_cuda(self):
+        return True
+
+
+def fake_inputs(t):
+    return {k: v.as_subclass(FakeCuda) if torch.is_tensor(v) else v for k, v in t.items()}
+
+
+def fake_module(m):
+    """a frozen bf16 copy of ``m`` whose parameters say they are on the GPU"""
+    m = I.as_bf16(m, "cpu")
+    for mod in m.modules():
+        for k, p in list(mod._parameters.items()):
+            if p is not None:
+                mod._parameters[k] = nn.Parameter(p.data, requires_grad=False).as_subclass(FakeCuda)
+    return m
+
+
+@pytest.mark.parametrize("flavour", I.FLAVOURS)
+def test_encoder_and_decoder_layers_name_a_shared_condition_alike(flavour):
+    """Tensors and parameters that say they are on the GPU: both layers have nothing to object to, and a parameter left in fp32, a
+    dropout that training mode applies and an activation outside relu / gelu draw the same one string from both."""
+    import deform_decoder_layer_inputs as DI
+    te, td = fake_inputs(I.to(I.make_inputs("small"), "cpu")), fake_inputs(DI.to(DI.make_inputs("small"), "cpu"))
+
+    def both(change=lambda m: m, **kw):
+        with torch.no_grad():
+            enc, dec = (change(fake_module(X.make_layer(flavour, "small", **kw))) for X in (I, DI))
+            assert enc.native_layer_applies(te["src"], te["pos"], te["reference_points"]) == (not reasons(flavour, enc, te))
+            return reasons(flavour, enc, te), DI.applies(flavour, dec, td)
+
+    def fp32_weight(m):
+        fc2 = m.linear2 if flavour == "unipose" else m.fc2
+        fc2.weight.data = fc2.weight.data.float()
+        return m
+
+    assert both() == ([], [])
+    assert both(fp32_weight) == (["parameters: bf16 on the GPU"],) * 2
+    assert both(lambda m: m.train()) == (["active dropout"],) * 2
+    assert both(activation="prelu" if flavour == "unipose" else "silu") == (["activation: relu or gelu"],) * 2

@@ -318,6 +318,9 @@ def test_routes_that_keep_the_composed_path(flavour, switch):
     assert composed_only(f32, I.to(I.make_inputs("small"), DEV, torch.float32)).dtype == torch.float32
     t4 = dict(t, reference_points=torch.cat([t["reference_points"], torch.full_like(t["reference_points"], 0.2)], -1))
     assert not m.native_layer_applies(t4["src"], t4["pos"], t4["reference_points"])
+    with torch.no_grad():
+        assert m.native_layer_reasons(t4["src"], t4["pos"], t4["reference_points"]) == ["reference_points: last dim 2"]
+        assert m.native_layer_reasons(t["src"], t["pos"], t["reference_points"]) == []
     composed_only(m, t4)                                     # reference_points with last dim 4
     if flavour == "unipose":
         pre = I.as_bf16(I.make_layer(flavour, "small", activation="prelu"), DEV)

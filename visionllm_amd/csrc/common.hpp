@@ -61,7 +61,8 @@ static inline int device_cus()
     }
     return v;
 }
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }   // (NULL passes: optional operands)
+static inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- bf16 <-> f32 (device) -------------------------------------------------------------------------
@@ -83,6 +84,17 @@ typedef float float4_t __attribute__((ext_vector_type(4)));
 typedef float float2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t uint4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t uint2_t __attribute__((ext_vector_type(2)));
+
+// eight bf16 in one 16-byte vector <-> eight floats
+__device__ __forceinline__ void unpack8(const uint4_t &q, float *v)
+{
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { v[2 * e] = bf16lo_to_f32(q[e]); v[2 * e + 1] = bf16hi_to_f32(q[e]); }
+}
+__device__ __forceinline__ uint4_t pack8(const float *v)
+{
+    return (uint4_t){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+}
 
 // sum over the wave, in every lane (a scalar register): four DPP steps inside the rows of 16 lanes (quad butterfly, half mirror, mirror),
 // lane 15 of rows 0 / 2 onto rows 1 / 3, lane 31 onto the upper half, lane 63 read out.  (Rounds 1-4: six dependent ds_bpermute round

@@ -12,19 +12,10 @@
 #include "common.hpp"
 #include "orchestrate.hpp"
 #include "deform_decoder_layer.hpp"
+#include "deform_blocks.hpp"
 
 namespace vllm {
 namespace {
-
-__device__ __forceinline__ void unpack8(const uint4_t &q, float *v)
-{
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[2 * e] = bf16lo_to_f32(q[e]); v[2 * e + 1] = bf16hi_to_f32(q[e]); }
-}
-__device__ __forceinline__ uint4_t pack8(const float *v)
-{
-    return (uint4_t){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
-}
 
 // A lane owns 8 consecutive outputs of one sine row ([y | x | w | h] groups of P, P % 8 == 0: a chunk lies in one group), so a row is
 // P / 2 lanes and a store 16 bytes.  The lanes of a row also write its L products ref * valid_ratios, one float4 each.  fp32 as the
@@ -148,8 +139,6 @@ int box_refine_launch(const uint16_t *h, int ldh, const uint16_t *W, const uint1
     VLLM_CHECK_LAUNCH("box_refine_kernel");
     return VLLM_OK;
 }
-
-bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 
 struct DecoderWs {
     long layer, layer_bytes;   // one layer's workspace, the largest of the layers', reused by every layer
@@ -312,9 +301,10 @@ extern "C" int vllm_deform_decoder_forward(const VllmDeformDecoderDesc *d, const
         // :1907-1921
         TRY(dec_layer_run(&d->layers[l], x, qpos, rpi, self_attn_mask, memory_text, text_key_padding_mask, memory, memory_padding_mask,
                           spatial_shapes, level_start_index, B, Lq, Lt, S, y, ws + w.layer, st));
-        // :1939
-        TRY(vllm_add_layernorm_bf16(y, C, nullptr, 0, d->layer_norm_w, d->layer_norm_b, intermediate + (long)l * R * C, C, nullptr, 0, nullptr, 0, R,
-                                    C, d->layer_norm_eps, stream));
+        // :1939 (no checks of its own: y is a piece of the workspace, layer_norm_w / _b and intermediate are 16-byte aligned by the
+        // checks above, a layer's block of intermediate is R C 2 bytes, C a multiple of 64 in 64 .. 512 by dec_layer_check_desc; R > 0)
+        TRY(add_layernorm_launch(y, C, nullptr, 0, d->layer_norm_w, d->layer_norm_b, intermediate + (long)l * R * C, C, nullptr, 0, nullptr, 0, R,
+                                 C, d->layer_norm_eps, st));
         // :1924-1937, :1940
         float *nref = intermediate_reference_points + (long)l * R * 4;
         if (d->box_heads) {

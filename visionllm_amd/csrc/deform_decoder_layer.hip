@@ -7,7 +7,7 @@
 //            GroundingDinoDecoderLayer.forward          grounding_dino/modeling_ov_grounding_dino_mask_dn.py:1332-1407.
 //
 // One call, one stream, a caller workspace.  The launches, in order (blocks 1 and 2 only where the descriptor has them):
-//   vllm_add_bf16            xp = tgt + pos, once: every later `x + pos` is the y_pos output of the LayerNorm in front of its reader
+//   add_bf16                 xp = tgt + pos, once: every later `x + pos` is the y_pos output of the LayerNorm in front of its reader
 //   1. GEMM N = 2C on q with in_proj_w[0:2C] -> [q | k];  GEMM N = C on tgt with in_proj_w[2C:3C] -> v;  mha (mha.hip) on the slices;
 //      out_proj with `tgt` added in its epilogue (EPI_RESIDUAL);  add_layernorm in place, y_pos -> xp
 //   2. GEMM N = C on xp with in_proj_w[0:C] -> q;  GEMM N = 2C on memory_text with in_proj_w[C:3C] -> [k | v];  mha;  out_proj + residual;
@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "orchestrate.hpp"
 #include "msda_layer.hpp"
+#include "deform_blocks.hpp"
 #include "deform_decoder_layer.hpp"
 
 namespace vllm {
@@ -45,6 +46,11 @@ DecWs dec_ws(const VllmDeformDecLayerDesc *d, long B, long Lq, long Lt, long S)
     return w;
 }
 
+FfnBlock dec_ffn(const VllmDeformDecLayerDesc *d)
+{
+    return {d->fc1_w, d->fc1_b, d->fc2_w, d->fc2_b, d->ffn_norm_w, d->ffn_norm_b, d->act, d->d_ffn, d->ffn_norm_eps};
+}
+
 long g_calls = 0;
 
 }  // namespace
@@ -56,18 +62,16 @@ int dec_layer_check_desc(const VllmDeformDecLayerDesc *d)
     const VllmMsdaLayerDesc &at = d->cross_attn;
     const int C = at.d_model;
     VLLM_REQUIRE(C >= 64 && C <= 512 && C % 64 == 0, "deform_dec_layer: d_model=%d must be a multiple of 64 in 64 .. 512 (the LayerNorm kernel's rows)", C);
-    VLLM_REQUIRE(d->d_ffn > 0 && d->d_ffn % 64 == 0, "deform_dec_layer: d_ffn=%d must be a positive multiple of 64", d->d_ffn);
-    VLLM_REQUIRE(d->act == 0 || d->act == VLLM_EPI_GELU, "deform_dec_layer: unknown act %d (0 = ReLU, VLLM_EPI_GELU = erf GELU)", d->act);
+    TRY(ffn_check("deform_dec_layer", dec_ffn(d)));
     if (d->has_self_attn || d->has_text_attn)
         VLLM_REQUIRE(d->n_heads_sa >= 1 && C % d->n_heads_sa == 0 && (C / d->n_heads_sa == 32 || C / d->n_heads_sa == 64),
                      "deform_dec_layer: n_heads_sa=%d with d_model=%d (head dim 32 or 64)", d->n_heads_sa, C);
-    VLLM_REQUIRE(d->sa_norm_eps >= 0.f && d->text_norm_eps >= 0.f && d->ca_norm_eps >= 0.f && d->ffn_norm_eps >= 0.f, "deform_dec_layer: negative eps");
+    VLLM_REQUIRE(d->sa_norm_eps >= 0.f && d->text_norm_eps >= 0.f && d->ca_norm_eps >= 0.f, "deform_dec_layer: negative eps");
     VLLM_REQUIRE(!d->has_self_attn || (d->sa_in_proj_w && d->sa_in_proj_b && d->sa_out_proj_w && d->sa_out_proj_b && d->sa_norm_w && d->sa_norm_b),
                  "deform_dec_layer: missing weights (self-attention)");
     VLLM_REQUIRE(!d->has_text_attn || (d->text_in_proj_w && d->text_in_proj_b && d->text_out_proj_w && d->text_out_proj_b && d->text_norm_w && d->text_norm_b),
                  "deform_dec_layer: missing weights (text attention)");
-    VLLM_REQUIRE(d->ca_norm_w && d->ca_norm_b && d->fc1_w && d->fc1_b && d->fc2_w && d->fc2_b && d->ffn_norm_w && d->ffn_norm_b && at.value_proj_b &&
-                     at.sampling_offsets_b && at.attention_weights_b && at.output_proj_b,
+    VLLM_REQUIRE(d->ca_norm_w && d->ca_norm_b && at.value_proj_b && at.sampling_offsets_b && at.attention_weights_b && at.output_proj_b,
                  "deform_dec_layer: missing weights");
     return VLLM_OK;
 }
@@ -82,12 +86,6 @@ int dec_layer_check_sizes(const VllmDeformDecLayerDesc *d, int B, int Lq, int Lt
     VLLM_REQUIRE(!d->has_text_attn || (long)B * Lt * 2 * d->cross_attn.d_model * 2 < (1L << 31),
                  "deform_dec_layer: B Lt=%ld rows of the text's [k | v] reach 2^31 bytes", (long)B * Lt);
     return VLLM_OK;
-}
-
-bool ranges_overlap(const void *a, long abytes, const void *b, long bbytes)
-{
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a && b && a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
 }
 
 long dec_layer_ws_bytes(const VllmDeformDecLayerDesc *d, int B, int Lq, int Lt, int S) { return dec_ws(d, B, Lq, Lt, S).total; }
@@ -124,10 +122,9 @@ int dec_layer_check_call(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, c
                  "deform_dec_layer: misaligned tgt / query_pos / memory_text / memory / out (16 bytes) or reference_points (8 bytes, 16 with ref_dim 4)");
     for (const uint16_t *p : {d->sa_in_proj_w, d->sa_in_proj_b, d->sa_out_proj_w, d->sa_out_proj_b, d->sa_norm_w, d->sa_norm_b, d->text_in_proj_w,
                               d->text_in_proj_b, d->text_out_proj_w, d->text_out_proj_b, d->text_norm_w, d->text_norm_b, d->ca_norm_w, d->ca_norm_b,
-                              d->fc1_w, d->fc1_b, d->fc2_w, d->fc2_b, d->ffn_norm_w, d->ffn_norm_b, at.value_proj_w, at.value_proj_b,
-                              at.sampling_offsets_w, at.sampling_offsets_b, at.attention_weights_w, at.attention_weights_b, at.output_proj_w,
-                              at.output_proj_b})
+                              d->fc1_w, d->fc1_b, d->fc2_w, d->fc2_b, d->ffn_norm_w, d->ffn_norm_b})
         VLLM_REQUIRE(aligned16(p), "deform_dec_layer: misaligned weight or bias (16 bytes)");
+    for (const uint16_t *p : msda_weights(at)) VLLM_REQUIRE(aligned16(p), "deform_dec_layer: misaligned weight or bias (16 bytes)");
     const long R = (long)B * Lq;
     const int C = at.d_model;
     const long obytes = R * C * 2;
@@ -154,21 +151,25 @@ int dec_layer_run(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, const ui
     const VllmMsdaLayerDesc &at = d->cross_attn;
     const bool sa = d->has_self_attn != 0, ta = d->has_text_attn != 0;
     const long R = (long)B * Lq;
-    const int C = at.d_model, F = d->d_ffn;
+    const int C = at.d_model;
     const DecCall c = dec_call(d, dec_ws(d, B, Lq, Lt, S), workspace);
-    uint16_t *xp = c.xp, *bufa = c.bufa, *bufb = c.bufb, *qk = c.qk, *vb = c.vb, *ctx = c.ctx, *tkv = c.tkv, *h = c.h;
+    uint16_t *xp = c.xp, *bufa = c.bufa, *bufb = c.bufb, *qk = c.qk, *vb = c.vb, *ctx = c.ctx, *tkv = c.tkv;
     const int H = c.H, D = c.D;
     const float scale = 1.0f / sqrtf((float)D);
-    vllm_stream_t stream = (vllm_stream_t)st;
 
+    // (the launchers without the public entries' checks: dec_layer_check_desc has C a multiple of 64 in 64 .. 512 and the norms' pointers,
+    // dec_layer_check_call tgt / query_pos / out and every weight 16-byte aligned; x, y and xp are 256-byte aligned workspace, dense rows; R > 0)
     const uint16_t *cur = tgt;          // the running x
     const uint16_t *curp = tgt;         // x + pos
-    if (query_pos) { TRY(vllm_add_bf16(tgt, query_pos, xp, R * C, stream)); curp = xp; }
+    if (query_pos) { TRY(add_launch(tgt, query_pos, xp, R * C, st)); curp = xp; }
     auto other = [&]() { return cur == bufa ? bufb : bufa; };
-    // the LayerNorm behind a block, in place, with the next block's x + pos
-    auto norm = [&](uint16_t *x, const uint16_t *nw, const uint16_t *nb, float eps, bool want_pos) {
+    // the tail of an attention block whose residual sum is in y: the LayerNorm in place, with x + pos for the block behind it
+    auto finish_block = [&](uint16_t *y, const uint16_t *nw, const uint16_t *nb, float eps, bool want_pos) {
         const bool yp = want_pos && query_pos;
-        return vllm_add_layernorm_bf16(x, C, nullptr, 0, nw, nb, x, C, yp ? query_pos : nullptr, C, yp ? xp : nullptr, C, R, C, eps, stream);
+        TRY(add_layernorm_launch(y, C, nullptr, 0, nw, nb, y, C, yp ? query_pos : nullptr, C, yp ? xp : nullptr, C, R, C, eps, st));
+        cur = y;
+        if (want_pos) curp = query_pos ? xp : y;
+        return VLLM_OK;
     };
 
     // 1. self-attention of the queries (modeling_unipose.py:3280-3284; ...mask_dn.py:1349-1356)
@@ -179,9 +180,7 @@ int dec_layer_run(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, const ui
                            nullptr, B, Lq, Lq, H, D, scale, st));
         uint16_t *y = other();
         TRY(gemm(st, EPI_RESIDUAL, ctx, C, d->sa_out_proj_w, C, d->sa_out_proj_b, y, C, (int)R, C, C, nullptr, cur, C));
-        TRY(norm(y, d->sa_norm_w, d->sa_norm_b, d->sa_norm_eps, true));
-        cur = y;
-        if (query_pos) curp = xp; else curp = y;
+        TRY(finish_block(y, d->sa_norm_w, d->sa_norm_b, d->sa_norm_eps, true));
     }
     // 2. text cross-attention (:3290-3294; :1361-1371)
     if (ta) {
@@ -191,23 +190,17 @@ int dec_layer_run(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, const ui
                            text_key_padding_mask, B, Lq, Lt, H, D, scale, st));
         uint16_t *y = other();
         TRY(gemm(st, EPI_RESIDUAL, ctx, C, d->text_out_proj_w, C, d->text_out_proj_b, y, C, (int)R, C, C, nullptr, cur, C));
-        TRY(norm(y, d->text_norm_w, d->text_norm_b, d->text_norm_eps, true));
-        cur = y;
-        if (query_pos) curp = xp; else curp = y;
+        TRY(finish_block(y, d->text_norm_w, d->text_norm_b, d->text_norm_eps, true));
     }
     // 3. deformable cross-attention over the memory (:3303-3309; :1377-1391): the residual goes into output_proj's epilogue
     {
         uint16_t *y = other();
         TRY(msda_layer_run(&at, curp, reference_points, memory, memory_padding_mask, spatial_shapes, level_start_index, B, Lq, S, y,
                            msda_layer_bufs(&at, c.attn, B, Lq, S), nullptr, st, cur));
-        TRY(norm(y, d->ca_norm_w, d->ca_norm_b, d->ca_norm_eps, false));
-        cur = y;
+        TRY(finish_block(y, d->ca_norm_w, d->ca_norm_b, d->ca_norm_eps, false));
     }
-    // 4. FFN (:3241-3248; :1394-1400)
-    uint16_t *y = other();
-    TRY(gemm(st, d->act == 0 ? EPI_RELU : EPI_GELU, cur, C, d->fc1_w, C, d->fc1_b, h, F, (int)R, F, C));
-    TRY(gemm(st, EPI_RESIDUAL, h, F, d->fc2_w, F, d->fc2_b, y, C, (int)R, C, F, nullptr, cur, C));
-    return vllm_add_layernorm_bf16(y, C, nullptr, 0, d->ffn_norm_w, d->ffn_norm_b, out, C, nullptr, 0, nullptr, 0, R, C, d->ffn_norm_eps, stream);
+    // 4. FFN (:3241-3248; :1394-1400), the whole intermediate at once
+    return ffn_block_run(st, dec_ffn(d), cur, R, C, c.h, R, other(), out, nullptr, nullptr);
 }
 
 }  // namespace vllm

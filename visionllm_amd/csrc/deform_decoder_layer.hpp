@@ -17,7 +17,5 @@ int dec_layer_run(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, const ui
                   const uint8_t *self_attn_mask, const uint16_t *memory_text, const uint8_t *text_key_padding_mask, const uint16_t *memory,
                   const uint8_t *memory_padding_mask, const int64_t *spatial_shapes, const int64_t *level_start_index, int B, int Lq, int Lt,
                   int S, uint16_t *out, void *workspace, hipStream_t st);
-// true where [a, a + abytes) and [b, b + bbytes) share a byte (either pointer null: false)
-bool ranges_overlap(const void *a, long abytes, const void *b, long bbytes);
 
 }  // namespace vllm

@@ -15,19 +15,10 @@
 #include <stdlib.h>
 #include "orchestrate.hpp"
 #include "msda_layer.hpp"
+#include "deform_blocks.hpp"
 
 namespace vllm {
 namespace {
-
-__device__ __forceinline__ void unpack8(const uint4_t &q, float *v)
-{
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[2 * e] = bf16lo_to_f32(q[e]); v[2 * e + 1] = bf16hi_to_f32(q[e]); }
-}
-__device__ __forceinline__ uint4_t pack8(const float *v)
-{
-    return (uint4_t){pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
-}
 
 // y = LayerNorm(x + res) * w + b over rows of C <= 8 G elements; y_pos = bf16(bf16(y) + pos).  G lanes share a row (32: two rows per
 // wave, 64: one) and lane j of the group owns the 16-byte chunk j, so a row is one load per lane whatever C is; lanes behind the row's
@@ -123,6 +114,8 @@ __global__ __launch_bounds__(256) void add_bf16_kernel(const uint16_t *__restric
     for (long k = n8 * 8 + t; k < n; k += stride) out[k] = f32_to_bf16(bf16_to_f32(a[k]) + bf16_to_f32(b[k]));
 }
 
+}  // namespace
+
 int add_layernorm_launch(const uint16_t *x, int ldx, const uint16_t *res, int ldr, const uint16_t *w, const uint16_t *b, uint16_t *y, int ldy,
                          const uint16_t *pos, int ldp, uint16_t *y_pos, int ldq, long rows, int C, float eps, hipStream_t st)
 {
@@ -144,8 +137,28 @@ int add_launch(const uint16_t *a, const uint16_t *b, uint16_t *out, long n, hipS
     return VLLM_OK;
 }
 
-// what vllm_add_layernorm_bf16 and the layer's two norms ask of a row operand: 16-byte aligned base, row stride a multiple of 8 and >= C
-bool row_operand_ok(const void *p, int ld, int C) { return aligned16(p) && ld >= C && ld % 8 == 0; }
+int ffn_check(const char *who, const FfnBlock &k)
+{
+    VLLM_REQUIRE(k.d_ffn > 0 && k.d_ffn % 64 == 0, "%s: d_ffn=%d must be a positive multiple of 64", who, k.d_ffn);
+    VLLM_REQUIRE(k.act == 0 || k.act == VLLM_EPI_GELU, "%s: unknown act %d (0 = ReLU, VLLM_EPI_GELU = erf GELU)", who, k.act);
+    VLLM_REQUIRE(k.eps >= 0.f, "%s: negative eps", who);
+    VLLM_REQUIRE(k.fc1_w && k.fc1_b && k.fc2_w && k.fc2_b && k.norm_w && k.norm_b, "%s: missing weights", who);
+    return VLLM_OK;
+}
+
+int ffn_block_run(hipStream_t st, const FfnBlock &k, const uint16_t *x, long R, int C, uint16_t *h, long slab_rows, uint16_t *t, uint16_t *out,
+                  const uint16_t *pos, uint16_t *y_pos)
+{
+    const int F = k.d_ffn;
+    for (long r0 = 0; r0 < R; r0 += slab_rows) {
+        const long m = R - r0 < slab_rows ? R - r0 : slab_rows;
+        TRY(gemm(st, k.act == 0 ? EPI_RELU : EPI_GELU, x + r0 * C, C, k.fc1_w, C, k.fc1_b, h, F, (int)m, F, C));
+        TRY(gemm(st, EPI_RESIDUAL, h, F, k.fc2_w, F, k.fc2_b, t + r0 * C, C, (int)m, C, F, nullptr, x + r0 * C, C));
+    }
+    return add_layernorm_launch(t, C, nullptr, 0, k.norm_w, k.norm_b, out, C, y_pos ? pos : nullptr, C, y_pos, C, R, C, k.eps, st);
+}
+
+namespace {
 
 // rows of the FFN intermediate per slab; 0 = the whole tensor at once, the default: measured at cfg 4, B = 8 the whole tensor is the
 // fastest of 0 / 65 536 / 16 384 rows (2191 / 2267 / 2360 us per layer, profiles/deform_encoder_layer.txt); a slab height is for
@@ -175,17 +188,21 @@ EncWs enc_ws(const VllmDeformEncLayerDesc *d, long B, long S)
     return w;
 }
 
+FfnBlock enc_ffn(const VllmDeformEncLayerDesc *d)
+{
+    return {d->fc1_w, d->fc1_b, d->fc2_w, d->fc2_b, d->norm2_w, d->norm2_b, d->act, d->d_ffn, d->norm2_eps};
+}
+
 int enc_check_desc(const VllmDeformEncLayerDesc *d)
 {
     VLLM_REQUIRE(d, "deform_enc_layer: null descriptor");
     TRY(msda_layer_check_desc(&d->attn));
     VLLM_REQUIRE(d->attn.ref_dim == 2, "deform_enc_layer: ref_dim=%d, the encoder layer takes 2-d reference points", d->attn.ref_dim);
     VLLM_REQUIRE(d->attn.d_model <= 512, "deform_enc_layer: d_model=%d above 512 (the LayerNorm kernel's rows)", d->attn.d_model);
-    VLLM_REQUIRE(d->d_ffn > 0 && d->d_ffn % 64 == 0, "deform_enc_layer: d_ffn=%d must be a positive multiple of 64", d->d_ffn);
-    VLLM_REQUIRE(d->act == 0 || d->act == VLLM_EPI_GELU, "deform_enc_layer: unknown act %d (0 = ReLU, VLLM_EPI_GELU = erf GELU)", d->act);
-    VLLM_REQUIRE(d->norm1_eps >= 0.f && d->norm2_eps >= 0.f, "deform_enc_layer: negative eps");
-    VLLM_REQUIRE(d->norm1_w && d->norm1_b && d->fc1_w && d->fc1_b && d->fc2_w && d->fc2_b && d->norm2_w && d->norm2_b && d->attn.value_proj_b &&
-                     d->attn.sampling_offsets_b && d->attn.attention_weights_b && d->attn.output_proj_b,
+    TRY(ffn_check("deform_enc_layer", enc_ffn(d)));
+    VLLM_REQUIRE(d->norm1_eps >= 0.f, "deform_enc_layer: negative eps");
+    VLLM_REQUIRE(d->norm1_w && d->norm1_b && d->attn.value_proj_b && d->attn.sampling_offsets_b && d->attn.attention_weights_b &&
+                     d->attn.output_proj_b,
                  "deform_enc_layer: missing weights");
     return VLLM_OK;
 }
@@ -254,10 +271,9 @@ extern "C" int vllm_deform_enc_layer_forward(const VllmDeformEncLayerDesc *d, co
     VLLM_REQUIRE(aligned16(src) && aligned16(pos) && aligned16(query_in) && aligned16(out) && aligned16(query_out) &&
                      (reinterpret_cast<uintptr_t>(reference_points) & 7u) == 0,
                  "deform_enc_layer: misaligned src / pos / query_in / out / query_out (16 bytes) or reference_points (8 bytes)");
-    for (const uint16_t *p : {d->norm1_w, d->norm1_b, d->fc1_w, d->fc1_b, d->fc2_w, d->fc2_b, d->norm2_w, d->norm2_b, at.value_proj_w, at.value_proj_b,
-                              at.sampling_offsets_w, at.sampling_offsets_b, at.attention_weights_w, at.attention_weights_b, at.output_proj_w,
-                              at.output_proj_b})
+    for (const uint16_t *p : {d->norm1_w, d->norm1_b, d->fc1_w, d->fc1_b, d->fc2_w, d->fc2_b, d->norm2_w, d->norm2_b})
         VLLM_REQUIRE(aligned16(p), "deform_enc_layer: misaligned weight or bias (16 bytes)");
+    for (const uint16_t *p : msda_weights(at)) VLLM_REQUIRE(aligned16(p), "deform_enc_layer: misaligned weight or bias (16 bytes)");
     const EncWs w = enc_ws(d, B, S);
     VLLM_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= w.total,
                  "deform_enc_layer: workspace too small (%ld < %ld bytes) or misaligned", workspace_bytes, w.total);
@@ -265,7 +281,7 @@ extern "C" int vllm_deform_enc_layer_forward(const VllmDeformEncLayerDesc *d, co
     hipStream_t st = (hipStream_t)stream;
     char *ws = (char *)workspace;
     const long R = (long)B * S;
-    const int C = at.d_model, F = d->d_ffn;
+    const int C = at.d_model;
     uint16_t *t0 = (uint16_t *)(ws + w.t0), *x1 = (uint16_t *)(ws + w.x1), *h = (uint16_t *)(ws + w.h);
     // 1. the query (modeling_unipose.py:3174 with_pos_embed; ...mask_dn.py:771-772)
     const uint16_t *query = query_in ? query_in : src;
@@ -275,12 +291,7 @@ extern "C" int vllm_deform_enc_layer_forward(const VllmDeformEncLayerDesc *d, co
                        msda_layer_bufs(&at, ws + w.attn, B, S, S), nullptr, st, src));
     // 3. norm1 (:3177; :1165), in place
     TRY(add_layernorm_launch(x1, C, nullptr, 0, d->norm1_w, d->norm1_b, x1, C, nullptr, 0, nullptr, 0, R, C, d->norm1_eps, st));
-    // 4. / 5. t0 = x1 + linear2(act(linear1(x1))) (:3167-3168; :1167-1174), a slab of rows at a time.  (t0 held the query: the attention has read it.)
-    for (long r0 = 0; r0 < R; r0 += w.slab) {
-        const long m = R - r0 < w.slab ? R - r0 : w.slab;
-        TRY(gemm(st, d->act == 0 ? EPI_RELU : EPI_GELU, x1 + r0 * C, C, d->fc1_w, C, d->fc1_b, h, F, (int)m, F, C));
-        TRY(gemm(st, EPI_RESIDUAL, h, F, d->fc2_w, F, d->fc2_b, t0 + r0 * C, C, (int)m, C, F, nullptr, x1 + r0 * C, C));
-    }
-    // 6. norm2 (:3169; :1175) -> out, and the next layer's query out + pos
-    return add_layernorm_launch(t0, C, nullptr, 0, d->norm2_w, d->norm2_b, out, C, query_out ? pos : nullptr, C, query_out, C, R, C, d->norm2_eps, st);
+    // 4. - 6. t0 = x1 + linear2(act(linear1(x1))) (:3167-3168; :1167-1174), a slab of rows at a time (t0 held the query: the attention has read
+    // it); norm2 (:3169; :1175) -> out, and the next layer's query out + pos
+    return ffn_block_run(st, enc_ffn(d), x1, R, C, h, w.slab, t0, out, pos, query_out);
 }

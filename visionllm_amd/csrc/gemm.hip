@@ -249,8 +249,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_bf16_kernel(const GemmAr
 
 int gemm256_bf16_launch(int epi, GemmArgs a, hipStream_t st);   // gemm256.hip
 
-static inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }   // (NULL passes: optional operands)
-
 int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st)
 {
     VLLM_REQUIRE(a.M >= 0 && a.N > 0 && a.K > 0, "gemm: bad dims M=%d N=%d K=%d", a.M, a.N, a.K);

@@ -189,13 +189,6 @@ int norm_bf16_launch(bool rms, const uint16_t *x, int ldx, const uint16_t *w, co
 constexpr int RB_THREADS = 256;
 constexpr int RB_MAX_C = 8192;   // 4 chunks of 8 columns per thread
 
-__device__ __forceinline__ void bf16x8_to_f32(const uint4_t &v, float (&f)[8])
-{
-    const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { f[2 * k] = bf16lo_to_f32(u[k]); f[2 * k + 1] = bf16hi_to_f32(u[k]); }
-}
-
 // sum over the TPR threads that share a row, the same value in each of them: DPP tree inside the wave, then the row's waves in a
 // fixed order.  `par` alternates between two LDS slots, so one barrier per sum is enough (a slot is rewritten two sums later, behind
 // the barrier in between).  Every thread of the block must call it (TPR > 64: a block-wide barrier).
@@ -230,7 +223,7 @@ __global__ __launch_bounds__(RB_THREADS) void rms_bwd_kernel(const uint16_t *__r
         const int c = i * TPR + tl;
         uint4_t wv = {0, 0, 0, 0};
         if (c < nchunk) wv = *reinterpret_cast<const uint4_t *>(w + c * 8);
-        bf16x8_to_f32(wv, wf[i]);
+        unpack8(wv, wf[i]);
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[i][k] = 0.f;
     }
@@ -258,8 +251,8 @@ __global__ __launch_bounds__(RB_THREADS) void rms_bwd_kernel(const uint16_t *__r
         float ss = 0.f;
 #pragma unroll
         for (int i = 0; i < MAXCH; ++i) {
-            bf16x8_to_f32(nx[i], xv[i]);
-            bf16x8_to_f32(ng[i], gv[i]);
+            unpack8(nx[i], xv[i]);
+            unpack8(ng[i], gv[i]);
             rv[i] = nr[i];
 #pragma unroll
             for (int k = 0; k < 8; ++k) ss = fmaf(xv[i][k], xv[i][k], ss);
@@ -286,7 +279,7 @@ __global__ __launch_bounds__(RB_THREADS) void rms_bwd_kernel(const uint16_t *__r
                 const int c = i * TPR + tl;
                 if (c < nchunk && r < r1) {
                     float rf[8], o[8];
-                    bf16x8_to_f32(rv[i], rf);
+                    unpack8(rv[i], rf);
 #pragma unroll
                     for (int k = 0; k < 8; ++k) o[k] = rstd * (gv[i][k] - xv[i][k] * mgx) + rf[k];
                     const uint4_t ov = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])};
@@ -328,7 +321,7 @@ __global__ __launch_bounds__(RB_THREADS) void ln_res_bwd_kernel(const uint16_t *
         const int c = i * TPR + tl;
         uint4_t wv = {0, 0, 0, 0};
         if (c < nchunk) wv = *reinterpret_cast<const uint4_t *>(w + c * 8);
-        bf16x8_to_f32(wv, wf[i]);
+        unpack8(wv, wf[i]);
 #pragma unroll
         for (int k = 0; k < 8; ++k) accw[i][k] = accb[i][k] = 0.f;
     }
@@ -356,8 +349,8 @@ __global__ __launch_bounds__(RB_THREADS) void ln_res_bwd_kernel(const uint16_t *
         float s = 0.f;
 #pragma unroll
         for (int i = 0; i < MAXCH; ++i) {
-            bf16x8_to_f32(nx[i], xv[i]);
-            bf16x8_to_f32(ng[i], gv[i]);
+            unpack8(nx[i], xv[i]);
+            unpack8(ng[i], gv[i]);
             rv[i] = nr[i];
 #pragma unroll
             for (int k = 0; k < 8; ++k) s += xv[i][k];
@@ -401,7 +394,7 @@ __global__ __launch_bounds__(RB_THREADS) void ln_res_bwd_kernel(const uint16_t *
                 const int c = i * TPR + tl;
                 if (c < nchunk && r < r1) {
                     float rf[8], o[8];
-                    bf16x8_to_f32(rv[i], rf);
+                    unpack8(rv[i], rf);
 #pragma unroll
                     for (int k = 0; k < 8; ++k) o[k] = rstd * (gv[i][k] - mg - xv[i][k] * mgx) + rf[k];
                     const uint4_t ov = {pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3]), pack_bf16x2(o[4], o[5]), pack_bf16x2(o[6], o[7])};
@@ -439,7 +432,7 @@ __global__ __launch_bounds__(RB_THREADS) void ls_bwd_kernel(const uint16_t *__re
         const int c = i * TPR + tl;
         uint4_t sv = {0, 0, 0, 0};
         if (c < nchunk) sv = *reinterpret_cast<const uint4_t *>(ls + c * 8);
-        bf16x8_to_f32(sv, sf[i]);
+        unpack8(sv, sf[i]);
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[i][k] = 0.f;
     }
@@ -470,8 +463,8 @@ __global__ __launch_bounds__(RB_THREADS) void ls_bwd_kernel(const uint16_t *__re
             for (int i = 0; i < MAXCH; ++i) {
                 const int c = i * TPR + tl;
                 float gf[8], yf[8];
-                bf16x8_to_f32(cg[i], gf);
-                bf16x8_to_f32(cy[i], yf);
+                unpack8(cg[i], gf);
+                unpack8(cy[i], yf);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) acc[i][k] = fmaf(gf[k], yf[k], acc[i][k]);   // (rows past the range were requested as zeros)
                 if (DY && c < nchunk && r < r1) {

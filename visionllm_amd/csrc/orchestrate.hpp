@@ -1,4 +1,5 @@
-// Host-side scaffolding shared by the orchestrators (vit.cpp, layer_train.cpp, bridge_train.cpp, embed_train.hip, msda_layer.hip, msda_layer_train.cpp): the
+// Host-side scaffolding shared by the orchestrators (vit.cpp, layer_train.cpp, bridge_train.cpp, region_train.cpp, embed_train.hip,
+// msda_layer.hip, msda_layer_train.cpp, dcnv3_layer.hip, deform_encoder_layer.hip, deform_decoder_layer.hip, deform_decoder.hip): the
 // pieces every entry point that strings kernels together on the caller's stream used to copy from the one before.  Host code only.
 #pragma once
 #include <initializer_list>
@@ -15,6 +16,16 @@ struct Carver {
     long off = 0;
     long take(long bytes) { const long o = off; off += align256(bytes); return o; }
 };
+
+// true where [a, a + abytes) and [b, b + bbytes) share a byte (either pointer null: false)
+inline bool ranges_overlap(const void *a, long abytes, const void *b, long bbytes)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + (uintptr_t)bbytes && b0 < a0 + (uintptr_t)abytes;
+}
+
+// what the row kernels ask of an operand of rows of C bf16: 16-byte aligned base, row stride a multiple of 8 and >= C
+inline bool row_operand_ok(const void *p, int ld, int C) { return aligned16(p) && ld >= C && ld % 8 == 0; }
 
 // The flags of the stream-K scratch are zeroed once per orchestrated call (kernels.hpp, SK_FLAG_BYTES); a call without scratch has none.
 inline int sk_scratch_reset(void *sk, hipStream_t st, const char *who)

@@ -57,15 +57,9 @@ __global__ __launch_bounds__(256) void region_im2col_kernel(const PIX *__restric
                 else v[e] = (float)s;
             }
         }
-        const uint4_t o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+        const uint4_t o = pack8(v);
         *reinterpret_cast<uint4_t *>(A + r * Kpad + ch * 8) = o;
     }
-}
-
-__device__ __forceinline__ void unpack8(const uint4_t &q, float *v)
-{
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[2 * e] = bf16lo_to_f32(q[e]); v[2 * e + 1] = bf16hi_to_f32(q[e]); }
 }
 
 // G lanes share a row (G a power of two, 8 .. 64), lane j of the group owns the 16-byte chunks j, j + G, ... (nch <= LG_NCH of them);
@@ -117,14 +111,14 @@ __global__ __launch_bounds__(256) void ln_gelu_kernel(const uint16_t *__restrict
             unpack8(*reinterpret_cast<const uint4_t *>(b + c0), gb);
 #pragma unroll
             for (int e = 0; e < 8; ++e) p[e] = v[q][e] * r * gw[e] + gb[e];
-            const uint4_t po = {pack_bf16x2(p[0], p[1]), pack_bf16x2(p[2], p[3]), pack_bf16x2(p[4], p[5]), pack_bf16x2(p[6], p[7])};
+            const uint4_t po = pack8(p);
             if (pre) *reinterpret_cast<uint4_t *>(pre + row * C + c0) = po;
             float pr[8];
             unpack8(po, pr);   // the GELU of the ROUNDED value: what the backward's gelu'(saved pre) differentiates
 #pragma unroll
             // 0.5 x erfc(-x / sqrt 2) = 0.5 x (1 + erf(x / sqrt 2)) without the cancellation of 1 + erf in the negative tail
             for (int e = 0; e < 8; ++e) a[e] = 0.5f * pr[e] * erfcf(pr[e] * -0.70710678118654752440f);
-            const uint4_t yo = {pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(a[4], a[5]), pack_bf16x2(a[6], a[7])};
+            const uint4_t yo = pack8(a);
             *reinterpret_cast<uint4_t *>(y + row * C + c0) = yo;
         }
     }
@@ -236,7 +230,7 @@ __global__ __launch_bounds__(256) void region_outer_kernel(const float *__restri
         unpack8(*reinterpret_cast<const uint4_t *>(g + in * C + ch * 8), v);
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = wv != 0.f ? wv * v[e] : 0.f;   // (a zero weight stays zero whatever g holds)
-        const uint4_t o = {pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
+        const uint4_t o = pack8(v);
         *reinterpret_cast<uint4_t *>(out + np * C + ch * 8) = o;
     }
 }

@@ -24,6 +24,7 @@ from torch.autograd.function import once_differentiable
 from torch.nn.init import constant_, xavier_uniform_
 
 from . import _lib
+from ._native_call import put
 
 
 def dcnv3_forward(input, offset, mask, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w,
@@ -295,12 +296,9 @@ class DCNv3(nn.Module):
         desc.dilation, desc.center_feature_scale, desc.n_proj = self.dilation, int(bool(self.center_feature_scale)), pw.shape[0]
         desc.offset_scale, desc.ln_eps = float(self.offset_scale), float(ln.eps)
         keep = []
-        for name, t in (("input_proj_w", self.input_proj.weight), ("input_proj_b", self.input_proj.bias), ("dw_w", conv.weight),
-                        ("dw_b", conv.bias), ("ln_w", ln.weight), ("ln_b", ln.bias), ("proj_w", pw), ("proj_b", pb),
-                        ("output_proj_w", self.output_proj.weight), ("output_proj_b", self.output_proj.bias)):
-            a = _lib.aligned(t.detach())
-            keep.append(a)
-            setattr(desc, name, a.data_ptr())
+        for name, w, b in (("input_proj", self.input_proj.weight, self.input_proj.bias), ("dw", conv.weight, conv.bias),
+                           ("ln", ln.weight, ln.bias), ("proj", pw, pb), ("output_proj", self.output_proj.weight, self.output_proj.bias)):
+            put(desc, keep, name, w, b)
         return desc, keep
 
     def _native_forward(self, input):

@@ -30,15 +30,9 @@ import torch
 from torch import nn
 
 from . import _lib
-from .deformable_encoder import _act2fn, _get_activation_fn, _native_act
-from .ms_deform_attn import (GroundingDinoMultiscaleDeformableAttention, MSDeformAttn, known_geometry, level_pixels,
-                             msda_layer_fused_ok)
-
-_ATTN_LINEARS = ("value_proj", "sampling_offsets", "attention_weights", "output_proj")
-
-
-def _is_gpu_bf16(t, dims=3):
-    return torch.is_tensor(t) and t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == dims
+from ._native_call import (MSDA_LINEARS, act2fn, fill_msda_desc, get_activation_fn, is_gpu_bf16, mask_u8, memory_operands, module_reasons,
+                           msda_params, native_act, opt_aligned, put)
+from .ms_deform_attn import GroundingDinoMultiscaleDeformableAttention, MSDeformAttn, known_geometry, level_pixels
 
 
 def _mha_reasons(name, mha, d_model):
@@ -60,37 +54,22 @@ def native_layer_reasons(layer, parts, tgt, pos, reference_points, memory_text, 
     """Every reason why ``vllm_deform_dec_layer_forward`` does not serve this call, as a list of strings (empty: it does).  ``parts`` is
     the layer's ``_parts()``; tensors as the layer's ``forward`` receives them (``batch_first`` tells the layout of tgt / pos / memory)."""
     why = []
-    if not (_is_gpu_bf16(tgt) and _is_gpu_bf16(memory)):
+    if not (is_gpu_bf16(tgt) and is_gpu_bf16(memory)):
         why.append("tgt / memory: bf16 CUDA tensors [., ., C]")
         if not (torch.is_tensor(tgt) and tgt.dim() == 3 and torch.is_tensor(memory) and memory.dim() == 3):
             return why
-    if pos is not None and not (_is_gpu_bf16(pos) and pos.shape == tgt.shape):
+    if pos is not None and not (is_gpu_bf16(pos) and pos.shape == tgt.shape):
         why.append("query_pos: a bf16 CUDA tensor of tgt's shape")
     bdim, qdim = (0, 1) if batch_first else (1, 0)
     B, Lq, C = tgt.shape[bdim], tgt.shape[qdim], tgt.shape[2]
     sa, ta = parts["self_attn"], parts["text_attn"]
-    mods = [parts["ca_norm"], parts["fc1"], parts["fc2"], parts["ffn_norm"]] + [getattr(parts["cross_attn"], n) for n in _ATTN_LINEARS]
+    mods = [parts["ca_norm"], parts["fc1"], parts["fc2"], parts["ffn_norm"]] + [getattr(parts["cross_attn"], n) for n in MSDA_LINEARS]
     if sa is not None:
         mods += [sa, parts["sa_norm"]]
     if ta is not None:
         mods += [ta, parts["text_norm"]]
-    params = [p for m in mods for p in m.parameters()]
-    if any(p.dtype != torch.bfloat16 or not p.is_cuda for p in params):
-        why.append("parameters: bf16 on the GPU")
-    if any(getattr(m, "bias", 0) is None for m in mods if not isinstance(m, nn.MultiheadAttention)):
-        why.append("parameters: a Linear / LayerNorm without bias")
-    if torch.is_grad_enabled() and (any(p.requires_grad for p in params) or
-                                    any(torch.is_tensor(t) and t.requires_grad for t in (tgt, pos, memory, memory_text, reference_points))):
-        why.append("requires_grad under grad mode: there is no native backward")
-    if layer.training and any(p > 0 for p in parts["dropouts"]):
-        why.append("active dropout")
-    if parts["act"] is None:
-        why.append("activation: relu or gelu")
-    if reference_points is None or not torch.is_tensor(reference_points) or reference_points.shape[-1] not in (2, 4):
-        why.append("reference_points: last dim 2 or 4")
-    elif not (_is_gpu_bf16(tgt) and _is_gpu_bf16(memory)) or not msda_layer_fused_ok(
-            tgt, memory, *(getattr(parts["cross_attn"], n) for n in _ATTN_LINEARS), reference_points=reference_points):
-        why.append("cross-attention: msda_layer_fused_ok")
+    why += module_reasons(layer.training, mods, parts["dropouts"], parts["act"], parts["cross_attn"], "cross-attention", tgt, memory,
+                          reference_points, (2, 4), (tgt, pos, memory, memory_text, reference_points), parts["fc1"].out_features)
     if sa is not None:
         why += _mha_reasons("self_attn", sa, C)
         if self_attn_mask is not None and not (torch.is_tensor(self_attn_mask) and self_attn_mask.dtype == torch.bool and
@@ -104,9 +83,6 @@ def native_layer_reasons(layer, parts, tgt, pos, reference_points, memory_text, 
         if text_mask is not None and not (torch.is_tensor(text_mask) and text_mask.dtype == torch.bool and torch.is_tensor(memory_text) and
                                           memory_text.dim() == 3 and tuple(text_mask.shape) == (B, memory_text.shape[1])):
             why.append("text mask: None or bool [B, Lt]")
-    d_ffn = parts["fc1"].out_features
-    if not (C % 64 == 0 and C <= 512 and d_ffn % 64 == 0 and getattr(parts["cross_attn"], "d_model", C) == C):
-        why.append("d_model a multiple of 64 up to 512, d_ffn a multiple of 64")
     return why
 
 
@@ -114,29 +90,20 @@ def _fill_layer_desc(desc, parts, C, ref_dim, keep):
     """``desc`` (a VllmDeformDecLayerDesc) from a layer's ``_parts()``, everything but ``cross_attn.geometry``; the tensors whose
     pointers it holds are appended to ``keep``"""
     attn = parts["cross_attn"]
-    a = desc.cross_attn
-    a.d_model, a.n_heads, a.n_levels, a.n_points, a.ref_dim = C, attn.n_heads, attn.n_levels, attn.n_points, ref_dim
-    a.use_4d_normalizer = int(bool(getattr(attn, "use_4D_normalizer", False)))
+    fill_msda_desc(desc.cross_attn, keep, C, attn.n_heads, attn.n_levels, attn.n_points, ref_dim, getattr(attn, "use_4D_normalizer", False),
+                   msda_params(attn))
     sa, ta = parts["self_attn"], parts["text_attn"]
     desc.d_ffn, desc.act = parts["fc1"].out_features, parts["act"]
     desc.has_self_attn, desc.has_text_attn = int(sa is not None), int(ta is not None)
     desc.n_heads_sa = sa.num_heads if sa is not None else ta.num_heads if ta is not None else 0
     desc.ca_norm_eps, desc.ffn_norm_eps = parts["ca_norm"].eps, parts["ffn_norm"].eps
-
-    def put(struct, name, weight, bias):
-        w, b = _lib.aligned(weight.detach()), _lib.aligned(bias.detach())
-        keep.extend((w, b))
-        setattr(struct, name + "_w", w.data_ptr())
-        setattr(struct, name + "_b", b.data_ptr())
-    for name in _ATTN_LINEARS:
-        put(a, name, getattr(attn, name).weight, getattr(attn, name).bias)
-    for name, mod in (("ca_norm", parts["ca_norm"]), ("fc1", parts["fc1"]), ("fc2", parts["fc2"]), ("ffn_norm", parts["ffn_norm"])):
-        put(desc, name, mod.weight, mod.bias)
+    for name in ("ca_norm", "fc1", "fc2", "ffn_norm"):
+        put(desc, keep, name, parts[name].weight, parts[name].bias)
     for pre, mha, norm in (("sa", sa, parts["sa_norm"]), ("text", ta, parts["text_norm"])):
         if mha is not None:
-            put(desc, pre + "_in_proj", mha.in_proj_weight, mha.in_proj_bias)
-            put(desc, pre + "_out_proj", mha.out_proj.weight, mha.out_proj.bias)
-            put(desc, pre + "_norm", norm.weight, norm.bias)
+            put(desc, keep, pre + "_in_proj", mha.in_proj_weight, mha.in_proj_bias)
+            put(desc, keep, pre + "_out_proj", mha.out_proj.weight, mha.out_proj.bias)
+            put(desc, keep, pre + "_norm", norm.weight, norm.bias)
             setattr(desc, pre + "_norm_eps", norm.eps)
 
 
@@ -146,39 +113,20 @@ def deform_dec_layer_forward(parts, tgt, pos, reference_points, self_attn_mask, 
     None, ``reference_points`` [B, Lq, L, 2 | 4], ``self_attn_mask`` bool [Lq, Lq] (True = may not attend) or None, ``memory_text``
     [B, Lt, C], ``text_mask`` bool [B, Lt] (True = ignore) or None, ``memory`` [B, S, C], ``memory_padding_mask`` bool [B, S] (True =
     padded) or None."""
-    attn = parts["cross_attn"]
     B, Lq, C = tgt.shape
     S = memory.shape[1]
-    n_levels, ref_dim = attn.n_levels, reference_points.shape[-1]
-    if reference_points.dim() != 4 or reference_points.shape[0] not in (1, B) or reference_points.shape[1] not in (1, Lq) or \
-            reference_points.shape[2] not in (1, n_levels):
-        raise RuntimeError(f"deform_dec_layer_forward: reference_points {tuple(reference_points.shape)} does not broadcast to "
-                           f"({B}, {Lq}, {n_levels}, 2|4)")
-    if tuple(memory.shape) != (B, S, C):
-        raise RuntimeError(f"deform_dec_layer_forward: memory {tuple(memory.shape)} vs tgt {tuple(tgt.shape)}")
-    if tuple(spatial_shapes.shape) != (n_levels, 2) or level_start_index.numel() != n_levels:
-        raise RuntimeError(f"deform_dec_layer_forward: spatial_shapes {tuple(spatial_shapes.shape)} / level_start_index "
-                           f"({level_start_index.numel()}) do not describe {n_levels} levels")
-    if memory_padding_mask is not None and tuple(memory_padding_mask.shape) != (B, S):
-        raise RuntimeError(f"deform_dec_layer_forward: padding mask {tuple(memory_padding_mask.shape)} must be ({B}, {S})")
+    x, ref, mem, shapes, lsi, pmask = memory_operands("deform_dec_layer_forward", tgt, reference_points, memory, spatial_shapes,
+                                                      level_start_index, memory_padding_mask, parts["cross_attn"].n_levels)
+    p = opt_aligned(pos)
     L = _lib.lib()
     desc = _lib.VllmDeformDecLayerDesc()
     keep = []
-    _fill_layer_desc(desc, parts, C, ref_dim, keep)
-    a, sa, ta = desc.cross_attn, parts["self_attn"], parts["text_attn"]
-    x = _lib.aligned(tgt)
-    p = None if pos is None else _lib.aligned(pos)
-    mem = _lib.aligned(memory)
-    ref = _lib.aligned(reference_points.to(torch.float32).expand(B, Lq, n_levels, ref_dim), 16 if ref_dim == 4 else 8)
-    shapes = spatial_shapes.to(device=x.device, dtype=torch.int64).contiguous()
-    lsi = level_start_index.to(device=x.device, dtype=torch.int64).contiguous()
-    u8 = lambda m: None if m is None else m.to(device=x.device).to(torch.uint8).contiguous()
-    sam = u8(self_attn_mask) if sa is not None else None
+    _fill_layer_desc(desc, parts, C, ref.shape[-1], keep)
+    sam = mask_u8(self_attn_mask, x.device) if parts["self_attn"] is not None else None
     text, tmask, Lt = None, None, 0
-    if ta is not None:
-        text, tmask, Lt = _lib.aligned(memory_text), u8(text_mask), memory_text.shape[1]
-    pmask = u8(memory_padding_mask)
-    a.geometry = known_geometry(spatial_shapes, Lq)
+    if parts["text_attn"] is not None:
+        text, tmask, Lt = _lib.aligned(memory_text), mask_u8(text_mask, x.device), memory_text.shape[1]
+    desc.cross_attn.geometry = known_geometry(spatial_shapes, Lq)
     ws, wsb = _lib.sized_workspace(x.device, L.vllm_deform_dec_layer_workspace_bytes(ctypes.byref(desc), B, Lq, Lt, S),
                                    "vllm_deform_dec_layer_workspace_bytes")
     out = torch.empty_like(x)
@@ -223,7 +171,7 @@ class DeformableTransformerDecoderLayer(nn.Module):
 
         # ffn
         self.linear1 = nn.Linear(d_model, d_ffn)
-        self.activation = _get_activation_fn(activation, d_model=d_ffn, batch_dim=1)
+        self.activation = get_activation_fn(activation, d_model=d_ffn, batch_dim=1)
         self.dropout3 = nn.Dropout(dropout) if dropout > 0 else nn.Identity()
         self.linear2 = nn.Linear(d_ffn, d_model)
         self.dropout4 = nn.Dropout(dropout) if dropout > 0 else nn.Identity()
@@ -265,7 +213,7 @@ class DeformableTransformerDecoderLayer(nn.Module):
             drops += [getattr(self.catext_dropout, "p", 0.0), text.dropout]
         return dict(cross_attn=self.cross_attn, self_attn=self.self_attn, sa_norm=self.norm2, text_attn=text,
                     text_norm=self.catext_norm if text is not None else None, ca_norm=self.norm1, fc1=self.linear1, fc2=self.linear2,
-                    ffn_norm=self.norm3, act=_native_act(self.activation), dropouts=drops)
+                    ffn_norm=self.norm3, act=native_act(self.activation), dropouts=drops)
 
     def native_layer_reasons(self, tgt, tgt_query_pos=None, tgt_reference_points=None, memory_text=None, text_attention_mask=None,
                              memory=None, self_attn_mask=None, cross_attn_mask=None):
@@ -371,7 +319,7 @@ class GroundingDinoDecoderLayer(nn.Module):
             batch_first=True,
         )
         self.dropout = config.dropout
-        self.activation_fn = _act2fn(config.activation_function)
+        self.activation_fn = act2fn(config.activation_function)
         self.activation_dropout = config.activation_dropout
 
         self.self_attn_layer_norm = nn.LayerNorm(self.embed_dim)
@@ -401,7 +349,7 @@ class GroundingDinoDecoderLayer(nn.Module):
     def _parts(self):
         return dict(cross_attn=self.encoder_attn, self_attn=self.self_attn, sa_norm=self.self_attn_layer_norm,
                     text_attn=self.encoder_attn_text, text_norm=self.encoder_attn_text_layer_norm, ca_norm=self.encoder_attn_layer_norm,
-                    fc1=self.fc1, fc2=self.fc2, ffn_norm=self.final_layer_norm, act=_native_act(self.activation_fn),
+                    fc1=self.fc1, fc2=self.fc2, ffn_norm=self.final_layer_norm, act=native_act(self.activation_fn),
                     dropouts=[self.dropout, self.activation_dropout, self.self_attn.dropout, self.encoder_attn_text.dropout])
 
     def native_layer_reasons(self, hidden_states, position_embeddings=None, reference_points=None, vision_encoder_hidden_states=None,
@@ -673,7 +621,7 @@ class GroundingDinoDecoder(nn.Module):
             why.append("parameters: 16-byte aligned storage")
         if any(m.bias is None for m in self.reference_points_head.layers):
             why.append("parameters: a Linear without bias")
-        if not (_is_gpu_bf16(x) and _is_gpu_bf16(mem)):
+        if not (is_gpu_bf16(x) and is_gpu_bf16(mem)):
             why.append("inputs_embeds / vision_encoder_hidden_states: bf16 CUDA tensors [B, ., C]")
         if not (torch.is_tensor(ref) and ref.dim() == 3 and ref.shape[-1] == 4):
             why.append("reference_points: [B, Lq, 4] (2-d reference points keep the composed path)")
@@ -733,25 +681,19 @@ class GroundingDinoDecoder(nn.Module):
             raise ValueError("Make sure to align the spatial shapes with the sequence length of the encoder hidden states")
         B, Lq, C = x.shape
         S, Lt, n = mem.shape[1], text.shape[1], len(self.layers)
-        if tuple(mem.shape) != (B, S, C) or tuple(spatial_shapes.shape) != (valid_ratios.shape[1], 2) or \
-                level_start_index.numel() != valid_ratios.shape[1]:
-            raise RuntimeError(f"GroundingDinoDecoder: memory {tuple(mem.shape)} / spatial_shapes {tuple(spatial_shapes.shape)} / "
-                               f"level_start_index ({level_start_index.numel()}) vs inputs_embeds {tuple(x.shape)}")
-        if attention_mask is not None and tuple(attention_mask.shape) != (B, S):
-            raise RuntimeError(f"GroundingDinoDecoder: vision_encoder_attention_mask {tuple(attention_mask.shape)} must be ({B}, {S})")
+        # (the decoder's reference points are [B, Lq, 4], one per query: the call multiplies them by valid_ratios itself)
+        xa, _, mema, shapes, lsi, pmask = memory_operands("GroundingDinoDecoder", x, None, mem, spatial_shapes, level_start_index,
+                                                          None if attention_mask is None else ~attention_mask, valid_ratios.shape[1])
         L = _lib.lib()
         heads, params = self._own_params()
         st = self._native_state(x.device, heads, params)
         geo = known_geometry(spatial_shapes, Lq)
         for ld in st["layers"]:
             ld.cross_attn.geometry = geo
-        xa, mema, texta = _lib.aligned(x), _lib.aligned(mem), _lib.aligned(text)
+        texta = _lib.aligned(text)
         ref = _lib.aligned(reference_points.to(torch.float32))
         vr = _lib.aligned(valid_ratios.to(torch.float32))
-        shapes = spatial_shapes.to(device=x.device, dtype=torch.int64).contiguous()
-        lsi = level_start_index.to(device=x.device, dtype=torch.int64).contiguous()
-        u8 = lambda m: None if m is None else m.to(device=x.device).to(torch.uint8).contiguous()
-        sam, tmask, pmask = u8(self_attn_mask), u8(text_mask), u8(None if attention_mask is None else ~attention_mask)
+        sam, tmask = mask_u8(self_attn_mask, x.device), mask_u8(text_mask, x.device)
         ws, wsb = _lib.sized_workspace(x.device, L.vllm_deform_decoder_workspace_bytes(ctypes.byref(st["desc"]), B, Lq, Lt, S),
                                        "vllm_deform_decoder_workspace_bytes")
         inter = torch.empty((n, B, Lq, C), dtype=torch.bfloat16, device=x.device)

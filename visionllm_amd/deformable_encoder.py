@@ -17,67 +17,27 @@ not mirrored: the constructor raises ``NotImplementedError`` for them.
 import ctypes
 
 import torch
-import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from .ms_deform_attn import (GroundingDinoMultiscaleDeformableAttention, MSDeformAttn, known_geometry, level_pixels,
-                             msda_layer_fused_ok)
-
-_ATTN_LINEARS = ("value_proj", "sampling_offsets", "attention_weights", "output_proj")
-ACT_RELU, ACT_GELU = 0, _lib.EPI_GELU   # VllmDeformEncLayerDesc.act
+from ._native_call import (act2fn, fill_msda_desc, get_activation_fn, is_gpu_bf16, memory_operands, module_reasons, msda_params,
+                           native_act, opt_aligned, put)
+from .ms_deform_attn import GroundingDinoMultiscaleDeformableAttention, MSDeformAttn, known_geometry, level_pixels
 
 
-def _get_activation_fn(activation, d_model=256, batch_dim=0):
-    """Return an activation function given a string (unipose/utils/model_utils.py:162-175)"""
-    if activation == "relu":
-        return F.relu
-    if activation == "gelu":
-        return F.gelu
-    if activation == "glu":
-        return F.glu
-    if activation == "prelu":
-        return nn.PReLU()
-    if activation == "selu":
-        return F.selu
-    raise RuntimeError(F"activation should be relu/gelu, not {activation}.")
-
-
-def _act2fn(name):
-    """transformers' ACT2FN for the names a Grounding-DINO config uses (the package itself is not required)"""
-    table = {"relu": F.relu, "gelu": F.gelu, "silu": F.silu, "swish": F.silu, "tanh": torch.tanh, "sigmoid": torch.sigmoid,
-             "selu": F.selu}
-    if name in table:
-        return table[name]
-    from transformers.activations import ACT2FN
-    return ACT2FN[name]
-
-
-def _native_act(fn):
-    return ACT_RELU if fn is F.relu else ACT_GELU if fn is F.gelu else None
-
-
-def _applies(layer, attn, norms, linears, act, dropouts, src, pos, reference_points, query_in=None):
-    """The conditions of the native call that both flavours share (see the classes' ``native_layer_applies``)."""
-    if not (torch.is_tensor(src) and src.is_cuda and src.dtype == torch.bfloat16 and src.dim() == 3):
-        return False
-    if layer.training and any(p > 0 for p in dropouts):
-        return False
-    if act is None or reference_points is None or reference_points.shape[-1] != 2:
-        return False
-    for t in (pos, query_in):
-        if t is not None and not (t.is_cuda and t.dtype == torch.bfloat16 and t.shape == src.shape):
-            return False
-    mods = tuple(norms) + tuple(linears)
-    if any(p.dtype != torch.bfloat16 or not p.is_cuda for m in mods for p in m.parameters()) or any(m.bias is None for m in mods):
-        return False
-    if torch.is_grad_enabled() and (any(p.requires_grad for m in mods for p in m.parameters()) or src.requires_grad or
-                                    (pos is not None and pos.requires_grad) or (query_in is not None and query_in.requires_grad)):
-        return False
-    if not msda_layer_fused_ok(src, src, *(getattr(attn, n) for n in _ATTN_LINEARS), reference_points=reference_points):
-        return False
-    d_model, d_ffn = src.shape[-1], linears[0].out_features
-    return d_model % 64 == 0 and d_model <= 512 and d_ffn % 64 == 0 and getattr(attn, "d_model", d_model) == d_model
+def _reasons(layer, attn, norms, linears, act, dropouts, src, pos, reference_points, query_in=None):
+    """Every reason why ``vllm_deform_enc_layer_forward`` does not serve this call, as a list of strings (empty: it does): the inputs'
+    own, then the module's (module_reasons, the decoder layers' words).  Only the layer's norms and FFN linears are asked for bf16 GPU
+    parameters here; the attention linears answer through msda_layer_fused_ok."""
+    why = []
+    if not is_gpu_bf16(src):
+        why.append("src: a bf16 CUDA tensor [B, S, C]")
+        if not (torch.is_tensor(src) and src.dim() == 3):
+            return why
+    if any(t is not None and not (is_gpu_bf16(t) and t.shape == src.shape) for t in (pos, query_in)):
+        why.append("pos / query_in: bf16 CUDA tensors of src's shape")
+    return why + module_reasons(layer.training, tuple(norms) + tuple(linears), dropouts, act, attn, "self-attention", src, src,
+                                reference_points, (2,), (src, pos, query_in), linears[0].out_features)
 
 
 def deform_enc_layer_forward(attn, norm1, linear1, act, linear2, norm2, src, pos, reference_points, spatial_shapes, level_start_index,
@@ -86,41 +46,17 @@ def deform_enc_layer_forward(attn, norm1, linear1, act, linear2, norm2, src, pos
     None, ``reference_points`` [B, S, L, 2], ``padding_mask`` [B, S] bool (True = padded) or None, ``act`` ACT_RELU / ACT_GELU;
     ``query_in`` is the ``query_out`` of the layer in front (``src + pos`` already formed)."""
     B, S, C = src.shape
-    n_levels = attn.n_levels
-    if reference_points.dim() != 4 or reference_points.shape[0] not in (1, B) or reference_points.shape[1] not in (1, S) or \
-            reference_points.shape[2] not in (1, n_levels) or reference_points.shape[3] != 2:
-        raise RuntimeError(f"deform_enc_layer_forward: reference_points {tuple(reference_points.shape)} does not broadcast to "
-                           f"({B}, {S}, {n_levels}, 2)")
-    if tuple(spatial_shapes.shape) != (n_levels, 2) or level_start_index.numel() != n_levels:
-        raise RuntimeError(f"deform_enc_layer_forward: spatial_shapes {tuple(spatial_shapes.shape)} / level_start_index "
-                           f"({level_start_index.numel()}) do not describe {n_levels} levels")
-    if padding_mask is not None and tuple(padding_mask.shape) != (B, S):
-        raise RuntimeError(f"deform_enc_layer_forward: padding mask {tuple(padding_mask.shape)} must be ({B}, {S})")
+    x, ref, _, shapes, lsi, mask = memory_operands("deform_enc_layer_forward", src, reference_points, src, spatial_shapes, level_start_index,
+                                                   padding_mask, attn.n_levels, ref_dim=2)
+    p, q = opt_aligned(pos), opt_aligned(query_in)
     L = _lib.lib()
     desc = _lib.VllmDeformEncLayerDesc()
-    a = desc.attn
-    a.d_model, a.n_heads, a.n_levels, a.n_points, a.ref_dim = C, attn.n_heads, n_levels, attn.n_points, 2
-    a.use_4d_normalizer = 0
     desc.d_ffn, desc.act, desc.norm1_eps, desc.norm2_eps = linear1.out_features, act, norm1.eps, norm2.eps
     keep = []
-
-    def put(struct, name, mod):
-        w, b = _lib.aligned(mod.weight.detach()), _lib.aligned(mod.bias.detach())
-        keep.extend((w, b))
-        setattr(struct, name + "_w", w.data_ptr())
-        setattr(struct, name + "_b", b.data_ptr())
-    for name in _ATTN_LINEARS:
-        put(a, name, getattr(attn, name))
+    fill_msda_desc(desc.attn, keep, C, attn.n_heads, attn.n_levels, attn.n_points, 2, False, msda_params(attn))
     for name, mod in (("norm1", norm1), ("fc1", linear1), ("fc2", linear2), ("norm2", norm2)):
-        put(desc, name, mod)
-    x = _lib.aligned(src)
-    p = None if pos is None else _lib.aligned(pos)
-    q = None if query_in is None else _lib.aligned(query_in)
-    ref = _lib.aligned(reference_points.to(torch.float32).expand(B, S, n_levels, 2), 8)
-    shapes = spatial_shapes.to(device=x.device, dtype=torch.int64).contiguous()
-    lsi = level_start_index.to(device=x.device, dtype=torch.int64).contiguous()
-    mask = None if padding_mask is None else padding_mask.to(torch.uint8).contiguous()
-    a.geometry = known_geometry(spatial_shapes, S)
+        put(desc, keep, name, mod.weight, mod.bias)
+    desc.attn.geometry = known_geometry(spatial_shapes, S)
     ws, wsb = _lib.sized_workspace(x.device, L.vllm_deform_enc_layer_workspace_bytes(ctypes.byref(desc), B, S),
                                    "vllm_deform_enc_layer_workspace_bytes")
     out = torch.empty_like(x)
@@ -159,7 +95,7 @@ class DeformableTransformerEncoderLayer(nn.Module):
 
         # ffn
         self.linear1 = nn.Linear(d_model, d_ffn)
-        self.activation = _get_activation_fn(activation, d_model=d_ffn)
+        self.activation = get_activation_fn(activation, d_model=d_ffn)
         self.dropout2 = nn.Dropout(dropout)
         self.linear2 = nn.Linear(d_ffn, d_model)
         self.dropout3 = nn.Dropout(dropout)
@@ -178,17 +114,21 @@ class DeformableTransformerEncoderLayer(nn.Module):
         src = self.norm2(src)
         return src
 
+    def native_layer_reasons(self, src, pos, reference_points, query_in=None):
+        """why this call keeps the composed path, as a list of strings (empty: the native call serves it)"""
+        return _reasons(self, self.self_attn, (self.norm1, self.norm2), (self.linear1, self.linear2), native_act(self.activation),
+                        (self.dropout1.p, self.dropout2.p, self.dropout3.p), src, pos, reference_points, query_in)
+
     def native_layer_applies(self, src, pos, reference_points, query_in=None):
         """What vllm_deform_enc_layer_forward serves: a bf16 module and bf16 inputs on the GPU, nothing that needs a gradient, no active
         dropout, a relu / gelu activation, 2-d reference points, the fused attention's own conditions (msda_layer_fused_ok) and d_model
         (at most 512) and d_ffn multiples of 64."""
-        return _applies(self, self.self_attn, (self.norm1, self.norm2), (self.linear1, self.linear2), _native_act(self.activation),
-                        (self.dropout1.p, self.dropout2.p, self.dropout3.p), src, pos, reference_points, query_in)
+        return not self.native_layer_reasons(src, pos, reference_points, query_in)
 
     def _native_forward(self, src, pos, reference_points, spatial_shapes, level_start_index, key_padding_mask, query_in=None,
                         want_query_out=False):
         assert level_pixels(spatial_shapes) == src.shape[1]   # MSDeformAttn.forward's own check (ms_deform_attn.py:100)
-        return deform_enc_layer_forward(self.self_attn, self.norm1, self.linear1, _native_act(self.activation), self.linear2, self.norm2,
+        return deform_enc_layer_forward(self.self_attn, self.norm1, self.linear1, native_act(self.activation), self.linear2, self.norm2,
                                         src, pos, reference_points, spatial_shapes, level_start_index, key_padding_mask, query_in,
                                         want_query_out)
 
@@ -222,26 +162,30 @@ class GroundingDinoDeformableLayer(nn.Module):
         )
         self.self_attn_layer_norm = nn.LayerNorm(self.embed_dim)
         self.dropout = config.dropout
-        self.activation_fn = _act2fn(config.activation_function)
+        self.activation_fn = act2fn(config.activation_function)
         self.activation_dropout = config.activation_dropout
         self.fc1 = nn.Linear(self.embed_dim, config.encoder_ffn_dim)
         self.fc2 = nn.Linear(config.encoder_ffn_dim, self.embed_dim)
         self.final_layer_norm = nn.LayerNorm(self.embed_dim)
 
-    def native_layer_applies(self, hidden_states, position_embeddings, reference_points, output_attentions=False, query_in=None):
-        """As DeformableTransformerEncoderLayer.native_layer_applies; a call with ``output_attentions`` keeps the composed path (the
-        attention weights stay inside the native call)."""
+    def native_layer_reasons(self, hidden_states, position_embeddings, reference_points, output_attentions=False, query_in=None):
+        """why this call keeps the composed path, as a list of strings (empty: the native call serves it)"""
+        why = _reasons(self, self.self_attn, (self.self_attn_layer_norm, self.final_layer_norm), (self.fc1, self.fc2),
+                       native_act(self.activation_fn), (self.dropout, self.activation_dropout), hidden_states, position_embeddings,
+                       reference_points, query_in)
         if output_attentions:
-            return False
-        return _applies(self, self.self_attn, (self.self_attn_layer_norm, self.final_layer_norm), (self.fc1, self.fc2),
-                        _native_act(self.activation_fn), (self.dropout, self.activation_dropout), hidden_states, position_embeddings,
-                        reference_points, query_in)
+            why.append("output_attentions: the attention weights stay inside the native call")
+        return why
+
+    def native_layer_applies(self, hidden_states, position_embeddings, reference_points, output_attentions=False, query_in=None):
+        """As DeformableTransformerEncoderLayer.native_layer_applies; a call with ``output_attentions`` keeps the composed path."""
+        return not self.native_layer_reasons(hidden_states, position_embeddings, reference_points, output_attentions, query_in)
 
     def _native_forward(self, hidden_states, attention_mask, position_embeddings, reference_points, spatial_shapes, level_start_index,
                         query_in=None, want_query_out=False):
         if level_pixels(spatial_shapes) != hidden_states.shape[1]:   # the attention module's own check (...mask_dn.py:741)
             raise ValueError("Make sure to align the spatial shapes with the sequence length of the encoder hidden states")
-        return deform_enc_layer_forward(self.self_attn, self.self_attn_layer_norm, self.fc1, _native_act(self.activation_fn), self.fc2,
+        return deform_enc_layer_forward(self.self_attn, self.self_attn_layer_norm, self.fc1, native_act(self.activation_fn), self.fc2,
                                         self.final_layer_norm, hidden_states, position_embeddings, reference_points, spatial_shapes,
                                         level_start_index, None if attention_mask is None else ~attention_mask, query_in, want_query_out)
 

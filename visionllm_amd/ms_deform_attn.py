@@ -29,6 +29,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._native_call import MSDA_LINEARS, fill_msda_desc, memory_operands, msda_layer_fused_ok   # noqa: F401 (re-exported)
 
 
 def _check_inputs(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step):
@@ -239,21 +240,6 @@ def _sampling_locations(reference_points, sampling_offsets, spatial_shapes, n_po
         "Last dim of reference_points must be 2 or 4, but get {} instead.".format(reference_points.shape[-1]))
 
 
-def msda_layer_fused_ok(query, input_flatten, *linears, reference_points=None):
-    """The fused HIP layer serves inference-dtype (bf16) modules on the GPU; anything else keeps the composed path."""
-    if not (query.is_cuda and query.dtype == torch.bfloat16 and input_flatten.dtype == torch.bfloat16):
-        return False
-    if torch.is_grad_enabled():
-        # training differentiates through the composed path (autograd Function around the operator): trainable
-        # parameters, or a frozen module whose INPUTS carry gradients to upstream layers (the fused call has no grad_fn)
-        if any(p.requires_grad for lin in linears for p in lin.parameters()):
-            return False
-        if query.requires_grad or input_flatten.requires_grad or (reference_points is not None and reference_points.requires_grad):
-            return False
-    d_model = query.shape[-1]
-    return d_model % 64 == 0 and all(lin.weight.dtype == torch.bfloat16 and lin.bias is not None for lin in linears)
-
-
 GEO_UNKNOWN, GEO_PYRAMID, GEO_GENERAL, GEO_NESTED = 0, 1, 2, 3   # VLLM_GEO_* of include/vllm_hip.h
 _SHAPE_FACTS = {}   # id(spatial_shapes) -> (weakref, tensor version, sum of H * W, geometry)
 
@@ -355,37 +341,14 @@ def msda_layer_prepare(query, reference_points, input_flatten, spatial_shapes, l
     if reference_points.shape[-1] not in (2, 4):
         raise ValueError("Last dim of reference_points must be 2 or 4, but get {} instead.".format(
             reference_points.shape[-1]))
-    # the native kernels index these tensors by (B, Lq, n_levels): a broadcastable view must be materialised here
-    if reference_points.dim() != 4 or reference_points.shape[0] not in (1, B) or reference_points.shape[1] not in (1, Lq) or \
-            reference_points.shape[2] not in (1, n_levels):
-        raise RuntimeError(f"msda_layer_forward: reference_points {tuple(reference_points.shape)} does not broadcast to "
-                           f"({B}, {Lq}, {n_levels}, 2|4)")
-    reference_points = reference_points.expand(B, Lq, n_levels, reference_points.shape[-1])
-    if tuple(input_flatten.shape) != (B, S, C):
-        raise RuntimeError(f"msda_layer_forward: input_flatten {tuple(input_flatten.shape)} vs query {tuple(query.shape)}")
-    if tuple(spatial_shapes.shape) != (n_levels, 2) or level_start_index.numel() != n_levels:
-        raise RuntimeError(f"msda_layer_forward: spatial_shapes {tuple(spatial_shapes.shape)} / level_start_index "
-                           f"({level_start_index.numel()}) do not describe {n_levels} levels")
-    if padding_mask is not None and tuple(padding_mask.shape) != (B, S):
-        raise RuntimeError(f"msda_layer_forward: padding mask {tuple(padding_mask.shape)} must be ({B}, {S})")
+    q, ref, x, shapes, lsi, mask = memory_operands("msda_layer_forward", query, reference_points, input_flatten, spatial_shapes,
+                                                   level_start_index, padding_mask, n_levels)
     L = _lib.lib()
     desc = _lib.VllmMsdaLayerDesc()
-    desc.d_model, desc.n_heads, desc.n_levels, desc.n_points = C, n_heads, n_levels, n_points
-    desc.ref_dim, desc.use_4d_normalizer = reference_points.shape[-1], int(bool(use_4d_normalizer))
     keep = []
-    for name, lin in (("value_proj", value_proj), ("sampling_offsets", sampling_offsets),
-                      ("attention_weights", attention_weights), ("output_proj", output_proj)):
-        w, b = _lib.aligned(lin.weight.detach()), _lib.aligned(lin.bias.detach().to(torch.bfloat16))
-        keep += [w, b]
-        setattr(desc, name + "_w", w.data_ptr())
-        setattr(desc, name + "_b", b.data_ptr())
-    q = _lib.aligned(query)           # (the GEMMs need 16-byte aligned rows: views at another storage offset are copied)
-    x = _lib.aligned(input_flatten)
-    # (the sampling epilogue reads a query's reference point as one 8-byte / 16-byte vector: a view that is not aligned so is copied)
-    ref = _lib.aligned(reference_points.to(torch.float32), 16 if reference_points.shape[-1] == 4 else 8)
-    shapes = spatial_shapes.to(device=q.device, dtype=torch.int64).contiguous()
-    lsi = level_start_index.to(device=q.device, dtype=torch.int64).contiguous()
-    mask = None if padding_mask is None else padding_mask.to(torch.uint8).contiguous()
+    fill_msda_desc(desc, keep, C, n_heads, n_levels, n_points, ref.shape[-1], use_4d_normalizer,
+                   [t for lin in (value_proj, sampling_offsets, attention_weights, output_proj)
+                    for t in (lin.weight, lin.bias.detach().to(torch.bfloat16))])
     ws, wsb = _lib.sized_workspace(q.device, L.vllm_msda_layer_workspace_bytes(ctypes.byref(desc), B, Lq, S), "vllm_msda_layer_workspace_bytes")
     out = torch.empty_like(q)
 
@@ -400,9 +363,6 @@ def msda_layer_prepare(query, reference_points, input_flatten, spatial_shapes, l
         launch.keep = keep   # (parameters referenced by the descriptor stay alive until the call has been enqueued)
         return out
     return launch
-
-
-_LAYER_LINEARS = ("value_proj", "sampling_offsets", "attention_weights", "output_proj")   # the order of VllmMsdaLayerDesc / VllmMsdaLayerGrads
 
 
 def msda_layer_train_ok(query, input_flatten, *linears, reference_points=None):
@@ -431,31 +391,15 @@ def _native_training_wanted(query, input_flatten, linears, reference_points):
 def _train_desc(meta, ref_dim, C, params, keep):
     n_heads, n_levels, n_points, use_4d = meta
     desc = _lib.VllmMsdaLayerDesc()
-    desc.d_model, desc.n_heads, desc.n_levels, desc.n_points = C, n_heads, n_levels, n_points
-    desc.ref_dim, desc.use_4d_normalizer = ref_dim, int(bool(use_4d))
-    for i, name in enumerate(_LAYER_LINEARS):
-        w, b = _lib.aligned(params[2 * i].detach()), _lib.aligned(params[2 * i + 1].detach())
-        keep += [w, b]
-        setattr(desc, name + "_w", w.data_ptr())
-        setattr(desc, name + "_b", b.data_ptr())
+    fill_msda_desc(desc, keep, C, n_heads, n_levels, n_points, ref_dim, use_4d, params)
     return desc
-
-
-def _train_operands(query, reference_points, input_flatten, spatial_shapes, level_start_index, padding_mask):
-    """the C call's operands: contiguous, aligned as include/vllm_hip.h asks (a view at another storage offset is copied)"""
-    q, x = _lib.aligned(query.detach()), _lib.aligned(input_flatten.detach())
-    ref = _lib.aligned(reference_points.detach().to(torch.float32), 16 if reference_points.shape[-1] == 4 else 8)
-    shapes = spatial_shapes.to(device=q.device, dtype=torch.int64).contiguous()
-    lsi = level_start_index.to(device=q.device, dtype=torch.int64).contiguous()
-    mask = None if padding_mask is None else padding_mask.to(torch.uint8).contiguous()
-    return q, ref, x, shapes, lsi, mask
 
 
 class MSDeformAttnLayerFunction(Function):
     """The whole layer as one autograd node over (query, input_flatten, the eight parameters): vllm_msda_layer_forward_train, whose
     output has the bits of the inference call, and vllm_msda_layer_backward.  ``meta`` = (n_heads, n_levels, n_points,
-    use_4d_normalizer); reference_points [B, Lq, L, 2|4] (already expanded), spatial_shapes, level_start_index and padding_mask get no
-    gradient.  Inputs, parameters and the kept activations go through save_for_backward, so an in-place change between forward and
+    use_4d_normalizer); reference_points (anything that broadcasts to [B, Lq, L, 2|4]), spatial_shapes, level_start_index and
+    padding_mask get no gradient.  Inputs, parameters and the kept activations go through save_for_backward, so an in-place change between forward and
     backward fails autograd's version check instead of producing wrong gradients."""
 
     @staticmethod
@@ -467,8 +411,8 @@ class MSDeformAttnLayerFunction(Function):
         keep = []
         desc = _train_desc(meta, reference_points.shape[-1], C, params, keep)
         desc.geometry = known_geometry(spatial_shapes, Lq)
-        q, ref, x, shapes, lsi, mask = _train_operands(query, reference_points, input_flatten, spatial_shapes, level_start_index,
-                                                       padding_mask)
+        q, ref, x, shapes, lsi, mask = memory_operands("msda_layer_train", query.detach(), reference_points.detach(), input_flatten.detach(),
+                                                       spatial_shapes, level_start_index, padding_mask, meta[1])
         dev = q.device
         nsaved = L.vllm_msda_layer_saved_bytes(ctypes.byref(desc), B, Lq, S)
         _lib.check(0 if nsaved >= 0 else -1, "vllm_msda_layer_saved_bytes")
@@ -499,8 +443,8 @@ class MSDeformAttnLayerFunction(Function):
         L = _lib.lib()
         keep = []
         desc = _train_desc(ctx.meta, reference_points.shape[-1], C, params, keep)
-        q, ref, x, shapes, lsi, mask = _train_operands(query, reference_points, input_flatten, spatial_shapes, level_start_index,
-                                                       padding_mask)
+        q, ref, x, shapes, lsi, mask = memory_operands("msda_layer_train", query.detach(), reference_points.detach(), input_flatten.detach(),
+                                                       spatial_shapes, level_start_index, padding_mask, ctx.meta[1])
         dev = q.device
         need_q, need_x = ctx.needs_input_grad[1], ctx.needs_input_grad[3]
         need = list(ctx.needs_input_grad[7:])
@@ -512,7 +456,7 @@ class MSDeformAttnLayerFunction(Function):
         gq = torch.empty((B, Lq, C), **bf) if need_q else None
         gx = torch.empty((B, S, C), **bf) if need_x else None
         gs = _lib.VllmMsdaLayerGrads()
-        for i, name in enumerate(_LAYER_LINEARS):
+        for i, name in enumerate(MSDA_LINEARS):
             setattr(gs, name + "_w", None if grads[2 * i] is None else grads[2 * i].data_ptr())
             setattr(gs, name + "_b", None if grads[2 * i + 1] is None else grads[2 * i + 1].data_ptr())
         g = _lib.aligned(grad_out.to(torch.bfloat16))
@@ -530,23 +474,9 @@ class MSDeformAttnLayerFunction(Function):
 def msda_layer_train(query, reference_points, input_flatten, spatial_shapes, level_start_index, padding_mask, value_proj,
                      sampling_offsets, attention_weights, output_proj, n_heads, n_levels, n_points, use_4d_normalizer=False):
     """msda_layer_forward with a native backward (MSDeformAttnLayerFunction): same arguments, same output bits."""
-    B, Lq, C = query.shape
-    S = input_flatten.shape[1]
     if reference_points.shape[-1] not in (2, 4):
         raise ValueError("Last dim of reference_points must be 2 or 4, but get {} instead.".format(
             reference_points.shape[-1]))
-    if reference_points.dim() != 4 or reference_points.shape[0] not in (1, B) or reference_points.shape[1] not in (1, Lq) or \
-            reference_points.shape[2] not in (1, n_levels):
-        raise RuntimeError(f"msda_layer_train: reference_points {tuple(reference_points.shape)} does not broadcast to "
-                           f"({B}, {Lq}, {n_levels}, 2|4)")
-    reference_points = reference_points.expand(B, Lq, n_levels, reference_points.shape[-1])
-    if tuple(input_flatten.shape) != (B, S, C):
-        raise RuntimeError(f"msda_layer_train: input_flatten {tuple(input_flatten.shape)} vs query {tuple(query.shape)}")
-    if tuple(spatial_shapes.shape) != (n_levels, 2) or level_start_index.numel() != n_levels:
-        raise RuntimeError(f"msda_layer_train: spatial_shapes {tuple(spatial_shapes.shape)} / level_start_index "
-                           f"({level_start_index.numel()}) do not describe {n_levels} levels")
-    if padding_mask is not None and tuple(padding_mask.shape) != (B, S):
-        raise RuntimeError(f"msda_layer_train: padding mask {tuple(padding_mask.shape)} must be ({B}, {S})")
     linears = (value_proj, sampling_offsets, attention_weights, output_proj)
     if not msda_layer_train_ok(query, input_flatten, *linears, reference_points=reference_points):
         raise RuntimeError("msda_layer_train: bf16 CUDA tensors, d_model % 64 == 0, bf16 weights and biases, and reference_points "
