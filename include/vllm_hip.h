@@ -502,6 +502,71 @@ int vllm_box_refine_f32(const uint16_t *h, int ldh, const uint16_t *W, const uin
                         float eps, vllm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * f2e. The two-stage QUERY SELECTION of Grounding-DINO between the encoder and the decoder above, bf16 modules (inference).
+ *
+ * Replaces gen_encoder_output_proposals and the `two_stage` statements of
+ *   OVGroundingDinoModel.forward   visionllmv2/model/grounding_dino/modeling_ov_grounding_dino_mask_dn.py:2228-2276, :2503-2543
+ * with GroundingDinoContrastiveEmbedding (:1410-1428), without the mask heads.  The selection depends only on the row maximum of the class
+ * logits; the box head, the logit rows and the proposal logits are formed for the k selected rows only.  In this order:
+ *   1. extents: per image and level, valid_height = the unpadded cells of column 0, valid_width = those of row 0 (a fixed-order count)
+ *   2. enc_output (GEMM + bias) on the raw memory rows, read in place, then enc_output_norm.  A row the reference zero-fills (padded, or
+ *      an invalid proposal) is normalised from the bias itself: it comes out exactly as LayerNorm(bias).  A proposal is
+ *      ((x + 0.5) / valid_width, (y + 0.5) / valid_height, 0.05 * 2^level twice) in fp32 with a true division, and valid when all four
+ *      values lie strictly inside (0.01, 0.99).
+ *   3. vllm_rowmax_dot_bf16: score[b, s] = bf16(max over unmasked text tokens of q[b, s] . text[b, t]) as fp32; no [B, S, Lt] tensor
+ *   4. vllm_topk_rows_f32: the k largest per image -- value descending, ties by ascending index, NaN greatest
+ *   5. on the B k selected rows: a gather -> target; the box head (two ReLU GEMMs, the last linear in fp32, never rounded) plus the row's
+ *      proposal logit log(p / (1 - p)) (+inf for a padded row or an invalid proposal) -> coords_logits; reference_points = its sigmoid
+ *      (+inf gives 1.0); class_logits = bf16(target . text^T) widened to fp32, -inf at masked tokens and from Lt up to max_text_len.
+ * No atomics on any output: the same bits on every run.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct VllmQuerySelectDesc {
+    int32_t d_model;                         /* C: a multiple of 64 in 64 .. 512 */
+    int32_t max_text_len;                    /* columns of class_logits, 1 .. 256 */
+    int32_t n_levels;                        /* rows of spatial_shapes, 1 .. 16 */
+    float   layer_norm_eps;
+    const uint16_t *enc_output_w, *enc_output_b;             /* [C, C] [C]  (device, bf16) */
+    const uint16_t *enc_output_norm_w, *enc_output_norm_b;   /* [C] [C] */
+    VllmBoxHead box_head;                    /* encoder_output_bbox_embed */
+} VllmQuerySelectDesc;
+unsigned long vllm_query_select_desc_sizeof(void);
+/* Bytes of device scratch vllm_query_select_forward needs; host-only; 0 for B k == 0, negative for a refused descriptor or sizes. */
+long vllm_query_select_workspace_bytes(const VllmQuerySelectDesc *desc, int B, int S, int Lt, int k);
+long vllm_query_select_calls(void);   /* calls of vllm_query_select_forward in this process that reached their launches (tests) */
+/* memory [B, S, C] bf16; padding_mask [B, S] uint8, 1 = padded; text [B, Lt, C] bf16; text_token_mask [B, Lt] uint8, 1 = a real token;
+ * spatial_shapes [n_levels, 2] and level_start_index [n_levels] int64 on the device, describing S rows.  Outputs: topk_index [B, k] int64;
+ * target [B, k, C] bf16; coords_logits and reference_points [B, k, 4] fp32; class_logits [B, k, max_text_len] fp32; scores [B, S] fp32,
+ * optional (NULL keeps them in the workspace).  Sizes: 1 <= Lt <= max_text_len, 1 <= k <= min(S, 2048), B S C 2 < 2^31.  One stream, no
+ * allocation, no synchronisation.  A refused call (NULL or misaligned operand; an output overlapping an input, another output or the
+ * workspace; sizes outside the contract; short or misaligned workspace: VLLM_EINVAL, reason in vllm_last_error()) has enqueued nothing;
+ * B k == 0 returns VLLM_OK. */
+/* Alignment: memory, text, target, coords_logits, reference_points, every weight / bias and workspace 16 bytes; spatial_shapes,
+ * level_start_index, topk_index and the box head's last bias 8 bytes; class_logits, scores 4 bytes; the masks: element alignment. */
+int vllm_query_select_forward(const VllmQuerySelectDesc *desc, const uint16_t *memory, const uint8_t *padding_mask, const uint16_t *text,
+                              const uint8_t *text_token_mask, const int64_t *spatial_shapes, const int64_t *level_start_index, int B, int S,
+                              int Lt, int k, int64_t *topk_index, uint16_t *target, float *coords_logits, float *reference_points,
+                              float *class_logits, float *scores, void *workspace, long workspace_bytes, vllm_stream_t stream);
+/* The three new kernels of the call, exposed for the parity tests and for other selection flavours.  No atomics on an output.
+ * vllm_rowmax_dot_bf16: scores [B, S] fp32 = bf16(max over tokens t with text_token_mask[b, t] != 0 of sum_c q[b, s, c] text[b, t, c]),
+ *   fp32 accumulation; q [B, S, C], text [B, Lt, C] bf16, dense.  Every token masked: -inf; a NaN logit: NaN.  C a multiple of 64 in
+ *   64 .. 512, 1 <= Lt <= 256, any S.
+ * vllm_topk_rows_f32: index [B, k] int64 = per row of scores [B, S] the indices of its k largest, value descending, ties by ascending
+ *   index, NaN greatest, -0 == +0: torch.sort(scores, descending=True, stable=True).indices[:, :k].  1 <= k <= min(S, 2048), S < 2^31.
+ * vllm_query_select_tail_f32: step 1 and the fp32 part of step 5 for rows given by topk_index [B, k]: extents [B, L, 2] int32 (written),
+ *   coords_logits[r] = h[r] . W^T + b + proposal logit, reference_points = sigmoid; h [B k, C] bf16 with row stride ldh (a multiple of 8,
+ *   at least C), W [4, C], b [4] bf16; valid [B k] uint8 (optional): the proposals' validity flags.
+ * A refused call (VLLM_EINVAL) has enqueued nothing; no rows returns VLLM_OK. */
+/* Alignment: q, text, h, W, coords_logits, reference_points 16 bytes; b, index, topk_index and the level tensors 8 bytes; scores,
+ * extents 4 bytes. */
+int vllm_rowmax_dot_bf16(const uint16_t *q, const uint16_t *text, const uint8_t *text_token_mask, int B, int S, int Lt, int C, float *scores,
+                         vllm_stream_t stream);
+int vllm_topk_rows_f32(const float *scores, int B, int S, int k, int64_t *index, vllm_stream_t stream);
+int vllm_query_select_tail_f32(const uint16_t *h, int ldh, const uint16_t *W, const uint16_t *b, const int64_t *topk_index,
+                               const uint8_t *padding_mask, const int64_t *spatial_shapes, const int64_t *level_start_index, int B, int S,
+                               int L, int k, int C, int32_t *extents, float *coords_logits, float *reference_points, uint8_t *valid,
+                               vllm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * f3b. The whole DCNv3 layer, bf16 modules (inference).
  *
  * Replaces the body of DCNv3.forward, visionllmv2/model/ops_dcnv3/modules/dcnv3.py:313-351, with the CenterFeatureScaleModule

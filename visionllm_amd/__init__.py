@@ -12,6 +12,9 @@ Host-side mirror of the reference's operator/module interfaces for that path onl
 * ``deformable_decoder`` -- ``DeformableTransformerDecoderLayer`` (UniPose) and ``GroundingDinoDecoderLayer`` (HF) mirrors with the
   one-call native forward, and ``GroundingDinoDecoder`` (with ``GroundingDinoMLPPredictionHead``), the whole decoder loop as one native
   call; the four names are also attributes of this package.
+* ``query_selection`` -- ``GroundingDinoQuerySelection``: the two-stage query selection between that encoder and that decoder
+  (``gen_encoder_output_proposals``, the contrastive class head, the top-k and the gathers) with the one-call native forward; also an
+  attribute of this package.
 
 All compute goes through ``libvllm_hip.so`` (hand-written HIP, C ABI in ``include/vllm_hip.h``).  There is NO
 CPU fallback: calling an op without the built extension, or with CPU tensors, raises.
@@ -22,7 +25,8 @@ __version__ = "0.1.0"
 
 _ENCODER_EXPORTS = ("DeformableTransformerEncoderLayer", "GroundingDinoDeformableLayer", "encoder_layers_forward")
 _DECODER_EXPORTS = ("DeformableTransformerDecoderLayer", "GroundingDinoDecoderLayer", "GroundingDinoDecoder", "GroundingDinoMLPPredictionHead")
-__all__ = ["build", "lib", "lib_path", *_ENCODER_EXPORTS, *_DECODER_EXPORTS]
+_SELECTION_EXPORTS = ("GroundingDinoQuerySelection",)
+__all__ = ["build", "lib", "lib_path", *_ENCODER_EXPORTS, *_DECODER_EXPORTS, *_SELECTION_EXPORTS]
 
 
 def __getattr__(name):
@@ -33,4 +37,7 @@ def __getattr__(name):
     if name in _DECODER_EXPORTS:
         from . import deformable_decoder
         return getattr(deformable_decoder, name)
+    if name in _SELECTION_EXPORTS:
+        from . import query_selection
+        return getattr(query_selection, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -186,6 +186,11 @@ class VllmDeformDecoderDesc(ctypes.Structure):
                [("box_heads", ctypes.POINTER(VllmBoxHead))]
 
 
+class VllmQuerySelectDesc(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("d_model", "max_text_len", "n_levels")] + [("layer_norm_eps", ctypes.c_float)] + \
+               [(n, _P) for n in ("enc_output_w", "enc_output_b", "enc_output_norm_w", "enc_output_norm_b")] + [("box_head", VllmBoxHead)]
+
+
 class VllmDcnv3LayerDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("channels", "group", "kernel_size", "dw_kernel_size", "dilation", "center_feature_scale",
                                               "n_proj")] + \
@@ -257,6 +262,7 @@ def check_struct_layouts():
     assert ctypes.sizeof(VllmDeformEncLayerDesc) == L.vllm_deform_enc_layer_desc_sizeof(), "VllmDeformEncLayerDesc layout mismatch"
     assert ctypes.sizeof(VllmDeformDecLayerDesc) == L.vllm_deform_dec_layer_desc_sizeof(), "VllmDeformDecLayerDesc layout mismatch"
     assert ctypes.sizeof(VllmDeformDecoderDesc) == L.vllm_deform_decoder_desc_sizeof(), "VllmDeformDecoderDesc layout mismatch"
+    assert ctypes.sizeof(VllmQuerySelectDesc) == L.vllm_query_select_desc_sizeof(), "VllmQuerySelectDesc layout mismatch"
     assert ctypes.sizeof(VllmVitDesc) == L.vllm_vit_desc_sizeof(), "VllmVitDesc layout mismatch"
     assert ctypes.sizeof(VllmVitLayer) == L.vllm_vit_layer_sizeof(), "VllmVitLayer layout mismatch"
     assert ctypes.sizeof(VllmBridgeDesc) == L.vllm_bridge_desc_sizeof(), "VllmBridgeDesc layout mismatch"
