@@ -314,7 +314,10 @@ def test_every_runtime_option_is_documented_in_the_header():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = open(os.path.join(root, "visionllm_amd", "csrc", "runtime.cpp")).read()
     hdr = open(os.path.join(root, "include", "vllm_hip.h")).read()
-    names = sorted(set(re.findall(r'strcmp\(name, "([a-z_0-9]+)"\)', src)))
+    names = sorted(re.findall(r'^\s*\{"([a-z_0-9]+)", "VLLM_[A-Z_0-9]+", ', src, flags=re.M))   # the rows of the option table
     assert len(names) >= 8, names
+    assert names == sorted(["msda_tiled", "dcnv3_tiled", "dcnv3_bwd_tiled", "gemm_half_tail", "gemm_res_ring", "msda_layer_value_bf16",
+                            "gemm_skinny", "deform_enc_ffn_slab_rows", "msda_layer_fused", "gemm_direct_store", "attn_variant", "gemm_tile_rb",
+                            "gemm_variant"])
     missing = [n for n in names if f'"{n}"' not in hdr]
     assert not missing, f"options without a description in include/vllm_hip.h: {missing}"

@@ -1,5 +1,7 @@
-"""ctypes binding of libvllm_hip.so.  The header ``include/vllm_hip.h`` is the single source of truth: the
-prototypes below are parsed from it, so a symbol that is declared but not exported fails at load time."""
+"""ctypes binding of libvllm_hip.so.  The header ``include/vllm_hip.h`` is the single source of truth: the prototypes AND the
+descriptor structs (``_lib.VllmVitDesc``, ...) are parsed from it when this module is imported, which does not load the library.
+Loading it (``lib()``) fails when a declared symbol is not exported, and checks every struct's size against the library's own
+``vllm_*_sizeof()`` once."""
 import ctypes
 import os
 import re
@@ -56,8 +58,36 @@ def parse_header(path: str = HEADER):
     return protos
 
 
+_MEMBER_CTYPES = {
+    "int": ctypes.c_int, "int32_t": ctypes.c_int32, "long": ctypes.c_long, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+    "double": ctypes.c_double, "uint16_t": ctypes.c_uint16, "uint8_t": ctypes.c_uint8,
+}
+
+
+def parse_structs(path: str = HEADER):
+    """-> {name: ctypes.Structure subclass} for every ``typedef struct ... { ... } Name;`` of the header, in declaration order.  A
+    pointer member is c_void_p, a pointer to an earlier struct POINTER(that class), a struct by value that class, ``[N]`` an array.
+    A declaration that is none of these raises: a member left out would shift every member behind it."""
+    src = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    src = re.sub(r"//[^\n]*", " ", src)
+    structs = {}
+    for m in re.finditer(r"typedef\s+struct\s+\w*\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
+        name, fields = m.group(2), []
+        for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):
+            head = re.match(r"(?:const\s+)?(\w+)\b(.*)", decl, flags=re.S)
+            base = head and (structs.get(head.group(1)) or _MEMBER_CTYPES.get(head.group(1)))
+            members = [re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*", d) for d in head.group(2).split(",")] if base else [None]
+            if not all(members):
+                raise ValueError(f"{path}: struct {name}: cannot read the member declaration {decl!r}")
+            for star, member, count in (dm.groups() for dm in members):
+                t = base if not star else ctypes.POINTER(base) if issubclass(base, ctypes.Structure) else ctypes.c_void_p
+                fields.append((member, t * int(count) if count else t))
+        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+    return structs
+
+
 def header_abi_version(path: str = HEADER) -> int:
-    """VLLM_ABI_VERSION of include/vllm_hip.h (the mirrors below are written against THIS header)."""
+    """VLLM_ABI_VERSION of include/vllm_hip.h (the structs below are parsed from THIS header)."""
     m = re.search(r"^#define\s+VLLM_ABI_VERSION\s+(\d+)", open(path).read(), flags=re.M)
     if not m:
         raise RuntimeError("include/vllm_hip.h: VLLM_ABI_VERSION not found")
@@ -79,7 +109,8 @@ def lib():
     # ("no ROCm-capable device is detected" at the first launch).
     import torch  # noqa: F401
     L = ctypes.CDLL(path)
-    for name, (restype, argtypes) in parse_header().items():
+    protos = parse_header()
+    for name, (restype, argtypes) in protos.items():
         fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
         fn.restype = restype
         fn.argtypes = argtypes
@@ -87,6 +118,7 @@ def lib():
     if L.vllm_abi_version() != want:
         raise RuntimeError(f"libvllm_hip.so ABI version {L.vllm_abi_version()} != header's VLLM_ABI_VERSION {want}: rebuild "
                            "(make -C visionllm_amd/csrc)")
+    _check_struct_layouts(L, protos)
     _lib = L
     return L
 
@@ -124,155 +156,41 @@ def current_stream(device=None):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
-# ---- ctypes mirrors of the descriptor structs of include/vllm_hip.h (sizes are verified against the library) ----
-_P = ctypes.c_void_p
+# ---- the descriptor structs of include/vllm_hip.h as ctypes classes: _lib.VllmVitDesc, ... (generated, never written by hand) ----
+STRUCTS = parse_structs()
+globals().update(STRUCTS)
 
 
-class VllmVitLayer(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ("norm1_w", "norm1_b", "qkv_w", "qkv_b", "q_norm_w", "k_norm_w", "proj_w", "proj_b",
-                                  "ls1", "norm2_w", "norm2_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2",
-                                  "qkv_w_ln", "qkv_colsum", "qkv_bias_ln", "fc1_w_ln", "fc1_colsum", "fc1_bias_ln")]
+def pointer_fields(struct):
+    """Names of ``struct``'s plain pointer members (no arrays, no pointers to structs), in the header's order: the order in which a
+    caller walks the weights, saved tensors or gradients that the struct carries."""
+    return tuple(n for n, t in struct._fields_ if t is ctypes.c_void_p)
 
 
-class VllmVitDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("arch", "num_layers", "hidden", "heads", "inter", "patch", "image",
-                                            "kpad", "act", "pixel_is_f32")] + \
-               [("eps", ctypes.c_float)] + \
-               [(n, _P) for n in ("patch_w", "patch_b", "cls", "pos", "pre_ln_w", "pre_ln_b")] + \
-               [("layers", ctypes.POINTER(VllmVitLayer))]
+REGION_PARAMS = pointer_fields(STRUCTS["VllmRegionEncoderGrads"])   # the stem's parameters; VllmRegionEncoder has them in this order too
 
 
-class VllmBridgeDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("kind", "depth", "in_features", "out_features", "pixel_shuffle",
-                                            "skip_cls")] + \
-               [("ln_eps", ctypes.c_float), ("ln_w", _P), ("ln_b", _P), ("w", _P * 4), ("b", _P * 4)]
-
-
-class VllmMsdaLayerDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("d_model", "n_heads", "n_levels", "n_points", "ref_dim",
-                                              "use_4d_normalizer", "geometry", "reserved0")] + \
-               [(n, _P) for n in ("value_proj_w", "value_proj_b", "sampling_offsets_w", "sampling_offsets_b",
-                                  "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
-
-
-class VllmMsdaLayerGrads(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ("value_proj_w", "value_proj_b", "sampling_offsets_w", "sampling_offsets_b",
-                                  "attention_weights_w", "attention_weights_b", "output_proj_w", "output_proj_b")]
-
-
-class VllmDeformEncLayerDesc(ctypes.Structure):
-    _fields_ = [("attn", VllmMsdaLayerDesc), ("d_ffn", ctypes.c_int32), ("act", ctypes.c_int32), ("norm1_eps", ctypes.c_float),
-                ("norm2_eps", ctypes.c_float)] + \
-               [(n, _P) for n in ("norm1_w", "norm1_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "norm2_w", "norm2_b")]
-
-
-class VllmDeformDecLayerDesc(ctypes.Structure):
-    _fields_ = [("cross_attn", VllmMsdaLayerDesc)] + \
-               [(n, ctypes.c_int32) for n in ("d_ffn", "act", "n_heads_sa", "has_self_attn", "has_text_attn")] + \
-               [(n, ctypes.c_float) for n in ("sa_norm_eps", "text_norm_eps", "ca_norm_eps", "ffn_norm_eps")] + \
-               [(n, _P) for n in ("sa_in_proj_w", "sa_in_proj_b", "sa_out_proj_w", "sa_out_proj_b", "sa_norm_w", "sa_norm_b",
-                                  "text_in_proj_w", "text_in_proj_b", "text_out_proj_w", "text_out_proj_b", "text_norm_w", "text_norm_b",
-                                  "ca_norm_w", "ca_norm_b", "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ffn_norm_w", "ffn_norm_b")]
-
-
-class VllmBoxHead(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ("w0", "b0", "w1", "b1", "w2", "b2")]
-
-
-class VllmDeformDecoderDesc(ctypes.Structure):
-    _fields_ = [("n_layers", ctypes.c_int32), ("n_pos_feats", ctypes.c_int32), ("layer_norm_eps", ctypes.c_float),
-                ("inverse_sigmoid_eps", ctypes.c_float), ("layers", ctypes.POINTER(VllmDeformDecLayerDesc))] + \
-               [(n, _P) for n in ("ref_head_w0", "ref_head_b0", "ref_head_w1", "ref_head_b1", "layer_norm_w", "layer_norm_b", "dim_t")] + \
-               [("box_heads", ctypes.POINTER(VllmBoxHead))]
-
-
-class VllmQuerySelectDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("d_model", "max_text_len", "n_levels")] + [("layer_norm_eps", ctypes.c_float)] + \
-               [(n, _P) for n in ("enc_output_w", "enc_output_b", "enc_output_norm_w", "enc_output_norm_b")] + [("box_head", VllmBoxHead)]
-
-
-class VllmDcnv3LayerDesc(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("channels", "group", "kernel_size", "dw_kernel_size", "dilation", "center_feature_scale",
-                                              "n_proj")] + \
-               [("offset_scale", ctypes.c_float), ("ln_eps", ctypes.c_float), ("reserved0", ctypes.c_int32)] + \
-               [(n, _P) for n in ("input_proj_w", "input_proj_b", "dw_w", "dw_b", "ln_w", "ln_b", "proj_w", "proj_b",
-                                  "output_proj_w", "output_proj_b")]
-
-
-class VllmVitLayerTrain(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("hidden", "heads", "inter")] + [("eps", ctypes.c_float)] + \
-               [(n, _P) for n in ("norm1_w", "qkv_w", "qkv_b", "q_norm_w", "k_norm_w", "proj_w", "proj_b", "ls1", "norm2_w",
-                                  "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2")]
-
-
-class VllmVitLayerSaved(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ("qkv", "ctx", "lse", "y1", "x1", "h1", "a1", "y2")]
-
-
-class VllmVitLayerGrads(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ("norm1_w", "qkv_w", "qkv_b", "q_norm_w", "k_norm_w", "proj_w", "proj_b", "ls1", "norm2_w",
-                                  "fc1_w", "fc1_b", "fc2_w", "fc2_b", "ls2")]
-
-
-class VllmClipLayerTrain(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("hidden", "heads", "inter", "act")] + [("eps", ctypes.c_float)] + \
-               [(n, _P) for n in ("norm1_w", "norm1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "norm2_w", "norm2_b", "fc1_w", "fc1_b",
-                                  "fc2_w", "fc2_b")]
-
-
-class VllmClipLayerSaved(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ("qkv", "ctx", "lse", "x1", "h1", "a1")]
-
-
-class VllmClipLayerGrads(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ("norm1_w", "norm1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "norm2_w", "norm2_b", "fc1_w", "fc1_b",
-                                  "fc2_w", "fc2_b")]
-
-
-class VllmVitEmbed(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("hidden", "patch", "image", "pixel_is_f32")] + \
-               [(n, _P) for n in ("patch_w", "patch_b", "cls", "pos")]
-
-
-REGION_PARAMS = ("conv1_w", "conv1_b", "ln1_w", "ln1_b", "conv2_w", "conv2_b", "ln2_w", "ln2_b", "conv3_w", "conv3_b", "up_w", "up_b")
-
-
-class VllmRegionEncoder(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int) for n in ("hidden", "embed", "out_dim", "patch", "n", "H", "W", "levels", "points", "pixel_is_f32")] + \
-               [("eps", ctypes.c_float), ("reserved0", ctypes.c_int)] + [(n, _P) for n in REGION_PARAMS] + \
-               [("level", _P * 4), ("level_row_stride", ctypes.c_long * 4), ("level_image_stride", ctypes.c_long * 4)]
-
-
-class VllmRegionEncoderSaved(ctypes.Structure):
-    _fields_ = [(n, _P) for n in ("a1", "y1", "pre1", "g1", "y2", "pre2", "g2", "stem", "pooled")]
-
-
-class VllmRegionEncoderGrads(ctypes.Structure):
-    _fields_ = [(n, _P) for n in REGION_PARAMS] + [("level", _P * 4)]
+def _check_struct_layouts(L, protos):
+    """Every struct against the library's own sizeof: ``VllmFooBar`` against ``vllm_foo_bar_sizeof()``.  One without such an export
+    has to lie by value inside one that has it."""
+    checked = []
+    for name, cls in STRUCTS.items():
+        fn = "vllm_" + re.sub(r"(?<!^)(?=[A-Z])", "_", name[len("Vllm"):]).lower() + "_sizeof"
+        if fn not in protos:
+            continue
+        if ctypes.sizeof(cls) != getattr(L, fn)():
+            raise RuntimeError(f"{name}: {ctypes.sizeof(cls)} bytes as parsed from include/vllm_hip.h, {getattr(L, fn)()} in libvllm_hip.so: "
+                               "rebuild (make -C visionllm_amd/csrc)")
+        checked.append(cls)
+    inside = {t._type_ if issubclass(t, ctypes.Array) else t for c in checked for _, t in c._fields_}
+    loose =[n for n, cls in STRUCTS.items() if cls not in checked and cls not in inside]
+    if loose:
+        raise RuntimeError(f"include/vllm_hip.h: no vllm_*_sizeof() covers {', '.join(loose)}")
 
 
 def check_struct_layouts():
-    L = lib()
-    assert ctypes.sizeof(VllmRegionEncoder) == L.vllm_region_encoder_sizeof(), "VllmRegionEncoder layout mismatch"
-    assert ctypes.sizeof(VllmRegionEncoderSaved) == L.vllm_region_encoder_saved_sizeof(), "VllmRegionEncoderSaved layout mismatch"
-    assert ctypes.sizeof(VllmRegionEncoderGrads) == L.vllm_region_encoder_grads_sizeof(), "VllmRegionEncoderGrads layout mismatch"
-    assert ctypes.sizeof(VllmMsdaLayerDesc) == L.vllm_msda_layer_desc_sizeof(), "VllmMsdaLayerDesc layout mismatch"
-    assert ctypes.sizeof(VllmMsdaLayerGrads) == L.vllm_msda_layer_grads_sizeof(), "VllmMsdaLayerGrads layout mismatch"
-    assert ctypes.sizeof(VllmDcnv3LayerDesc) == L.vllm_dcnv3_layer_desc_sizeof(), "VllmDcnv3LayerDesc layout mismatch"
-    assert ctypes.sizeof(VllmDeformEncLayerDesc) == L.vllm_deform_enc_layer_desc_sizeof(), "VllmDeformEncLayerDesc layout mismatch"
-    assert ctypes.sizeof(VllmDeformDecLayerDesc) == L.vllm_deform_dec_layer_desc_sizeof(), "VllmDeformDecLayerDesc layout mismatch"
-    assert ctypes.sizeof(VllmDeformDecoderDesc) == L.vllm_deform_decoder_desc_sizeof(), "VllmDeformDecoderDesc layout mismatch"
-    assert ctypes.sizeof(VllmQuerySelectDesc) == L.vllm_query_select_desc_sizeof(), "VllmQuerySelectDesc layout mismatch"
-    assert ctypes.sizeof(VllmVitDesc) == L.vllm_vit_desc_sizeof(), "VllmVitDesc layout mismatch"
-    assert ctypes.sizeof(VllmVitLayer) == L.vllm_vit_layer_sizeof(), "VllmVitLayer layout mismatch"
-    assert ctypes.sizeof(VllmBridgeDesc) == L.vllm_bridge_desc_sizeof(), "VllmBridgeDesc layout mismatch"
-    assert ctypes.sizeof(VllmVitLayerTrain) == L.vllm_vit_layer_train_sizeof(), "VllmVitLayerTrain layout mismatch"
-    assert ctypes.sizeof(VllmVitLayerSaved) == L.vllm_vit_layer_saved_sizeof(), "VllmVitLayerSaved layout mismatch"
-    assert ctypes.sizeof(VllmVitLayerGrads) == L.vllm_vit_layer_grads_sizeof(), "VllmVitLayerGrads layout mismatch"
-    assert ctypes.sizeof(VllmVitEmbed) == L.vllm_vit_embed_sizeof(), "VllmVitEmbed layout mismatch"
-    assert ctypes.sizeof(VllmClipLayerTrain) == L.vllm_clip_layer_train_sizeof(), "VllmClipLayerTrain layout mismatch"
-    assert ctypes.sizeof(VllmClipLayerSaved) == L.vllm_clip_layer_saved_sizeof(), "VllmClipLayerSaved layout mismatch"
-    assert ctypes.sizeof(VllmClipLayerGrads) == L.vllm_clip_layer_grads_sizeof(), "VllmClipLayerGrads layout mismatch"
+    """The layouts are checked once, when the library is loaded: this loads it."""
+    lib()
 
 
 EPI_BIAS, EPI_GELU, EPI_QUICK_GELU, EPI_RESIDUAL, EPI_EMBED, EPI_F32 = 0, 1, 2, 3, 4, 5

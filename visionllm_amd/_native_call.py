@@ -6,7 +6,7 @@ from torch import nn
 
 from . import _lib
 
-MSDA_LINEARS = ("value_proj", "sampling_offsets", "attention_weights", "output_proj")   # the order of VllmMsdaLayerDesc / VllmMsdaLayerGrads
+MSDA_LINEARS = tuple(n[:-2] for n in _lib.pointer_fields(_lib.VllmMsdaLayerGrads) if n.endswith("_w"))   # each a <name>_w, <name>_b pair
 ACT_RELU, ACT_GELU = 0, _lib.EPI_GELU   # VllmDeformEncLayerDesc.act / VllmDeformDecLayerDesc.act
 
 

@@ -70,7 +70,6 @@ def _desc_for(mod, kind, pixel_shuffle_flag, skip_cls, keep):
 
 def _run(desc, hidden, n, T, C):
     lib = _lib.lib()
-    _lib.check_struct_layouts()
     T_out = T // 4 if desc.pixel_shuffle else T
     out = torch.empty((n, T_out, desc.out_features), dtype=torch.bfloat16, device=hidden.device)
     with torch.cuda.device(hidden.device):
@@ -176,7 +175,6 @@ class _BridgeTrain(torch.autograd.Function):
         d = _BridgeTrain._desc(kind, depth, eps, params, keep)
         rows, cout, dev = x.shape[0], d.out_features, x.device
         L = _lib.lib()
-        _lib.check_struct_layouts()
         out = torch.empty((rows, cout), dtype=torch.bfloat16, device=dev)
         pre = [torch.empty((rows, cout), dtype=torch.bfloat16, device=dev) for _ in range(depth - 1)]
         act = [torch.empty((rows, cout), dtype=torch.bfloat16, device=dev) for _ in range(depth - 1)]

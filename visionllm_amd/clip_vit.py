@@ -121,9 +121,8 @@ class _CLIPLayerNorm(nn.LayerNorm):
         return y.view(x.shape)
 
 
-_LAYER_PARAMS = ("norm1_w", "norm1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "norm2_w", "norm2_b", "fc1_w", "fc1_b", "fc2_w",
-                 "fc2_b")   # the order of VllmClipLayerTrain / VllmClipLayerGrads
-_SAVED = ("qkv", "ctx", "lse", "x1", "h1", "a1")   # VllmClipLayerSaved
+_LAYER_PARAMS = _lib.pointer_fields(_lib.VllmClipLayerGrads)   # the 12 of VllmClipLayerTrain too, in the same order
+_SAVED = _lib.pointer_fields(_lib.VllmClipLayerSaved)
 # the module's parameters as the autograd node receives them: q, k, v weights and biases apart (their gradients are slices of qkv's)
 _MODULE_PARAMS = ("norm1_w", "norm1_b", "q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "proj_w", "proj_b", "norm2_w", "norm2_b", "fc1_w",
                   "fc1_b", "fc2_w", "fc2_b")
@@ -304,7 +303,6 @@ class CLIPVisionModel(nn.Module):
             return plan.desc
         for n_, p in self.named_parameters():
             _require_bf16_cuda(n_, p)
-        _lib.check_struct_layouts()
         vm = self.vision_model
         emb = vm.embeddings
         kpad = kpad_for(cfg.patch_size)

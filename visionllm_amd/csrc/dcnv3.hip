@@ -9,6 +9,7 @@
 // clamped addresses and selects decide what contributes (a NaN at a clamped address cannot leak).
 #include "common.hpp"
 #include "dcnv3_geo.hpp"
+#include "kernels.hpp"
 
 namespace vllm {
 
@@ -18,7 +19,6 @@ int dcnv3_tiled_launch(const float *in, const float *off, const float *msk, cons
 bool dcnv3_pipe_ok(const Dcnv3Geo &q);                                                                           // dcnv3_pipe.hip
 int dcnv3_pipe_launch(const float *in, const float *off, const float *msk, const Dcnv3Geo &q, float offset_scale, float *out, int prof,
                       hipStream_t st);
-int dcnv3_tiled_enabled();   // runtime.cpp: 0 gather kernel, 1 pipelined tiled kernel (2: + phase clock), 3 two-block tiled kernel (4: + phase clock)
 
 namespace {
 

@@ -231,19 +231,6 @@ int bwd_geo(Dcnv3Geo &q, int N, int H, int W, int G, int C, int kh, int kw, int 
 }  // namespace
 }  // namespace vllm
 
-namespace vllm {
-static int g_dcnv3_bwd_tiled = -1;
-int dcnv3_bwd_tiled()
-{
-    if (g_dcnv3_bwd_tiled < 0) {
-        const char *e = getenv("VLLM_DCNV3_BWD_TILED");
-        g_dcnv3_bwd_tiled = e ? atoi(e) != 0 : 1;
-    }
-    return g_dcnv3_bwd_tiled;
-}
-int dcnv3_bwd_tiled_set(int v) { const int old = dcnv3_bwd_tiled(); g_dcnv3_bwd_tiled = v != 0; return old; }
-}  // namespace vllm
-
 using namespace vllm;
 
 extern "C" int vllm_dcnv3_backward_f32(const float *input, const float *offset, const float *mask, const float *grad_output, int N,

@@ -19,10 +19,9 @@
 // offsets being small.  Results equal the gather kernel to fp32 rounding (the mask value is folded into the weights).
 #include "common.hpp"
 #include "dcnv3_geo.hpp"
+#include "kernels.hpp"
 
 namespace vllm {
-
-int dcnv3_tiled_enabled();   // runtime.cpp
 
 namespace {
 

@@ -160,12 +160,9 @@ int ffn_block_run(hipStream_t st, const FfnBlock &k, const uint16_t *x, long R, 
 
 namespace {
 
-// rows of the FFN intermediate per slab; 0 = the whole tensor at once, the default: measured at cfg 4, B = 8 the whole tensor is the
-// fastest of 0 / 65 536 / 16 384 rows (2191 / 2267 / 2360 us per layer, profiles/deform_encoder_layer.txt); a slab height is for
-// callers who want the smaller workspace
-int g_slab_rows = -1;
-constexpr int SLAB_DEFAULT = 0;
-
+// deform_enc_ffn_slab_rows(): rows of the FFN intermediate per slab; 0 = the whole tensor at once, the default: measured at cfg 4, B = 8
+// the whole tensor is the fastest of 0 / 65 536 / 16 384 rows (2191 / 2267 / 2360 us per layer, profiles/deform_encoder_layer.txt); a slab
+// height is for callers who want the smaller workspace
 struct EncWs {
     long t0, x1, h, attn, total;   // t0: the query, later linear2's output; x1: src + attn, normalised in place; h: a slab of the intermediate
     long slab;                     // rows per slab
@@ -210,16 +207,6 @@ int enc_check_desc(const VllmDeformEncLayerDesc *d)
 long g_calls = 0;
 
 }  // namespace
-
-int deform_enc_ffn_slab_rows()
-{
-    if (g_slab_rows < 0) {
-        const char *e = getenv("VLLM_DEFORM_ENC_FFN_SLAB_ROWS");
-        g_slab_rows = e && atoi(e) >= 0 ? atoi(e) : SLAB_DEFAULT;
-    }
-    return g_slab_rows;
-}
-int deform_enc_ffn_slab_rows_set(int v) { const int old = deform_enc_ffn_slab_rows(); g_slab_rows = v; return old; }
 
 }  // namespace vllm
 

@@ -840,28 +840,8 @@ bool gemm256p_takes(int epi, const GemmArgs &a, int cus)
 
 static long g_p_half_launches = 0;   // launches whose last round ran as half-height tiles (tests assert the path they mean to cover ran)
 long gemm256p_half_launches() { return g_p_half_launches; }
-static int g_half_tail = -1;
-int gemm_half_tail()
-{
-    if (g_half_tail < 0) {
-        const char *e = getenv("VLLM_GEMM_HALF_TAIL");
-        g_half_tail = e ? atoi(e) != 0 : 1;
-    }
-    return g_half_tail;
-}
-int gemm_half_tail_set(int v) { const int old = gemm_half_tail(); g_half_tail = v != 0; return old; }
 // The residual epilogue without LayerScale takes its residual through the operand ring (kernel comment, RING) unless switched off:
 // VLLM_GEMM_RES_RING=0 / vllm_set_option("gemm_res_ring", 0) keep the epilogue's own loads (same-process A/B, tests of both routes).
-static int g_res_ring = -1;
-int gemm_res_ring()
-{
-    if (g_res_ring < 0) {
-        const char *e = getenv("VLLM_GEMM_RES_RING");
-        g_res_ring = e ? atoi(e) != 0 : 1;
-    }
-    return g_res_ring;
-}
-int gemm_res_ring_set(int v) { const int old = gemm_res_ring(); g_res_ring = v != 0; return old; }
 static long g_p_launches = 0;   // (vllm_gemm_persistent_launches: tests assert the path they mean to cover ran)
 long gemm256p_launches() { return g_p_launches; }
 

@@ -343,17 +343,6 @@ __global__ __launch_bounds__(SK_THREADS, 1) void gemm_skinny_kernel(const GemmAr
 
 }  // namespace
 
-static int g_skinny = -1;
-int gemm_skinny_enabled()
-{
-    if (g_skinny < 0) {
-        const char *e = getenv("VLLM_GEMM_SKINNY");
-        g_skinny = e ? atoi(e) != 0 : 1;
-    }
-    return g_skinny;
-}
-int gemm_skinny_set(int v) { const int old = gemm_skinny_enabled(); g_skinny = v != 0; return old; }
-
 // Does the shape belong here?  K = 256, N = 256 (fp32 / bias epilogues) or 8 heads x (8 L offsets + 4 L logits), L <= 4 levels of 4 points
 // (EPI_MSDA: 256 + 128 features at L = 4, 192 + 96 for the 3-level pixel decoder, msdeformattn_pixel_decoder.py:57-58), plain rows.
 bool gemm_skinny_takes(int epi, const GemmArgs &a)

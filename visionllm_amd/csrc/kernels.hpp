@@ -92,33 +92,46 @@ struct GemmArgs {
     uint16_t *pre = nullptr;   // EPI_GELU_SAVE / EPI_QUICK_GELU_SAVE / EPI_RESIDUAL_SAVE: [M, N] bf16 pre-activation / pre-LayerScale output, row stride ldy (8-byte aligned)
 };
 
-int gemm_direct_store();       // VLLM_GEMM_DIRECT_STORE / vllm_set_option("gemm_direct_store")
-int gemm_variant_override();   // VLLM_GEMM_VARIANT / vllm_set_option("gemm_variant")
-extern int g_gemm_tile_rb;
-int gemm_tile_rb();            // VLLM_GEMM_TILE_RB / vllm_set_option("gemm_tile_rb"): -1 automatic, 0 dense XCD order, RB > 0 banded
-int attn_variant();            // VLLM_ATTN_VARIANT / vllm_set_option("attn_variant"): bit0 pipe, bit1 defer, bit2 prio,
-                               // bit3 asm tr-reads, bit4 no padding trim, 32 = automatic (default)
-// gemm_skinny.hip: K = 256, N = 256 / 384 (the linears of a deformable-attention layer); VLLM_GEMM_SKINNY / option "gemm_skinny"
+// The runtime options of vllm_set_option("<name>") / VLLM_<NAME>: one id here, one row in the table of runtime.cpp (same order), which
+// holds the name, the default and the rule for a value.  g_options holds the current values; OPT_UNREAD = the environment has not been
+// read yet, which the first get does.  Plain ints without locking: see the header on when they may change.
+enum OptionId : int {
+    OPT_MSDA_TILED, OPT_DCNV3_TILED, OPT_DCNV3_BWD_TILED, OPT_GEMM_HALF_TAIL, OPT_GEMM_RES_RING, OPT_MSDA_LAYER_VALUE_BF16, OPT_GEMM_SKINNY,
+    OPT_DEFORM_ENC_FFN_SLAB_ROWS, OPT_MSDA_LAYER_FUSED, OPT_GEMM_DIRECT_STORE, OPT_ATTN_VARIANT, OPT_GEMM_TILE_RB, OPT_GEMM_VARIANT, OPT_COUNT
+};
+constexpr int OPT_UNREAD = -2147483647 - 1;   // no rule lets an option hold it
+struct OptionValues {
+    int v[OPT_COUNT];
+    constexpr OptionValues() : v{} { for (int &x : v) x = OPT_UNREAD; }
+};
+extern OptionValues g_options;
+int option_from_env(int id);   // runtime.cpp
+inline int option(int id)
+{
+    const int v = g_options.v[id];
+    return v != OPT_UNREAD ? v : option_from_env(id);
+}
+inline int msda_tiled_enabled() { return option(OPT_MSDA_TILED); }       // 0 gather kernel, 1 automatic (default), 21 automatic with generation 9's phase clock
+inline int dcnv3_tiled_enabled() { return option(OPT_DCNV3_TILED); }     // 0 gather kernel, 1 pipelined tiled kernel (2: + phase clock), 3 two-block tiled kernel (4: + phase clock)
+inline int dcnv3_bwd_tiled() { return option(OPT_DCNV3_BWD_TILED); }
+inline int gemm_half_tail() { return option(OPT_GEMM_HALF_TAIL); }       // half-height tiles in the persistent GEMM's last round
+inline int gemm_res_ring() { return option(OPT_GEMM_RES_RING); }         // the persistent GEMM's residual (no LayerScale) through the operand ring
+inline int msda_layer_value_bf16() { return option(OPT_MSDA_LAYER_VALUE_BF16); }   // 0: keep the value in fp32 for every query set (A/B)
+inline int gemm_skinny_enabled() { return option(OPT_GEMM_SKINNY); }
+inline int deform_enc_ffn_slab_rows() { return option(OPT_DEFORM_ENC_FFN_SLAB_ROWS); }   // rows of the FFN intermediate per slab, 0 = all
+inline int msda_layer_fused() { return option(OPT_MSDA_LAYER_FUSED); }   // 1 (default): query GEMM with the sampling epilogue + bf16 operator output; 0: round-1 composition
+inline int gemm_direct_store() { return option(OPT_GEMM_DIRECT_STORE); } // 0 through LDS, 1 direct, 2 automatic (default)
+inline int attn_variant() { return option(OPT_ATTN_VARIANT); }           // bit0 pipe, bit1 defer, bit2 prio, bit3 asm tr-reads, bit4 no padding trim, 32 = automatic (default)
+inline int gemm_tile_rb() { return option(OPT_GEMM_TILE_RB); }           // persistent GEMM tile order (gemm256p.hip): -1 automatic (default), 0 the dense XCD order, RB > 0 banded with RB row panels per band
+inline int gemm_variant_override() { return option(OPT_GEMM_VARIANT); }
+// gemm_skinny.hip: K = 256, N = 256 / 384 (the linears of a deformable-attention layer); option "gemm_skinny"
 bool gemm_skinny_takes(int epi, const GemmArgs &a);
 int gemm_skinny_launch(int epi, const GemmArgs &a, hipStream_t st);
-int gemm_skinny_enabled();
-int gemm_skinny_set(int v);
 struct Dcnv3Geo;
 bool dcnv3_bwd_mfma_takes(const Dcnv3Geo &q);   // msda_bwd_mfma.hip (template flag DCN): fp32, group channels 32
 int dcnv3_bwd_mfma_launch(const float *input, const float *offset, const float *mask, const float *grad_out, const Dcnv3Geo &q,
                           float offset_scale, float *grad_input, float *grad_offset, float *grad_mask, hipStream_t st);
-int dcnv3_bwd_tiled();       // VLLM_DCNV3_BWD_TILED / vllm_set_option("dcnv3_bwd_tiled")
-int dcnv3_bwd_tiled_set(int v);
-int gemm_half_tail();        // VLLM_GEMM_HALF_TAIL / vllm_set_option("gemm_half_tail"): half-height tiles in the persistent GEMM's last round
-int gemm_half_tail_set(int v);
-int gemm_res_ring();         // VLLM_GEMM_RES_RING / vllm_set_option("gemm_res_ring"): the persistent GEMM's residual (no LayerScale) through the operand ring
-int gemm_res_ring_set(int v);
 long gemm256p_half_launches();
-int msda_layer_value_bf16_set(int v);   // VLLM_MSDA_LAYER_VALUE_BF16 / vllm_set_option("msda_layer_value_bf16")
-int msda_layer_fused();        // VLLM_MSDA_LAYER_FUSED / vllm_set_option("msda_layer_fused")
-int msda_tiled_enabled();      // VLLM_MSDA_TILED / vllm_set_option("msda_tiled")
-int deform_enc_ffn_slab_rows();        // VLLM_DEFORM_ENC_FFN_SLAB_ROWS / vllm_set_option("deform_enc_ffn_slab_rows"): rows of the FFN intermediate per slab, 0 = all
-int deform_enc_ffn_slab_rows_set(int v);
 
 int gemm_bf16_launch(int epi, GemmArgs a, hipStream_t st);
 

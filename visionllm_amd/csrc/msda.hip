@@ -30,7 +30,6 @@
 namespace vllm {
 
 bool msda_tiled_ok(int D, int L, int P, int Lq, int S, int B, int M, const void *value, const void *out, const void *loc);
-int msda_tiled_enabled();   // runtime.cpp
 bool msda_pyramid_items_ok(int D, int L, int P, int Lq, int S, int B, int M);   // msda_tiled.hip
 int msda_tiled6_launch_bf16(const uint16_t *value, const int64_t *shapes, const int64_t *lsi, const float *loc,
                             const float *attw, int B, int S, int M, int L, int Lq, uint16_t *out, hipStream_t st);

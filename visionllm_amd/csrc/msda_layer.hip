@@ -122,13 +122,6 @@ __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float *__restric
 // msda_layer_fused = 0 (option / VLLM_MSDA_LAYER_FUSED): the round-1 composition (two query GEMMs + prep kernel + fp32
 // operator + conversion pass), kept as the A/B reference of the fused epilogue.
 inline bool layer_unfused() { return msda_layer_fused() == 0; }
-// VLLM_MSDA_LAYER_VALUE_BF16=0: keep the value in fp32 for every query set (A/B)
-static int g_layer_value_bf16 = -1;
-inline bool msda_layer_value_bf16()
-{
-    if (g_layer_value_bf16 < 0) { const char *e = getenv("VLLM_MSDA_LAYER_VALUE_BF16"); g_layer_value_bf16 = e && e[0] == '0' ? 0 : 1; }
-    return g_layer_value_bf16 != 0;
-}
 
 struct LayerWs {
     long value, off, logit, opout, opout_bf16, total;
@@ -181,7 +174,6 @@ int cvt_launch(const float *src, uint16_t *dst, long n, hipStream_t st, const in
 }
 
 }  // namespace
-int msda_layer_value_bf16_set(int v) { const int old = msda_layer_value_bf16() ? 1 : 0; g_layer_value_bf16 = v != 0; return old; }
 }  // namespace vllm
 
 using namespace vllm;

@@ -13,104 +13,72 @@ void set_error(const char *fmt, ...)
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-static int g_gemm_variant = -1, g_msda_tiled = -1, g_attn_variant = -1, g_gemm_direct = -1, g_layer_fused = -1;
-int g_dcnv3_tiled = -1;
-int dcnv3_tiled_enabled()
+
+// ---- runtime options: THE table.  One row per OptionId (kernels.hpp), in the enum's order; a new option is a row here, an id and an
+// inline getter there, and its description in include/vllm_hip.h.
+OptionValues g_options;
+namespace {
+struct Option {
+    const char *name, *env;   // vllm_set_option's name; the environment variable that gives the first value
+    int def;
+    enum Rule {
+        BOOL,        // stores v != 0
+        BOOL_ENV0,   // BOOL, but the environment switches it off by a text that begins with '0' and on by any other (no atoi)
+        RANGE,       // stores v where takes(v), the default for any other value on both routes
+        REJECT,      // stores v where takes(v); for any other value a set fails with `refusal` and changes nothing, the environment gives the default
+        MASK16,      // stores v & 0xffff
+    } rule;
+    bool (*takes)(int);    // RANGE, REJECT
+    const char *refusal;   // REJECT: the error text, printed with the value
+};
+const Option kOptions[OPT_COUNT] = {
+    {"msda_tiled", "VLLM_MSDA_TILED", 1, Option::REJECT, [](int v) { return v == 0 || v == 1 || v == 21; }, "msda_tiled must be one of 0, 1, 21 (got %d)"},
+    {"dcnv3_tiled", "VLLM_DCNV3_TILED", 1, Option::RANGE, [](int v) { return v >= 0 && v <= 4; }, nullptr},
+    {"dcnv3_bwd_tiled", "VLLM_DCNV3_BWD_TILED", 1, Option::BOOL, nullptr, nullptr},
+    {"gemm_half_tail", "VLLM_GEMM_HALF_TAIL", 1, Option::BOOL, nullptr, nullptr},
+    {"gemm_res_ring", "VLLM_GEMM_RES_RING", 1, Option::BOOL, nullptr, nullptr},
+    {"msda_layer_value_bf16", "VLLM_MSDA_LAYER_VALUE_BF16", 1, Option::BOOL_ENV0, nullptr, nullptr},
+    {"gemm_skinny", "VLLM_GEMM_SKINNY", 1, Option::BOOL, nullptr, nullptr},
+    {"deform_enc_ffn_slab_rows", "VLLM_DEFORM_ENC_FFN_SLAB_ROWS", 0, Option::REJECT, [](int v) { return v >= 0; }, "deform_enc_ffn_slab_rows must be >= 0 (got %d)"},
+    {"msda_layer_fused", "VLLM_MSDA_LAYER_FUSED", 1, Option::BOOL, nullptr, nullptr},
+    {"gemm_direct_store", "VLLM_GEMM_DIRECT_STORE", 2, Option::RANGE, [](int v) { return v >= 0 && v <= 2; }, nullptr},
+    {"attn_variant", "VLLM_ATTN_VARIANT", 32, Option::MASK16, nullptr, nullptr},
+    {"gemm_tile_rb", "VLLM_GEMM_TILE_RB", -1, Option::RANGE, [](int v) { return v >= -1 && v <= 32; }, nullptr},
+    {"gemm_variant", "VLLM_GEMM_VARIANT", 0, Option::REJECT, [](int v) { return v >= 0 && v <= 4 && v != 3; }, "gemm_variant must be 0, 1, 2 or 4"},
+};
+// *out = what `o` stores for `v`; false = it does not take v
+bool option_value(const Option &o, int v, int *out)
 {
-    if (g_dcnv3_tiled < 0) {   // 1 (default): LDS-tiled DCNv3 forward where it applies; 0: the gather kernel
-        const char *e = getenv("VLLM_DCNV3_TILED");
-        g_dcnv3_tiled = e ? atoi(e) : 1;
-        if (g_dcnv3_tiled < 0 || g_dcnv3_tiled > 4) g_dcnv3_tiled = 1;
-    }
-    return g_dcnv3_tiled;
+    *out = o.rule == Option::MASK16 ? v & 0xffff : o.takes ? v : v != 0;
+    return !o.takes || o.takes(v);
 }
-int msda_layer_fused()
+}  // namespace
+// the first get of an option: its value from the environment (read now, not at load), else the default
+int option_from_env(int id)
 {
-    if (g_layer_fused < 0) {   // 1 (default): query GEMM with the sampling epilogue + bf16 operator output; 0: round-1 composition
-        const char *e = getenv("VLLM_MSDA_LAYER_FUSED");
-        g_layer_fused = e ? (atoi(e) != 0) : 1;
-    }
-    return g_layer_fused;
-}
-int gemm_direct_store()
-{
-    if (g_gemm_direct < 0) {   // 0 through LDS, 1 direct, 2 automatic (default)
-        const char *e = getenv("VLLM_GEMM_DIRECT_STORE");
-        g_gemm_direct = e ? atoi(e) : 2;
-        if (g_gemm_direct < 0 || g_gemm_direct > 2) g_gemm_direct = 2;
-    }
-    return g_gemm_direct;
-}
-int attn_variant()
-{
-    if (g_attn_variant < 0) {
-        const char *e = getenv("VLLM_ATTN_VARIANT");
-        g_attn_variant = e ? (atoi(e) & 0xffff) : 32;
-    }
-    return g_attn_variant;
-}
-// persistent GEMM tile order (gemm256p.hip): -1 automatic (default), 0 the dense XCD order, RB > 0 banded with RB row panels per band
-int g_gemm_tile_rb = -2;
-int gemm_tile_rb()
-{
-    if (g_gemm_tile_rb == -2) {
-        const char *e = getenv("VLLM_GEMM_TILE_RB");
-        g_gemm_tile_rb = e ? atoi(e) : -1;
-        if (g_gemm_tile_rb < -1 || g_gemm_tile_rb > 32) g_gemm_tile_rb = -1;
-    }
-    return g_gemm_tile_rb;
-}
-int gemm_variant_override()
-{
-    if (g_gemm_variant < 0) {
-        const char *e = getenv("VLLM_GEMM_VARIANT");
-        g_gemm_variant = e ? atoi(e) : 0;
-        if (g_gemm_variant < 0 || g_gemm_variant > 4 || g_gemm_variant == 3) g_gemm_variant = 0;
-    }
-    return g_gemm_variant;
-}
-// "msda_tiled": 0 gather kernel, 1 automatic (default), 21 automatic with generation 9's phase clock
-static bool msda_tiled_valid(int v) { return v == 0 || v == 1 || v == 21; }
-int msda_tiled_enabled()
-{
-    if (g_msda_tiled < 0) {
-        const char *e = getenv("VLLM_MSDA_TILED");
-        g_msda_tiled = e && msda_tiled_valid(atoi(e)) ? atoi(e) : 1;
-    }
-    return g_msda_tiled;
+    const Option &o = kOptions[id];
+    const char *e = getenv(o.env);
+    int v = o.def;
+    if (e && o.rule == Option::BOOL_ENV0) v = e[0] != '0';
+    else if (e && !option_value(o, atoi(e), &v)) v = o.def;
+    return g_options.v[id] = v;
 }
 }  // namespace vllm
 
+// -> the previous effective value (which reads the environment if nothing has yet), or VLLM_EINVAL
 extern "C" int vllm_set_option(const char *name, int value)
 {
     if (!name) return VLLM_EINVAL;
-    if (!strcmp(name, "msda_tiled")) {
-        const int old = vllm::msda_tiled_enabled();
-        if (!vllm::msda_tiled_valid(value)) {
-            vllm::set_error("msda_tiled must be one of 0, 1, 21 (got %d)", value);
-            return VLLM_EINVAL;
+    for (int id = 0; id < vllm::OPT_COUNT; ++id) {
+        const vllm::Option &o = vllm::kOptions[id];
+        if (strcmp(name, o.name)) continue;
+        const int old = vllm::option(id);
+        int v;
+        if (!vllm::option_value(o, value, &v)) {
+            if (o.rule == vllm::Option::REJECT) { vllm::set_error(o.refusal, value); return VLLM_EINVAL; }
+            v = o.def;
         }
-        vllm::g_msda_tiled = value;
-        return old;
-    }
-    if (!strcmp(name, "dcnv3_tiled")) { const int old = vllm::dcnv3_tiled_enabled(); vllm::g_dcnv3_tiled = (value < 0 || value > 4) ? 1 : value; return old; }
-    if (!strcmp(name, "dcnv3_bwd_tiled")) return vllm::dcnv3_bwd_tiled_set(value);
-    if (!strcmp(name, "gemm_half_tail")) return vllm::gemm_half_tail_set(value);
-    if (!strcmp(name, "gemm_res_ring")) return vllm::gemm_res_ring_set(value);
-    if (!strcmp(name, "msda_layer_value_bf16")) return vllm::msda_layer_value_bf16_set(value);
-    if (!strcmp(name, "gemm_skinny")) return vllm::gemm_skinny_set(value);
-    if (!strcmp(name, "deform_enc_ffn_slab_rows")) {
-        if (value < 0) { vllm::set_error("deform_enc_ffn_slab_rows must be >= 0 (got %d)", value); return VLLM_EINVAL; }
-        return vllm::deform_enc_ffn_slab_rows_set(value);
-    }
-    if (!strcmp(name, "msda_layer_fused")) { const int old = vllm::msda_layer_fused(); vllm::g_layer_fused = value != 0; return old; }
-    if (!strcmp(name, "gemm_direct_store")) { const int old = vllm::gemm_direct_store(); vllm::g_gemm_direct = (value < 0 || value > 2) ? 2 : value; return old; }
-    if (!strcmp(name, "attn_variant")) { const int old = vllm::attn_variant(); vllm::g_attn_variant = value & 0xffff; return old; }
-    if (!strcmp(name, "gemm_tile_rb")) { const int old = vllm::gemm_tile_rb(); vllm::g_gemm_tile_rb = (value < -1 || value > 32) ? -1 : value; return old; }
-    if (!strcmp(name, "gemm_variant")) {
-        const int old = vllm::gemm_variant_override();
-        if (value < 0 || value > 4 || value == 3) { vllm::set_error("gemm_variant must be 0, 1, 2 or 4"); return VLLM_EINVAL; }
-        vllm::g_gemm_variant = value;
+        vllm::g_options.v[id] = v;
         return old;
     }
     vllm::set_error("unknown option %s", name);

@@ -167,9 +167,8 @@ class InternMLP(nn.Module):
         self.fc2 = nn.Linear(config.intermediate_size, config.hidden_size)
 
 
-_LAYER_PARAMS = ("norm1_w", "qkv_w", "qkv_b", "q_norm_w", "k_norm_w", "proj_w", "proj_b", "ls1", "norm2_w", "fc1_w", "fc1_b", "fc2_w",
-                 "fc2_b", "ls2")   # the order of VllmVitLayerTrain / VllmVitLayerGrads
-_SAVED = ("qkv", "ctx", "lse", "y1", "x1", "h1", "a1", "y2")   # VllmVitLayerSaved
+_LAYER_PARAMS = _lib.pointer_fields(_lib.VllmVitLayerGrads)   # the 14 of VllmVitLayerTrain too, in the same order
+_SAVED = _lib.pointer_fields(_lib.VllmVitLayerSaved)
 
 
 _TRAIN = LayerTrainABI("vit", _lib.VllmVitLayerTrain, _lib.VllmVitLayerSaved, _lib.VllmVitLayerGrads, _LAYER_PARAMS, _SAVED)
@@ -331,7 +330,6 @@ class InternVisionModel(nn.Module):
             return plan.desc
         for n_, p in self.named_parameters():
             _require_bf16_cuda(n_, p)
-        _lib.check_struct_layouts()
         emb = self.embeddings
         kpad = kpad_for(cfg.patch_size)
         pw = padded_patch_weight(emb.patch_embedding.weight, kpad)

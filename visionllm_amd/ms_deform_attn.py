@@ -407,7 +407,6 @@ class MSDeformAttnLayerFunction(Function):
         B, Lq, C = query.shape
         S = input_flatten.shape[1]
         L = _lib.lib()
-        _lib.check_struct_layouts()
         keep = []
         desc = _train_desc(meta, reference_points.shape[-1], C, params, keep)
         desc.geometry = known_geometry(spatial_shapes, Lq)

@@ -191,7 +191,7 @@ def _mask_stem(hidden_dim, embed_dim, kernel_size):
 _NATIVE_PARAMS = ("mask_embedding.0.weight", "mask_embedding.0.bias", "mask_embedding.1.weight", "mask_embedding.1.bias",
                   "mask_embedding.3.weight", "mask_embedding.3.bias", "mask_embedding.4.weight", "mask_embedding.4.bias",
                   "mask_embedding.6.weight", "mask_embedding.6.bias", "up_dim.weight", "up_dim.bias")   # (_lib.REGION_PARAMS' order)
-_NATIVE_SAVED = ("a1", "y1", "pre1", "g1", "y2", "pre2", "g2", "stem", "pooled")
+_NATIVE_SAVED = _lib.pointer_fields(_lib.VllmRegionEncoderSaved)
 _MAX_LEVELS = 4
 
 

@@ -117,7 +117,6 @@ def _embed_forward(pix, w, b, cls, pos):
     if pix.dim() != 4 or pix.shape[1] != 3 or pix.shape[2] != d.image or pix.shape[3] != d.image:
         raise ValueError(f"pixel_values must be [n, 3, {d.image}, {d.image}], got {tuple(pix.shape)}")
     L = _lib.lib()
-    _lib.check_struct_layouts()
     n, dev = pix.shape[0], pix.device
     out = torch.empty((n, S, d.hidden), dtype=torch.bfloat16, device=dev)
     with torch.cuda.device(dev):
@@ -196,7 +195,6 @@ class LayerTrainABI:
         """The training forward on x [B, S, C] (16-byte aligned) -> (out, the saved tensors in ``self.saved`` order)."""
         keep = []
         d = self.desc(scalars, params, keep)
-        _lib.check_struct_layouts()
         B, S, C = x.shape
         M, dev = B * S, x.device
         shapes = {"qkv": (M, 3 * C), "lse": (B, scalars["heads"], S), "h1": (M, scalars["inter"]), "a1": (M, scalars["inter"])}   # others: [M, C]
