@@ -567,6 +567,81 @@ int vllm_query_select_tail_f32(const uint16_t *h, int ldh, const uint16_t *W, co
                                vllm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * f2f. The FUSION LAYER of Grounding-DINO (bi-directional image <-> text attention) in front of every deformable encoder layer, bf16
+ * modules (inference).
+ *
+ * Replaces the bodies of
+ *   GroundingDinoBiMultiHeadAttention.forward, GroundingDinoFusionLayer.forward
+ *       visionllmv2/model/grounding_dino/modeling_ov_grounding_dino_mask_dn.py:860-1101
+ * with dropout and drop-path the identity and without the two [B, H, ., .] attention-weight tensors, which are never built.  The launches:
+ *   1. v = LN_vision(vision), t = LN_text(text)                                                              (vllm_layernorm_bf16)
+ *   2. vision_proj(v), values_vision_proj(v), text_proj(t), values_text_proj(t)                   (vllm_gemm_bf16, VLLM_EPI_BIAS)
+ *   3. text -> image attention: q = text_proj(t), k = vision_proj(v), v = values_vision_proj(v), key mask = vision_padding_mask, keys
+ *      split by vllm_xattn_plan
+ *   4. image -> text attention: q = vision_proj(v), k = text_proj(t), v = values_text_proj(t), key mask = text_padding_mask, one split.
+ *      (It runs behind 3 so that its output can take the memory of values_vision_proj(v), which 3 has read; the two do not depend
+ *      on each other.)
+ *   5. out_vision = v + vision_param * out_vision_proj(.), out_text = t + text_param * out_text_proj(.)   (VLLM_EPI_RESIDUAL with scale)
+ * softmax_scale = (embed_dim / n_heads)^-0.5 multiplies the fp32 scores.  No weight is copied or repacked.  Every tensor between two
+ * launches is bf16, as in the bf16 module; scores, softmax and sums are fp32, each stored tensor is rounded once.
+ * STATED DEPARTURES.  The call computes the EXACT masked softmax of both directions.  The reference subtracts the global maximum of all
+ * scores of the call, clamps to +-50000, subtracts (text side) the column maximum taken over ALL image tokens, padded ones included,
+ * and clamps again.  Softmax is shift-invariant, so: the second clamp never changes a result (exp(-50000) = 0 in every format); the
+ * first clamp changes one only where the scores of one call span more than about 49 900; the padded-token maximum changes one only
+ * where a padded token's score exceeds every unpadded one of its column by more than the exp underflow distance, where the reference
+ * gives 0 / 0.  In those two extreme cases the results differ from the reference's.
+ * d_model a multiple of 64 in 64 .. 512; embed_dim / n_heads 128 or 256; B S embed_dim 2 < 2^31; 1 <= Lt.  No runtime option.
+ * ------------------------------------------------------------------------------------------------ */
+/* A TAGGED struct, without a typedef name: C callers write `struct VllmFusionLayerDesc`.  (The set of typedef'd descriptors of this ABI
+ * version is closed and pinned by the boundary tests; the binding reads this form with the same member rules, _lib.parse_tagged_structs.) */
+struct VllmFusionLayerDesc {
+    int32_t d_model, embed_dim, n_heads;
+    float   vision_norm_eps, text_norm_eps;
+    const uint16_t *vision_norm_w, *vision_norm_b, *text_norm_w, *text_norm_b;                           /* [C] each  (device, bf16) */
+    const uint16_t *vision_proj_w, *vision_proj_b, *text_proj_w, *text_proj_b;                           /* [E, C] [E] */
+    const uint16_t *values_vision_proj_w, *values_vision_proj_b, *values_text_proj_w, *values_text_proj_b;
+    const uint16_t *out_vision_proj_w, *out_vision_proj_b, *out_text_proj_w, *out_text_proj_b;           /* [C, E] [C] */
+    const uint16_t *vision_param, *text_param;                                                           /* [C] */
+};
+unsigned long vllm_fusion_layer_desc_sizeof(void);
+/* Bytes of device scratch vllm_fusion_layer_forward needs; host-only; 0 for B S == 0, negative for a refused descriptor or sizes. */
+long vllm_fusion_layer_workspace_bytes(const struct VllmFusionLayerDesc *desc, int B, int S, int Lt);
+long vllm_fusion_layer_calls(void);   /* calls of vllm_fusion_layer_forward in this process that reached their launches (tests) */
+/* vision, out_vision [B, S, C] bf16; text, out_text [B, Lt, C] bf16; vision_padding_mask [B, S] / text_padding_mask [B, Lt] uint8
+ * (non-zero = padded: the key is ignored) or NULL.  A row whose keys are all masked is NaN, as in the module.  One stream, no
+ * allocation, no synchronisation.  A refused call (descriptor; sizes outside the contract; NULL or misaligned operand; out_vision /
+ * out_text overlapping an input or each other; NULL, misaligned or short workspace: VLLM_EINVAL, reason in vllm_last_error()) has
+ * enqueued nothing; B S == 0 returns VLLM_OK. */
+/* Alignment: vision, text, out_vision, out_text, every weight / bias / parameter of the descriptor and workspace 16 bytes; the masks:
+ * element alignment. */
+int vllm_fusion_layer_forward(const struct VllmFusionLayerDesc *desc, const uint16_t *vision, const uint16_t *text,
+                              const uint8_t *vision_padding_mask, const uint8_t *text_padding_mask, int B, int S, int Lt,
+                              uint16_t *out_vision, uint16_t *out_text, void *workspace, long workspace_bytes, vllm_stream_t stream);
+/* The attention kernel of steps 3 and 4, exposed for the parity tests: masked cross attention for head dims 128 / 256.
+ * Head h of token (b, i) of an operand is D contiguous bf16 at ptr + b * batch_stride + i * ld + h * D (strides in elements), so q, k
+ * and v are read in place from projection outputs.  D 128 or 256; Lq, Lk >= 1, neither bounded by a tile; H >= 1.
+ *   out[b, i, h, :] = softmax_j(softmax_scale * q . k_j, masked keys at -inf) V
+ * key_padding_mask [B, Lk] (non-zero = ignore this key) or NULL.  Scores, softmax and accumulation fp32, P rounded to bf16 before P V,
+ * one rounding of the result.  A row with EVERY key masked is NaN in all D outputs of that head.  Nothing is written outside the H D
+ * columns of an output row.
+ * vllm_xattn_plan: a pure function of its five arguments, never of the device: `splits` workgroups share the keys of one block of 64
+ * query rows, split s taking keys [s keys_per_split, min(Lk, (s + 1) keys_per_split)); keys_per_split is a multiple of the key tile
+ * (64).  splits is 1 up to 512 keys and wherever B H ceil(Lq / 64) reaches 512 workgroups; otherwise ceil(512 / (B H ceil(Lq / 64)))
+ * splits of at least four key tiles each.  With splits > 1 every split writes the fp32 (m, l, O) of its rows to `workspace`
+ * (vllm_xattn_workspace_bytes: B H Lq splits (D + 2) 4 bytes; 0 for one split, negative for refused sizes) and a second kernel combines
+ * them in ascending order; a split whose keys are all masked has m = -inf, l = 0 and takes weight 0.  No atomics: the same bits on
+ * every run and every box.  A refused call (D; a NULL operand; a misaligned pointer or stride; a row stride below H D; a NULL,
+ * misaligned or short workspace where the plan splits: VLLM_EINVAL, each with its own reason in vllm_last_error()) has enqueued nothing;
+ * B Lq == 0 returns VLLM_OK. */
+/* Alignment: q, k, v, out, workspace 16 bytes, the row and batch strides multiples of 8 elements; the mask: element alignment. */
+int vllm_xattn_fwd_bf16(const uint16_t *q, long q_batch_stride, int ldq, const uint16_t *k, long k_batch_stride, int ldk,
+                        const uint16_t *v, long v_batch_stride, int ldv, uint16_t *out, long o_batch_stride, int ldo,
+                        const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D, float softmax_scale, void *workspace,
+                        long workspace_bytes, vllm_stream_t stream);
+long vllm_xattn_workspace_bytes(int B, int Lq, int Lk, int H, int D);
+int vllm_xattn_plan(int B, int Lq, int Lk, int H, int D, int *splits, int *keys_per_split);
+
+/* ------------------------------------------------------------------------------------------------
  * f3b. The whole DCNv3 layer, bf16 modules (inference).
  *
  * Replaces the body of DCNv3.forward, visionllmv2/model/ops_dcnv3/modules/dcnv3.py:313-351, with the CenterFeatureScaleModule

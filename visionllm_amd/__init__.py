@@ -15,6 +15,9 @@ Host-side mirror of the reference's operator/module interfaces for that path onl
 * ``query_selection`` -- ``GroundingDinoQuerySelection``: the two-stage query selection between that encoder and that decoder
   (``gen_encoder_output_proposals``, the contrastive class head, the top-k and the gathers) with the one-call native forward; also an
   attribute of this package.
+* ``fusion_layer`` -- ``GroundingDinoFusionLayer`` (with ``GroundingDinoBiMultiHeadAttention`` and ``GroundingDinoDropPath``): the
+  bi-directional image <-> text attention in front of every Grounding-DINO encoder layer, with the one-call native forward; the three
+  names are also attributes of this package.
 
 All compute goes through ``libvllm_hip.so`` (hand-written HIP, C ABI in ``include/vllm_hip.h``).  There is NO
 CPU fallback: calling an op without the built extension, or with CPU tensors, raises.
@@ -26,7 +29,8 @@ __version__ = "0.1.0"
 _ENCODER_EXPORTS = ("DeformableTransformerEncoderLayer", "GroundingDinoDeformableLayer", "encoder_layers_forward")
 _DECODER_EXPORTS = ("DeformableTransformerDecoderLayer", "GroundingDinoDecoderLayer", "GroundingDinoDecoder", "GroundingDinoMLPPredictionHead")
 _SELECTION_EXPORTS = ("GroundingDinoQuerySelection",)
-__all__ = ["build", "lib", "lib_path", *_ENCODER_EXPORTS, *_DECODER_EXPORTS, *_SELECTION_EXPORTS]
+_FUSION_EXPORTS = ("GroundingDinoFusionLayer", "GroundingDinoBiMultiHeadAttention", "GroundingDinoDropPath")
+__all__ = ["build", "lib", "lib_path", *_ENCODER_EXPORTS, *_DECODER_EXPORTS, *_SELECTION_EXPORTS, *_FUSION_EXPORTS]
 
 
 def __getattr__(name):
@@ -40,4 +44,7 @@ def __getattr__(name):
     if name in _SELECTION_EXPORTS:
         from . import query_selection
         return getattr(query_selection, name)
+    if name in _FUSION_EXPORTS:
+        from . import fusion_layer
+        return getattr(fusion_layer, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -64,26 +64,42 @@ _MEMBER_CTYPES = {
 }
 
 
+def _strip_comments(path):
+    src = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    return re.sub(r"//[^\n]*", " ", src)
+
+
+def _struct_class(path, name, body, structs):
+    """the ctypes class of one struct body; ``structs``: the classes a member may name"""
+    fields = []
+    for decl in filter(None, (d.strip() for d in body.split(";"))):
+        head = re.match(r"(?:const\s+)?(\w+)\b(.*)", decl, flags=re.S)
+        base = head and (structs.get(head.group(1)) or _MEMBER_CTYPES.get(head.group(1)))
+        members = [re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*", d) for d in head.group(2).split(",")] if base else [None]
+        if not all(members):
+            raise ValueError(f"{path}: struct {name}: cannot read the member declaration {decl!r}")
+        for star, member, count in (dm.groups() for dm in members):
+            t = base if not star else ctypes.POINTER(base) if issubclass(base, ctypes.Structure) else ctypes.c_void_p
+            fields.append((member, t * int(count) if count else t))
+    return type(name, (ctypes.Structure,), {"_fields_": fields})
+
+
 def parse_structs(path: str = HEADER):
     """-> {name: ctypes.Structure subclass} for every ``typedef struct ... { ... } Name;`` of the header, in declaration order.  A
     pointer member is c_void_p, a pointer to an earlier struct POINTER(that class), a struct by value that class, ``[N]`` an array.
     A declaration that is none of these raises: a member left out would shift every member behind it."""
-    src = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
-    src = re.sub(r"//[^\n]*", " ", src)
     structs = {}
-    for m in re.finditer(r"typedef\s+struct\s+\w*\s*\{(.*?)\}\s*(\w+)\s*;", src, flags=re.S):
-        name, fields = m.group(2), []
-        for decl in filter(None, (d.strip() for d in m.group(1).split(";"))):
-            head = re.match(r"(?:const\s+)?(\w+)\b(.*)", decl, flags=re.S)
-            base = head and (structs.get(head.group(1)) or _MEMBER_CTYPES.get(head.group(1)))
-            members = [re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*", d) for d in head.group(2).split(",")] if base else [None]
-            if not all(members):
-                raise ValueError(f"{path}: struct {name}: cannot read the member declaration {decl!r}")
-            for star, member, count in (dm.groups() for dm in members):
-                t = base if not star else ctypes.POINTER(base) if issubclass(base, ctypes.Structure) else ctypes.c_void_p
-                fields.append((member, t * int(count) if count else t))
-        structs[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+    for m in re.finditer(r"typedef\s+struct\s+\w*\s*\{(.*?)\}\s*(\w+)\s*;", _strip_comments(path), flags=re.S):
+        structs[m.group(2)] = _struct_class(path, m.group(2), m.group(1), structs)
     return structs
+
+
+def parse_tagged_structs(path: str = HEADER):
+    """-> {tag: ctypes.Structure subclass} for every ``struct Tag { ... };`` of the header that has no typedef name (C callers write
+    ``struct Tag``), under the member rules of parse_structs; a member may name a typedef'd struct."""
+    known = parse_structs(path)
+    return {m.group(1): _struct_class(path, m.group(1), m.group(2), known)
+            for m in re.finditer(r"^struct\s+(\w+)\s*\{(.*?)\}\s*;", _strip_comments(path), flags=re.S | re.M)}
 
 
 def header_abi_version(path: str = HEADER) -> int:
@@ -159,6 +175,8 @@ def current_stream(device=None):
 # ---- the descriptor structs of include/vllm_hip.h as ctypes classes: _lib.VllmVitDesc, ... (generated, never written by hand) ----
 STRUCTS = parse_structs()
 globals().update(STRUCTS)
+TAGGED_STRUCTS = parse_tagged_structs()          # struct VllmFusionLayerDesc
+globals().update(TAGGED_STRUCTS)
 
 
 def pointer_fields(struct):
@@ -174,9 +192,11 @@ def _check_struct_layouts(L, protos):
     """Every struct against the library's own sizeof: ``VllmFooBar`` against ``vllm_foo_bar_sizeof()``.  One without such an export
     has to lie by value inside one that has it."""
     checked = []
-    for name, cls in STRUCTS.items():
+    for name, cls in {**STRUCTS, **TAGGED_STRUCTS}.items():
         fn = "vllm_" + re.sub(r"(?<!^)(?=[A-Z])", "_", name[len("Vllm"):]).lower() + "_sizeof"
         if fn not in protos:
+            if name in TAGGED_STRUCTS:
+                raise RuntimeError(f"include/vllm_hip.h: no {fn}() for struct {name}")
             continue
         if ctypes.sizeof(cls) != getattr(L, fn)():
             raise RuntimeError(f"{name}: {ctypes.sizeof(cls)} bytes as parsed from include/vllm_hip.h, {getattr(L, fn)()} in libvllm_hip.so: "
