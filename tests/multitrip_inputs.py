@@ -6,7 +6,8 @@ against the device they run on before they launch.
 
   walker                       a "trip"                                             restated from
   norm.hip backward kernels    one row of a virtual block's range of `rpb` rows     rb_plan (norm.hip)
-  add_layernorm, box_refine    one row group of a wave (2 rows at C <= 256, else 1)  add_layernorm_launch / box_refine_launch
+  add_layernorm, box_refine,   one row group of a wave (2 rows at C <= 256, else 1)  row_group_plan (row_groups.hpp)
+  qs_tail
   refpoint_embed, add_bf16     one 16-byte chunk (or element) of a thread           refpoint_embed_launch / add_launch
   f32 <-> bf16 conversions     one vector / element / chunk of a thread             cvt_launch, stream_grid (msda_layer*.hip)
   row movers, segment sum      one row (or row slab) of a wave                      grid_for (embed.hip)
@@ -104,9 +105,10 @@ def colsum_chain(rows, nbv):
     return ceil_div(rows, nbv) + ceil_div(nbv, 8) + 8
 
 
-# ---- add_layernorm_kernel / box_refine_kernel: row groups over waves -----------------------------------------------------------------
+# ---- add_layernorm_kernel / box_refine_kernel / qs_tail_kernel: row groups over waves ------------------------------------------------
 def group_plan(rows, C, cus):
-    """add_layernorm_launch / box_refine_launch -> dict(G, rows_per_group, ngroups, nwaves)"""
+    """row_group_plan(rows, C) of csrc/row_groups.hpp, the one launch geometry of the four row-group kernels (the workgroups it returns
+    times the four waves of ROWG_THREADS) -> dict(G, rows_per_group, ngroups, nwaves)"""
     G = 32 if C <= 256 else 64
     rpg = 64 // G
     ngroups = ceil_div(rows, rpg)

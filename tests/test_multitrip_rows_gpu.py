@@ -11,6 +11,8 @@ and bounds of the kernel-alone tests, imported from their modules:
                               |err| <= 1 bf16 ulp + 2^-17 mag, for the row gradient AND the column sums (see ``judge_sums``)
   add_layernorm               1 bf16 ulp + 2^-20 (|n w| + |b|)                          (test_add_layernorm_against_fp64)
   box_refine                  1/4 * 2^-17 (sum|h w| + |b| + |logit|) + 2^-22            (test_refine_kernel_against_fp64)
+  qs_tail                     2^-17 (sum|h w| + |b|) + 2^-22 / (p (1 - p)) + 2^-20, a quarter of it + 2^-22 for the reference points
+                                                                                        (test_tail_kernel_against_fp64)
   refpoint_embed              1 bf16 ulp + 2^-19, the fp32 product bit-exact            (test_refpoint_kernel_against_fp64)
   segment sum                 1 bf16 ulp + (n - 1) 2^-23 sum|terms|                     (test_token_loops_train_gpu)
   add, conversions, movers    bit-exact
@@ -22,6 +24,8 @@ import torch
 
 import clip_layer_train_inputs as CI
 import multitrip_inputs as M
+import query_selection_inputs as QI
+import test_query_selection_gpu as QT
 import vit_layer_train_inputs as VI
 from bounds import DEV, P, bf16_ulp, excess_ulp, stream
 from visionllm_amd import _lib
@@ -426,6 +430,71 @@ def test_box_refine_past_one_row_group_per_wave(C):
     run(alias, alias)
     assert torch.equal(bits(alias), bits(got)), "the in-place form differs"
     assert torch.equal(bits(run(ref, torch.full_like(ref, NAN))), bits(got)), "two runs differ"
+
+
+# ---- qs_tail_kernel ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("C", M.REFINE_C)
+def test_query_select_tail_past_one_row_group_per_wave(C):
+    """box_refine's row count (every wave walks 3 row groups, five of them a fourth, the last group ragged) as k * B selected rows over
+    the two-level threshold geometry of test_tail_kernel_against_fp64: every trip meets padded rows, invalid proposals and finite ones,
+    since the indices are drawn from all of S.  That test's bound, unchanged."""
+    rows = M.group_rows(C, cus())
+    plan = M.group_plan(rows, C, cus())
+    trips = M.ceil_div(plan["ngroups"], plan["nwaves"])
+    assert trips >= M.MIN_TRIPS and M.group_ok(rows, C, cus()), f"not a multi-trip shape on {cus()} compute units: {rows} rows, {plan}"
+    maps, two = QT.threshold_geometry()
+    B = next(n for n in (3, 5, 7, 1) if rows % n == 0)
+    k = rows // B
+    real = torch.stack([two[(i + 1) % 2] for i in range(B)])          # image 0 is the padded one
+    S = real.shape[1]
+    g = torch.Generator().manual_seed(C)
+    idx = torch.randint(0, S, (B, k), generator=g)
+    _, h = view(rows, C, 16, 8)
+    h.relu_()
+    W, b = bf(0.1 * torch.randn(4, C, device=DEV)), bf(0.1 * torch.randn(4, device=DEV))
+    pmask = (~real).to(torch.uint8).to(DEV)
+    shapes = torch.tensor(maps, dtype=torch.int64, device=DEV)
+    hw = shapes[:, 0] * shapes[:, 1]
+    lsi = torch.cumsum(hw, 0) - hw
+    idx_dev = idx.to(DEV)
+    what = f"tail rows {rows} = {B} x {k} C {C} trips {trips}"
+
+    def run():
+        ext = torch.full((B, len(maps), 2), -7, dtype=torch.int32, device=DEV)
+        coords = torch.full((rows, 4), NAN, dtype=torch.float32, device=DEV)
+        ref = torch.full((rows, 4), NAN, dtype=torch.float32, device=DEV)
+        valid = torch.full((rows,), 9, dtype=torch.uint8, device=DEV)
+        _lib.check(_lib.lib().vllm_query_select_tail_f32(P(h), h.stride(0), P(W), P(b), P(idx_dev), P(pmask), P(shapes), P(lsi), B, S, len(maps), k,
+                                                         C, P(ext), P(coords), P(ref), P(valid), stream()), "vllm_query_select_tail_f32")
+        torch.cuda.synchronize()
+        return ext, coords, ref, valid
+    ext, coords, ref, valid = run()
+    flags = QT.torch_valid_flags(~real.to(DEV), maps).cpu()
+    assert torch.equal(valid.cpu().bool().view(B, k), torch.gather(flags, 1, idx)), f"{what}: validity flags differ from torch's fp32 statements"
+    logit, _ = QI.closed_form_proposals(real, maps)
+    logit = torch.gather(logit, 1, idx[..., None].expand(-1, -1, 4)).view(rows, 4).to(DEV)
+    filled = torch.gather(~flags | ~real, 1, idx).view(rows).to(DEV)
+    rows_per_trip = plan["nwaves"] * plan["rows_per_group"]
+    for t in range(trips):
+        f = filled[t * rows_per_trip:(t + 1) * rows_per_trip]
+        assert f.any() and (~f).any(), f"{what}: trip {t} lacks filled or finite rows"
+    assert torch.equal(torch.isinf(coords), filled[:, None].expand(-1, 4)) and (coords[filled] > 0).all(), f"{what}: +inf exactly at filled rows"
+    assert (ref[filled] == 1.0).all(), f"{what}: sigmoid(+inf) is 1.0"
+    W64, b64 = W.double(), b.double()
+    worst = worst_ref = 0.0
+    for a, e in M.ref_slices(rows, C):
+        fin = ~filled[a:e]
+        h64 = h[a:e].double()
+        z = (h64 @ W64.T + b64)[fin] + logit[a:e][fin]
+        p = torch.sigmoid(logit[a:e][fin])
+        bound = 2.0 ** -17 * (h64.abs() @ W64.abs().T + b64.abs())[fin] + 2.0 ** -22 / (p * (1 - p)) + 2.0 ** -20
+        assert torch.isfinite(coords[a:e][fin]).all(), what
+        worst = max(worst, ((coords[a:e][fin].double() - z).abs() / bound).max().item())
+        worst_ref = max(worst_ref, ((ref[a:e][fin].double() - torch.sigmoid(z)).abs() / (0.25 * bound + 2.0 ** -22)).max().item())
+    print(f"{what}: coords max err / bound {worst:.3f}; reference points err / bound {worst_ref:.3f}")
+    assert worst <= 1.0 and worst_ref <= 1.0, what
+    for x, y in zip(run(), (ext, coords, ref, valid)):
+        assert torch.equal(QT.bits(x), QT.bits(y)), f"{what}: two runs differ"
 
 
 # ---- refpoint_embed_kernel -----------------------------------------------------------------------------------------------------------

@@ -6,8 +6,6 @@
 
 namespace vllm {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
 constexpr int ATT_THREADS = 256;

@@ -13,6 +13,7 @@
 #include "orchestrate.hpp"
 #include "deform_decoder_layer.hpp"
 #include "deform_blocks.hpp"
+#include "row_groups.hpp"
 
 namespace vllm {
 namespace {
@@ -53,62 +54,41 @@ __global__ __launch_bounds__(256) void refpoint_embed_kernel(const float *__rest
     }
 }
 
-// new_ref[r, k] = sigmoid(h[r, :] . W[k, :] + b[k] + inverse_sigmoid(ref[r, k])), fp32.  The rows of add_layernorm_kernel
-// (deform_encoder_layer.hip): G lanes share a row, lane j owns the 16-byte chunk j of it and keeps its 4 x 8 slice of W in registers; a
-// wave walks its rows with a grid stride and asks for the next rows' h and ref before it reduces the current ones.  The four sums go
-// through one fixed xor tree; lane k < 4 of the group finishes component k.  A lane reads the element of `ref` it writes and no other,
-// and a row is read only by the wave that writes it: new_ref may be ref.
-constexpr int BR_THREADS = 256;
+// new_ref[r, k] = sigmoid(h[r, :] . W[k, :] + b[k] + inverse_sigmoid(ref[r, k])), fp32.  Row groups (row_groups.hpp): a lane keeps its
+// 4 x 8 slice of W in registers; a wave asks for the next rows' h and ref before it reduces the current ones.  The four sums go through
+// one fixed xor tree; lane k < 4 of the group finishes component k.  A lane reads the element of `ref` it writes and no other, and a row
+// is read only by the wave that writes it: new_ref may be ref.
 struct BrRow { uint4_t x; float r; };
 
 template <int G>
-__global__ __launch_bounds__(BR_THREADS) void box_refine_kernel(const uint16_t *__restrict__ h, int ldh, const uint16_t *__restrict__ W,
+__global__ __launch_bounds__(ROWG_THREADS) void box_refine_kernel(const uint16_t *__restrict__ h, int ldh, const uint16_t *__restrict__ W,
                                                                 const uint16_t *__restrict__ bias, const float *ref, float *new_ref, long rows,
                                                                 int C, float eps)
 {
-    constexpr int RW = 64 / G;
-    const int lane = threadIdx.x & 63, j = lane % G, sub = lane / G;
-    const long nwaves = (long)gridDim.x * (BR_THREADS / 64), wave0 = (long)blockIdx.x * (BR_THREADS / 64) + (threadIdx.x >> 6);
-    const long ngroups = (rows + RW - 1) / RW;
-    const bool act = j < (C >> 3), fin = j < 4;
-    const int c0 = j * 8;
+    const RowLanes<G> ln(rows, C);
+    const int j = ln.j;
+    const bool fin = j < 4;
+    const long nwaves = ln.nwaves;
     float w[4][8];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        uint4_t wv = {0u, 0u, 0u, 0u};
-        if (act) wv = *reinterpret_cast<const uint4_t *>(W + (long)k * C + c0);
-        unpack8(wv, w[k]);
-    }
-    const float bk = fin ? bf16_to_f32(bias[j]) : 0.f;
+    const float bk = load_dot4<G>(W, bias, C, ln, w);
     auto load = [&](long g) {
         BrRow t = {{0u, 0u, 0u, 0u}, 0.5f};
-        const long row = g * RW + sub;
+        const long row = ln.row(g);
         if (row < rows) {
-            if (act) t.x = *reinterpret_cast<const uint4_t *>(h + row * ldh + c0);
+            if (ln.act) t.x = *reinterpret_cast<const uint4_t *>(h + row * ldh + ln.c0);
             if (fin) t.r = ref[row * 4 + j];
         }
         return t;
     };
-    long g = wave0;
+    long g = ln.wave0;
     BrRow cur = load(g);   // (g >= ngroups: row >= rows, nothing is read)
-    for (; g < ngroups; g += nwaves) {
+    for (; g < ln.ngroups; g += nwaves) {
         const BrRow nxt = load(g + nwaves);
-        const long row = g * RW + sub;
-        float v[8], s[4];
-        unpack8(cur.x, v);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            s[k] = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s[k] = fmaf(v[e], w[k][e], s[k]);
-        }
-#pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) s[k] += __shfl_xor(s[k], o);
-        }
+        const long row = ln.row(g);
+        float s[4];
+        dot4_rows<G>(cur.x, w, s);
         if (fin && row < rows) {
-            const float dot = j == 0 ? s[0] : j == 1 ? s[1] : j == 2 ? s[2] : s[3];
+            const float dot = dot4_pick(s, j);
             float x = cur.r;
             x = x < 0.f ? 0.f : x > 1.f ? 1.f : x;          // comparisons: a NaN stays a NaN, as in torch.clamp
             const float x1 = x < eps ? eps : x, om = 1.f - x, x2 = om < eps ? eps : om;
@@ -131,12 +111,7 @@ int refpoint_embed_launch(const float *ref, const float *vr, const float *dim_t,
 int box_refine_launch(const uint16_t *h, int ldh, const uint16_t *W, const uint16_t *b, const float *ref, float *new_ref, long rows, int C,
                       float eps, hipStream_t st)
 {
-    const int G = C <= 256 ? 32 : 64;
-    const long ngroups = (rows + 64 / G - 1) / (64 / G), want = (ngroups + 3) / 4, cap = (long)device_cus() * 8;
-    const dim3 grid((unsigned)(want < cap ? want : cap));
-    if (G == 32) VLLM_LAUNCH((box_refine_kernel<32>), grid, dim3(BR_THREADS), 0, st, h, ldh, W, b, ref, new_ref, rows, C, eps);
-    else VLLM_LAUNCH((box_refine_kernel<64>), grid, dim3(BR_THREADS), 0, st, h, ldh, W, b, ref, new_ref, rows, C, eps);
-    VLLM_CHECK_LAUNCH("box_refine_kernel");
+    VLLM_LAUNCH_ROW_GROUPS(box_refine_kernel, rows, C, st, h, ldh, W, b, ref, new_ref, rows, C, eps);
     return VLLM_OK;
 }
 

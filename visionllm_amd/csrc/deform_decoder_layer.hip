@@ -20,6 +20,7 @@
 #include "msda_layer.hpp"
 #include "deform_blocks.hpp"
 #include "deform_decoder_layer.hpp"
+#include "mha_core.hpp"
 
 namespace vllm {
 namespace {
@@ -95,16 +96,23 @@ struct DecCall {
     uint16_t *xp, *bufa, *bufb, *qk, *vb, *ctx, *tkv, *h;
     char *attn;
     int H, D;
+    AttnOperand sa_q, sa_k, sa_v;   // self-attention: q | k interleaved in qk [R, 2C], v in vb
+    AttnOperand ta_q, ta_k, ta_v;   // text attention: q in vb, k | v interleaved in tkv [B Lt, 2C]
+    AttnOperand ctx_o;              // both write ctx [R, C]
 };
-static DecCall dec_call(const VllmDeformDecLayerDesc *d, const DecWs &w, void *workspace)
+static DecCall dec_call(const VllmDeformDecLayerDesc *d, const DecWs &w, void *workspace, long Lq, long Lt)
 {
     char *ws = (char *)workspace;
+    const int C = d->cross_attn.d_model;
     DecCall c;
     c.xp = (uint16_t *)(ws + w.xp); c.bufa = (uint16_t *)(ws + w.a); c.bufb = (uint16_t *)(ws + w.b); c.qk = (uint16_t *)(ws + w.qk);
     c.vb = (uint16_t *)(ws + w.v); c.ctx = (uint16_t *)(ws + w.ctx); c.tkv = (uint16_t *)(ws + w.tkv); c.h = (uint16_t *)(ws + w.h);
     c.attn = ws + w.attn;
     c.H = d->n_heads_sa;
-    c.D = d->has_self_attn || d->has_text_attn ? d->cross_attn.d_model / c.H : 32;
+    c.D = d->has_self_attn || d->has_text_attn ? C / c.H : 32;
+    c.sa_q = {c.qk, Lq * 2 * C, 2 * C}; c.sa_k = {c.qk + C, Lq * 2 * C, 2 * C}; c.sa_v = {c.vb, Lq * C, C};
+    c.ta_q = {c.vb, Lq * C, C}; c.ta_k = {c.tkv, Lt * 2 * C, 2 * C}; c.ta_v = {c.tkv + C, Lt * 2 * C, 2 * C};
+    c.ctx_o = {c.ctx, Lq * C, C};
     return c;
 }
 
@@ -134,12 +142,10 @@ int dec_layer_check_call(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, c
     const DecWs w = dec_ws(d, B, Lq, Lt, S);
     VLLM_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= w.total,
                  "deform_dec_layer: workspace too small (%ld < %ld bytes) or misaligned", workspace_bytes, w.total);
-    const DecCall c = dec_call(d, w, const_cast<void *>(workspace));
-    const uint16_t *qk = c.qk, *vb = c.vb, *ctx = c.ctx, *tkv = c.tkv;
-    const int H = c.H, D = c.D;
+    const DecCall c = dec_call(d, w, const_cast<void *>(workspace), Lq, Lt);
     // the attention kernel's own gate, asked before anything is enqueued (dense slices of the buffers above: it cannot refuse them)
-    if (sa) TRY(mha_fwd_check(qk, (long)Lq * 2 * C, 2 * C, qk + C, (long)Lq * 2 * C, 2 * C, vb, (long)Lq * C, C, ctx, (long)Lq * C, C, B, Lq, Lq, H, D));
-    if (ta) TRY(mha_fwd_check(vb, (long)Lq * C, C, tkv, (long)Lt * 2 * C, 2 * C, tkv + C, (long)Lt * 2 * C, 2 * C, ctx, (long)Lq * C, C, B, Lq, Lt, H, D));
+    if (sa) TRY(mha_fwd_check(c.sa_q, c.sa_k, c.sa_v, c.ctx_o, B, Lq, Lq, c.H, c.D));
+    if (ta) TRY(mha_fwd_check(c.ta_q, c.ta_k, c.ta_v, c.ctx_o, B, Lq, Lt, c.H, c.D));
     return VLLM_OK;
 }
 
@@ -152,10 +158,9 @@ int dec_layer_run(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, const ui
     const bool sa = d->has_self_attn != 0, ta = d->has_text_attn != 0;
     const long R = (long)B * Lq;
     const int C = at.d_model;
-    const DecCall c = dec_call(d, dec_ws(d, B, Lq, Lt, S), workspace);
+    const DecCall c = dec_call(d, dec_ws(d, B, Lq, Lt, S), workspace, Lq, Lt);
     uint16_t *xp = c.xp, *bufa = c.bufa, *bufb = c.bufb, *qk = c.qk, *vb = c.vb, *ctx = c.ctx, *tkv = c.tkv;
-    const int H = c.H, D = c.D;
-    const float scale = 1.0f / sqrtf((float)D);
+    const float scale = 1.0f / sqrtf((float)c.D);
 
     // (the launchers without the public entries' checks: dec_layer_check_desc has C a multiple of 64 in 64 .. 512 and the norms' pointers,
     // dec_layer_check_call tgt / query_pos / out and every weight 16-byte aligned; x, y and xp are 256-byte aligned workspace, dense rows; R > 0)
@@ -176,8 +181,7 @@ int dec_layer_run(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, const ui
     if (sa) {
         TRY(gemm(st, EPI_BIAS, curp, C, d->sa_in_proj_w, C, d->sa_in_proj_b, qk, 2 * C, (int)R, 2 * C, C));
         TRY(gemm(st, EPI_BIAS, tgt, C, d->sa_in_proj_w + 2L * C * C, C, d->sa_in_proj_b + 2 * C, vb, C, (int)R, C, C));
-        TRY(mha_fwd_launch(qk, (long)Lq * 2 * C, 2 * C, qk + C, (long)Lq * 2 * C, 2 * C, vb, (long)Lq * C, C, ctx, (long)Lq * C, C, self_attn_mask,
-                           nullptr, B, Lq, Lq, H, D, scale, st));
+        TRY(mha_fwd_launch(c.sa_q, c.sa_k, c.sa_v, c.ctx_o, self_attn_mask, nullptr, B, Lq, Lq, c.H, c.D, scale, st));
         uint16_t *y = other();
         TRY(gemm(st, EPI_RESIDUAL, ctx, C, d->sa_out_proj_w, C, d->sa_out_proj_b, y, C, (int)R, C, C, nullptr, cur, C));
         TRY(finish_block(y, d->sa_norm_w, d->sa_norm_b, d->sa_norm_eps, true));
@@ -186,8 +190,7 @@ int dec_layer_run(const VllmDeformDecLayerDesc *d, const uint16_t *tgt, const ui
     if (ta) {
         TRY(gemm(st, EPI_BIAS, curp, C, d->text_in_proj_w, C, d->text_in_proj_b, vb, C, (int)R, C, C));
         TRY(gemm(st, EPI_BIAS, memory_text, C, d->text_in_proj_w + (long)C * C, C, d->text_in_proj_b + C, tkv, 2 * C, B * Lt, 2 * C, C));
-        TRY(mha_fwd_launch(vb, (long)Lq * C, C, tkv, (long)Lt * 2 * C, 2 * C, tkv + C, (long)Lt * 2 * C, 2 * C, ctx, (long)Lq * C, C, nullptr,
-                           text_key_padding_mask, B, Lq, Lt, H, D, scale, st));
+        TRY(mha_fwd_launch(c.ta_q, c.ta_k, c.ta_v, c.ctx_o, nullptr, text_key_padding_mask, B, Lq, Lt, c.H, c.D, scale, st));
         uint16_t *y = other();
         TRY(gemm(st, EPI_RESIDUAL, ctx, C, d->text_out_proj_w, C, d->text_out_proj_b, y, C, (int)R, C, C, nullptr, cur, C));
         TRY(finish_block(y, d->text_norm_w, d->text_norm_b, d->text_norm_eps, true));

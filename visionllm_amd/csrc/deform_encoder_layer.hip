@@ -16,6 +16,7 @@
 #include "orchestrate.hpp"
 #include "msda_layer.hpp"
 #include "deform_blocks.hpp"
+#include "row_groups.hpp"
 
 namespace vllm {
 namespace {
@@ -26,31 +27,23 @@ namespace {
 // before it reduces the current one (the scheme of rms_bwd_kernel, norm.hip): the reductions of one row run under the loads of the
 // next.  fp32 from the sum to the one rounding of y; the second moment is taken about the mean (norm_bf16_kernel).  x and y may be
 // the same memory: a lane writes the chunk it has read and no other.
-constexpr int ALN_THREADS = 256;
 struct AlnRow { uint4_t x, r, p; };
 
 template <int G>
-__global__ __launch_bounds__(ALN_THREADS) void add_layernorm_kernel(const uint16_t *x, int ldx, const uint16_t *res, int ldr,
+__global__ __launch_bounds__(ROWG_THREADS) void add_layernorm_kernel(const uint16_t *x, int ldx, const uint16_t *res, int ldr,
                                                                     const uint16_t *__restrict__ w, const uint16_t *__restrict__ b, uint16_t *y,
                                                                     int ldy, const uint16_t *pos, int ldp, uint16_t *y_pos, int ldq, long rows,
                                                                     int C, float eps)
 {
-    constexpr int R = 64 / G;
-    const int lane = threadIdx.x & 63, j = lane % G, sub = lane / G;
-    const long nwaves = (long)gridDim.x * (ALN_THREADS / 64), wave0 = (long)blockIdx.x * (ALN_THREADS / 64) + (threadIdx.x >> 6);
-    const long ngroups = (rows + R - 1) / R;
-    const bool act = j < (C >> 3);
-    const int c0 = j * 8;
+    const RowLanes<G> ln(rows, C);
+    const bool act = ln.act;
+    const int c0 = ln.c0;
+    const long nwaves = ln.nwaves;
     float gw[8], gb[8];
-    {
-        uint4_t wv = {0u, 0u, 0u, 0u}, bv = {0u, 0u, 0u, 0u};
-        if (act) { wv = *reinterpret_cast<const uint4_t *>(w + c0); bv = *reinterpret_cast<const uint4_t *>(b + c0); }
-        unpack8(wv, gw);
-        unpack8(bv, gb);
-    }
+    load_affine<G>(w, b, ln, gw, gb);
     auto load = [&](long g) {
         AlnRow t = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
-        const long row = g * R + sub;
+        const long row = ln.row(g);
         if (act && row < rows) {
             t.x = *reinterpret_cast<const uint4_t *>(x + row * ldx + c0);
             if (res) t.r = *reinterpret_cast<const uint4_t *>(res + row * ldr + c0);
@@ -59,31 +52,19 @@ __global__ __launch_bounds__(ALN_THREADS) void add_layernorm_kernel(const uint16
         return t;
     };
     const float invC = 1.0f / (float)C;
-    long g = wave0;
+    long g = ln.wave0;
     AlnRow cur = load(g);   // (g >= ngroups: row >= rows, nothing is read)
-    for (; g < ngroups; g += nwaves) {
+    for (; g < ln.ngroups; g += nwaves) {
         const AlnRow nxt = load(g + nwaves);
-        const long row = g * R + sub;
+        const long row = ln.row(g);
         float v[8], rr[8];
         unpack8(cur.x, v);
         unpack8(cur.r, rr);
-        float s = 0.f;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { v[e] += rr[e]; s += v[e]; }
-#pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        const float mean = s * invC;
-        float m2 = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { v[e] = act ? v[e] - mean : 0.f; m2 += v[e] * v[e]; }
-#pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) m2 += __shfl_xor(m2, o);
-        const float rstd = 1.0f / sqrtf(m2 * invC + eps);
+        for (int e = 0; e < 8; ++e) v[e] += rr[e];
+        const float rstd = layernorm_center<G>(v, act, invC, eps);
         if (act && row < rows) {
-            float o8[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o8[e] = v[e] * rstd * gw[e] + gb[e];
-            const uint4_t yo = pack8(o8);
+            const uint4_t yo = layernorm_chunk(v, rstd, gw, gb);
             *reinterpret_cast<uint4_t *>(y + row * ldy + c0) = yo;
             if (y_pos) {   // from the STORED y: the bits of adding pos to y afterwards
                 float ys[8], pp[8];
@@ -119,12 +100,7 @@ __global__ __launch_bounds__(256) void add_bf16_kernel(const uint16_t *__restric
 int add_layernorm_launch(const uint16_t *x, int ldx, const uint16_t *res, int ldr, const uint16_t *w, const uint16_t *b, uint16_t *y, int ldy,
                          const uint16_t *pos, int ldp, uint16_t *y_pos, int ldq, long rows, int C, float eps, hipStream_t st)
 {
-    const int G = C <= 256 ? 32 : 64;
-    const long ngroups = (rows + 64 / G - 1) / (64 / G), want = (ngroups + 3) / 4, cap = (long)device_cus() * 8;
-    const dim3 grid((unsigned)(want < cap ? want : cap));
-    if (G == 32) VLLM_LAUNCH((add_layernorm_kernel<32>), grid, dim3(ALN_THREADS), 0, st, x, ldx, res, ldr, w, b, y, ldy, pos, ldp, y_pos, ldq, rows, C, eps);
-    else VLLM_LAUNCH((add_layernorm_kernel<64>), grid, dim3(ALN_THREADS), 0, st, x, ldx, res, ldr, w, b, y, ldy, pos, ldp, y_pos, ldq, rows, C, eps);
-    VLLM_CHECK_LAUNCH("add_layernorm_kernel");
+    VLLM_LAUNCH_ROW_GROUPS(add_layernorm_kernel, rows, C, st, x, ldx, res, ldr, w, b, y, ldy, pos, ldp, y_pos, ldq, rows, C, eps);
     return VLLM_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <math.h>
 #include "common.hpp"
 #include "orchestrate.hpp"
+#include "mha_core.hpp"
 
 namespace vllm {
 namespace {
@@ -110,9 +111,10 @@ extern "C" int vllm_fusion_layer_forward(const VllmFusionLayerDesc *d, const uin
     uint16_t *vn = (uint16_t *)(ws + w.vn), *tn = (uint16_t *)(ws + w.tn), *qv = (uint16_t *)(ws + w.qv), *vv = (uint16_t *)(ws + w.vv);
     uint16_t *kt = (uint16_t *)(ws + w.kt), *vt = (uint16_t *)(ws + w.vt), *at = (uint16_t *)(ws + w.at), *av = vv;
     const long sE = (long)S * E, tE = (long)Lt * E;
+    const AttnOperand Qv = {qv, sE, E}, Vv = {vv, sE, E}, Av = {av, sE, E}, Kt = {kt, tE, E}, Vt = {vt, tE, E}, At = {at, tE, E};
     // the attention launches' own gates, before anything is enqueued
-    TRY(xattn_fwd_check(kt, tE, E, qv, sE, E, vv, sE, E, at, tE, E, B, Lt, S, H, D, ws + w.xa, w.xa_bytes));
-    TRY(xattn_fwd_check(qv, sE, E, kt, tE, E, vt, tE, E, av, sE, E, B, S, Lt, H, D, ws + w.xa, w.xa_bytes));
+    TRY(xattn_fwd_check(Kt, Qv, Vv, At, B, Lt, S, H, D, ws + w.xa, w.xa_bytes));
+    TRY(xattn_fwd_check(Qv, Kt, Vt, Av, B, S, Lt, H, D, ws + w.xa, w.xa_bytes));
     ++g_calls;
     hipStream_t st = (hipStream_t)stream;
     const float scale = 1.0f / sqrtf((float)D);
@@ -125,9 +127,9 @@ extern "C" int vllm_fusion_layer_forward(const VllmFusionLayerDesc *d, const uin
     TRY(gemm(st, EPI_BIAS, tn, C, d->text_proj_w, C, d->text_proj_b, kt, E, (int)Rt, E, C));
     TRY(gemm(st, EPI_BIAS, tn, C, d->values_text_proj_w, C, d->values_text_proj_b, vt, E, (int)Rt, E, C));
     // 3. text -> image (:958-971, :983): the keys are the image tokens, split by the plan
-    TRY(xattn_fwd_launch(kt, tE, E, qv, sE, E, vv, sE, E, at, tE, E, vision_padding_mask, B, Lt, S, H, D, scale, ws + w.xa, w.xa_bytes, st));
+    TRY(xattn_fwd_launch(Kt, Qv, Vv, At, vision_padding_mask, B, Lt, S, H, D, scale, ws + w.xa, w.xa_bytes, st));
     // 4. image -> text (:973-977, :982), into the memory of values_vision_proj's output
-    TRY(xattn_fwd_launch(qv, sE, E, kt, tE, E, vt, tE, E, av, sE, E, text_padding_mask, B, S, Lt, H, D, scale, ws + w.xa, w.xa_bytes, st));
+    TRY(xattn_fwd_launch(Qv, Kt, Vt, Av, text_padding_mask, B, S, Lt, H, D, scale, ws + w.xa, w.xa_bytes, st));
     // 5. output projections, layer scale, residual on the NORMALISED inputs (:1003-1004, :1098-1099)
     TRY(gemm(st, EPI_RESIDUAL, av, E, d->out_vision_proj_w, E, d->out_vision_proj_b, out_vision, C, (int)Rv, C, E, d->vision_param, vn, C));
     return gemm(st, EPI_RESIDUAL, at, E, d->out_text_proj_w, E, d->out_text_proj_b, out_text, C, (int)Rt, C, E, d->text_param, tn, C);

@@ -22,9 +22,6 @@
 
 namespace vllm {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int GEMM_THREADS = 256;
 constexpr int TILE_BYTES = BM * BK * 2;  // 16 KiB per operand per stage

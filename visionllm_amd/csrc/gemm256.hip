@@ -22,9 +22,6 @@
 
 namespace vllm {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 __device__ unsigned long long g_g2_prof[8];   // VLLM_GEMM_PROF: shader-clock ticks of wave 0 per phase, summed over blocks
 constexpr int G2_BN = 256, G2_BK = 64;   // block rows are 64 * MT (template parameter)
 constexpr int G2_THREADS = 512;
@@ -475,7 +472,6 @@ __global__ __launch_bounds__(G2_THREADS, 1) void gemm256_bf16_kernel(const GemmA
         // thread and acquire polls cost ~100 us per GEMM: each is a walk over the XCD's L2.)
         // scratch slot: 32 16-byte vectors per thread, vector v of thread t at (v * 512 + t) -> every access is a coalesced 8 KiB row
         const __amdgpu_buffer_rsrc_t ws_rs = __builtin_amdgcn_make_buffer_rsrc((void *)a.sk_ws, 0, (int)(a.sk_blocks * (32 * G2_THREADS * 16)), 0x00020000);
-        typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
         constexpr int AUX_SC1 = 16;
         if (!finishing) {
             const int base = (rid * (32 * G2_THREADS) + tid_l) * 16;

@@ -33,11 +33,6 @@ namespace vllm {
 
 namespace {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int P_BN = 256, P_BK = 64, P_THREADS = 512;
 constexpr int P_HALF = 128 * P_BK * 2;            // 16 KiB half-tile
 constexpr int P_STAGE = 4 * P_HALF;               // A0 A1 B0 B1

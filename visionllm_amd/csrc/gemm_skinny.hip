@@ -32,11 +32,6 @@ namespace vllm {
 
 namespace {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-
 constexpr int SK_K = 256, SK_KS = SK_K / 32, SK_R = 64, SK_STAGE = SK_R * SK_K * 2, SK_S = 4, SK_THREADS = 512;
 constexpr int SK_AUX = 8 * 1024;           // per stage: one 1 KiB slot per wave for the chunk's per-row epilogue inputs
 constexpr int SK_LDS = SK_S * (SK_STAGE + SK_AUX);   // 160 KiB

@@ -23,10 +23,6 @@ namespace vllm {
 
 namespace {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int WG_TN = 128, WG_TK = 128, WG_BM = 64;   // output tile (n x k), reduction rows per step
 constexpr int WG_THREADS = 256;
 constexpr int WG_ROW = 256;                          // bytes per staged row (128 bf16)

@@ -244,20 +244,19 @@ int attn_bwd_launch(const uint16_t *qkv, const uint16_t *out, const float *lse, 
 
 // mha.hip: masked attention for short sequences (the decoder layers' self- and text attention); the arguments of vllm_mha_fwd_bf16.
 // mha_fwd_check is the launch's own gate, host-only: an orchestrator asks it before it enqueues anything.
-int mha_fwd_check(const uint16_t *q, long q_bs, int ldq, const uint16_t *k, long k_bs, int ldk, const uint16_t *v, long v_bs, int ldv,
-                  const uint16_t *out, long o_bs, int ldo, int B, int Lq, int Lk, int H, int D);
-int mha_fwd_launch(const uint16_t *q, long q_bs, int ldq, const uint16_t *k, long k_bs, int ldk, const uint16_t *v, long v_bs, int ldv,
-                   uint16_t *out, long o_bs, int ldo, const uint8_t *attn_mask, const uint8_t *key_padding_mask, int B, int Lq, int Lk,
-                   int H, int D, float softmax_scale, hipStream_t st);
+// An operand is {pointer, batch stride, row stride} (AttnOperand, mha_core.hpp); `out` is written by the launch.
+struct AttnOperand;
+int mha_fwd_check(const AttnOperand &q, const AttnOperand &k, const AttnOperand &v, const AttnOperand &out, int B, int Lq, int Lk, int H, int D);
+int mha_fwd_launch(const AttnOperand &q, const AttnOperand &k, const AttnOperand &v, const AttnOperand &out, const uint8_t *attn_mask,
+                   const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D, float softmax_scale, hipStream_t st);
 
 // xattn.hip: masked cross attention for head dims 128 / 256 with an optional key split; the arguments of vllm_xattn_fwd_bf16.
 // xattn_fwd_check is the launch's own gate, host-only; xattn_ws_bytes the bytes the plan's partials take (0: one split).
 long xattn_ws_bytes(int B, int Lq, int Lk, int H, int D);
-int xattn_fwd_check(const uint16_t *q, long q_bs, int ldq, const uint16_t *k, long k_bs, int ldk, const uint16_t *v, long v_bs, int ldv,
-                    const uint16_t *out, long o_bs, int ldo, int B, int Lq, int Lk, int H, int D, const void *ws, long ws_bytes);
-int xattn_fwd_launch(const uint16_t *q, long q_bs, int ldq, const uint16_t *k, long k_bs, int ldk, const uint16_t *v, long v_bs, int ldv,
-                     uint16_t *out, long o_bs, int ldo, const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D,
-                     float softmax_scale, void *ws, long ws_bytes, hipStream_t st);
+int xattn_fwd_check(const AttnOperand &q, const AttnOperand &k, const AttnOperand &v, const AttnOperand &out, int B, int Lq, int Lk, int H, int D,
+                    const void *ws, long ws_bytes);
+int xattn_fwd_launch(const AttnOperand &q, const AttnOperand &k, const AttnOperand &v, const AttnOperand &out, const uint8_t *key_padding_mask,
+                     int B, int Lq, int Lk, int H, int D, float softmax_scale, void *ws, long ws_bytes, hipStream_t st);
 
 // embed_train.hip: a Conv2d weight [C, K] as the module stores it <-> its K-padded copy [C, kpad] (16-byte aligned kpad rows; [C, K] 4-byte)
 int pad_weight_launch(const uint16_t *w, uint16_t *wp, int C, int K, int kpad, hipStream_t st);

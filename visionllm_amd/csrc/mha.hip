@@ -22,12 +22,12 @@
 #include <math.h>
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mha_core.hpp"
 
 namespace vllm {
 namespace {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-constexpr int MHA_THREADS = 256, MHA_QBLK = 64, MHA_KV = 64;
+constexpr int MHA_THREADS = ATILE_THREADS, MHA_QBLK = ATILE_QBLK, MHA_KV = ATILE_KV;
 
 struct MhaArgs {
     const uint16_t *q, *k, *v;
@@ -41,14 +41,13 @@ struct MhaArgs {
 };
 
 // 4 workgroups per CU at the workload shape (B 8 x H 8 x 15 blocks over 256 CUs) = 4 waves per SIMD, a budget of 128 VGPRs: the kernel
-// takes 77 (D 32) / 112 (D 64) VGPRs and 9.8 / 18.5 KB of static LDS per workgroup, no scratch
+// takes 75 (D 32) / 112 (D 64) VGPRs and 9.8 / 18.5 KB of static LDS per workgroup, no scratch
 template <int D>
 __global__ __launch_bounds__(MHA_THREADS, 4) void mha_fwd_kernel(const MhaArgs a)
 {
     constexpr int KS = D / 32;            // k-steps of K Q^T
     constexpr int DB = D / 16;            // 16-wide blocks of the output's channels
-    constexpr int KLD = D + 8;            // K tile: [key][d], row stride in elements
-    constexpr int VLD = MHA_KV + 8;       // V tile: [d][key]
+    constexpr int KLD = atile_kld<D>(), VLD = ATILE_VLD;   // row strides of the K tile [key][d] and of the V tile [d][key], in elements
     constexpr int CPR = D / 8;            // 16-byte chunks per K / V row
     constexpr int RPP = MHA_THREADS / CPR;   // rows one staging pass covers
     constexpr int NI = MHA_KV / RPP;      // staging passes per tile
@@ -57,23 +56,18 @@ __global__ __launch_bounds__(MHA_THREADS, 4) void mha_fwd_kernel(const MhaArgs a
     __shared__ __attribute__((aligned(16))) uint8_t dead[MHA_KV];
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, g = lane >> 4;
-    // ---- block -> (image, head, query block): all query blocks of an (image, head) on one XCD ----
-    const int xcd = blockIdx.x & 7, sidx = blockIdx.x >> 3;
-    const int bh = (sidx / a.nqt) * 8 + xcd, qt = sidx % a.nqt;
-    if (bh >= a.B * a.H) return;   // (block-uniform, in front of every barrier)
+    int bh, qt;   // block -> (image, head, query block)
+    if (!atile_block(a.nqt, a.B * a.H, bh, qt)) return;
     const int b = bh / a.H, head = bh % a.H;
     const uint16_t *qb = a.q + (long)b * a.q_bs + (long)head * D;
     const uint16_t *kb_ = a.k + (long)b * a.k_bs + (long)head * D;
     const uint16_t *vb_ = a.v + (long)b * a.v_bs + (long)head * D;
     const uint8_t *kpm = a.kpm ? a.kpm + (long)b * a.Lk : nullptr;
 
-    // ---- Q fragments (B operand): lane (query l15, g) holds Q[query][32 ks + 8 g .. + 7]; rows behind Lq read row Lq - 1 ----
     const int q_row = qt * MHA_QBLK + wave * 16 + l15;
-    const int q_ld = q_row < a.Lq ? q_row : a.Lq - 1;
     const bool live_wave = qt * MHA_QBLK + wave * 16 < a.Lq;   // wave-uniform
     bf16x8_t qf[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) qf[s] = *reinterpret_cast<const bf16x8_t *>(qb + (long)q_ld * a.ldq + 32 * s + 8 * g);
+    const int q_ld = atile_load_q<KS>(qb, q_row, a.Lq, a.ldq, g, qf);
     const uint8_t *am = a.am ? a.am + (long)q_ld * a.Lk : nullptr;
 
     float4_t o[DB];
@@ -145,125 +139,48 @@ __global__ __launch_bounds__(MHA_THREADS, 4) void mha_fwd_kernel(const MhaArgs a
                 mw[kb][s] = w;
             }
 
-        // ---- S^T = K Q^T, key rows permuted (file comment): st[kb][s][r] = score of key 32 kb + 8 g + 4 s + r ----
         float4_t st[2][2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const int row = kb * 32 + 8 * (l15 >> 2) + 4 * s + (l15 & 3);
-                float4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int c = 0; c < KS; ++c) {
-                    const bf16x8_t kf = *reinterpret_cast<const bf16x8_t *>(&ks[row * KLD + 32 * c + 8 * g]);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[c], acc, 0, 0, 0);
-                }
-                st[kb][s] = acc;
-            }
-
-        // ---- online softmax, exp2 domain ----
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float x = ((mw[kb][s] >> (8 * r)) & 0xffu) ? -INFINITY : st[kb][s][r] * a.c2;
-                    st[kb][s][r] = x;
-                    mx = fmaxf(mx, x);
-                }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx);
-        // every key so far masked: m_new is -inf; subtract 0 instead, so that p = exp2(-inf) = 0 and nothing forms (-inf) - (-inf)
-        const float m_use = m_new == -INFINITY ? 0.f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);   // m_run = -inf: 0, and l_run and o are still 0
-        m_run = m_new;
-        l_run *= alpha;
-#pragma unroll
-        for (int d = 0; d < DB; ++d) o[d] *= alpha;
-        // P rounded to bf16 (what P V multiplies); the row sum is taken from the ROUNDED values, so O / l normalises what was accumulated
         bf16x8_t pf[2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            uint4_t pw;
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int r = 0; r < 4; r += 2) {
-                    const float p0 = __builtin_amdgcn_exp2f(st[kb][s][r] - m_use), p1 = __builtin_amdgcn_exp2f(st[kb][s][r + 1] - m_use);
-                    const uint32_t w = pack_bf16x2(p0, p1);
-                    pw[2 * s + (r >> 1)] = w;
-                    l_run += bf16lo_to_f32(w) + bf16hi_to_f32(w);
-                }
-            pf[kb] = __builtin_bit_cast(bf16x8_t, pw);
-        }
-        // ---- O^T += V^T P^T: A = V^T, lane (channel 16 d + l15, g) reads keys 32 kb + 8 g .. + 7 of its channel ----
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int d = 0; d < DB; ++d) {
-                const bf16x8_t vf = *reinterpret_cast<const bf16x8_t *>(&vt[(d * 16 + l15) * VLD + kb * 32 + 8 * g]);
-                o[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[kb], o[d], 0, 0, 0);
-            }
+        atile_scores<D>(ks, qf, l15, g, st);
+        atile_softmax<DB>(st, mw, a.c2, m_run, l_run, o, pf);
+        atile_accumulate<D>(vt, pf, l15, g, o);
     }
 
     // ---- finalize: lane (query l15, g) holds channels 16 d + 4 g + r ----
     if (!live_wave) return;
-    float l_tot = l_run + __shfl_xor(l_run, 16);
-    l_tot += __shfl_xor(l_tot, 32);
-    const bool none = m_run == -INFINITY;   // every key of the row masked (the groups of a query agree: m_run is the reduced maximum)
-    const float inv = 1.0f / l_tot;
-    if (q_row < a.Lq) {
-        uint16_t *op = a.out + (long)b * a.o_bs + (long)q_row * a.ldo + head * D + 4 * g;
-#pragma unroll
-        for (int d = 0; d < DB; ++d) {
-            uint2_t w;
-            w.x = none ? 0x7fc07fc0u : pack_bf16x2(o[d][0] * inv, o[d][1] * inv);
-            w.y = none ? 0x7fc07fc0u : pack_bf16x2(o[d][2] * inv, o[d][3] * inv);
-            *reinterpret_cast<uint2_t *>(op + d * 16) = w;
-        }
-    }
+    const float l_tot = atile_row_sum(l_run);
+    if (q_row < a.Lq) atile_store_row<DB>(a.out + (long)b * a.o_bs + (long)q_row * a.ldo + head * D + 4 * g, o, m_run, l_tot);
 }
 
-bool operand_ok(const void *p, long bs, int ld, int HD) { return aligned16(p) && ld % 8 == 0 && ld >= HD && bs % 8 == 0; }
+bool operand_ok(const AttnOperand &x, int HD) { return aligned16(x.p) && x.ld % 8 == 0 && x.ld >= HD && x.bs % 8 == 0; }
 
 }  // namespace
 
 // host-only: VLLM_OK where vllm_mha_fwd_bf16 would launch (or has nothing to do), VLLM_EINVAL with the reason otherwise
-int mha_fwd_check(const uint16_t *q, long q_bs, int ldq, const uint16_t *k, long k_bs, int ldk, const uint16_t *v, long v_bs, int ldv,
-                  const uint16_t *out, long o_bs, int ldo, int B, int Lq, int Lk, int H, int D)
+int mha_fwd_check(const AttnOperand &q, const AttnOperand &k, const AttnOperand &v, const AttnOperand &out, int B, int Lq, int Lk, int H, int D)
 {
     VLLM_REQUIRE(D == 32 || D == 64, "mha_fwd: head dim %d (32 or 64)", D);
     VLLM_REQUIRE(B >= 0 && Lq >= 0 && Lk >= 0 && H >= 1 && (long)B * H < (1L << 28) && (long)H * D < (1L << 24),
                  "mha_fwd: B=%d Lq=%d Lk=%d H=%d (B, Lq, Lk >= 0; H >= 1)", B, Lq, Lk, H);
     if ((long)B * Lq == 0) return VLLM_OK;
     VLLM_REQUIRE(Lk >= 1, "mha_fwd: Lk=%d (at least one key)", Lk);
-    VLLM_REQUIRE(q && k && v && out, "mha_fwd: null pointer (q / k / v / out)");
-    VLLM_REQUIRE(operand_ok(q, q_bs, ldq, H * D) && operand_ok(k, k_bs, ldk, H * D) && operand_ok(v, v_bs, ldv, H * D) &&
-                     operand_ok(out, o_bs, ldo, H * D),
+    VLLM_REQUIRE(q.p && k.p && v.p && out.p, "mha_fwd: null pointer (q / k / v / out)");
+    VLLM_REQUIRE(operand_ok(q, H * D) && operand_ok(k, H * D) && operand_ok(v, H * D) && operand_ok(out, H * D),
                  "mha_fwd: misaligned operand (16-byte aligned pointers; row and batch strides multiples of 8 elements, row stride at least H D)");
     return VLLM_OK;
 }
 
-int mha_fwd_launch(const uint16_t *q, long q_bs, int ldq, const uint16_t *k, long k_bs, int ldk, const uint16_t *v, long v_bs, int ldv,
-                   uint16_t *out, long o_bs, int ldo, const uint8_t *attn_mask, const uint8_t *key_padding_mask, int B, int Lq, int Lk,
-                   int H, int D, float softmax_scale, hipStream_t st)
+int mha_fwd_launch(const AttnOperand &q, const AttnOperand &k, const AttnOperand &v, const AttnOperand &out, const uint8_t *attn_mask,
+                   const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D, float softmax_scale, hipStream_t st)
 {
-    const int rc = mha_fwd_check(q, q_bs, ldq, k, k_bs, ldk, v, v_bs, ldv, out, o_bs, ldo, B, Lq, Lk, H, D);
+    const int rc = mha_fwd_check(q, k, v, out, B, Lq, Lk, H, D);
     if (rc != VLLM_OK) return rc;
     if ((long)B * Lq == 0) return VLLM_OK;
     MhaArgs a;
-    a.q = q; a.k = k; a.v = v; a.out = out;
-    a.q_bs = q_bs; a.k_bs = k_bs; a.v_bs = v_bs; a.o_bs = o_bs;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-    a.am = attn_mask; a.kpm = key_padding_mask;
+    atile_fill_args(a, q, k, v, out, key_padding_mask, B, Lq, Lk, H, softmax_scale);
+    a.am = attn_mask;
     a.am_words = attn_mask && (reinterpret_cast<uintptr_t>(attn_mask) & 3u) == 0 && Lk % 4 == 0;
-    a.B = B; a.Lq = Lq; a.Lk = Lk; a.H = H;
-    a.nqt = (Lq + MHA_QBLK - 1) / MHA_QBLK;
-    a.c2 = softmax_scale * 1.4426950408889634f;
-    const long blocks = (long)(((long)B * H + 7) / 8) * 8 * a.nqt;
+    const long blocks = atile_blocks(B, H, a.nqt);
     VLLM_REQUIRE(blocks < (1L << 31), "mha_fwd: too many workgroups (B H Lq / 64 >= 2^31)");
     const dim3 grid((unsigned)blocks), block(MHA_THREADS);
     if (D == 32) VLLM_LAUNCH((mha_fwd_kernel<32>), grid, block, 0, st, a);
@@ -281,6 +198,6 @@ extern "C" int vllm_mha_fwd_bf16(const uint16_t *q, long q_batch_stride, int ldq
                                  const uint8_t *attn_mask, const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D,
                                  float softmax_scale, vllm_stream_t stream)
 {
-    return mha_fwd_launch(q, q_batch_stride, ldq, k, k_batch_stride, ldk, v, v_batch_stride, ldv, out, o_batch_stride, ldo, attn_mask,
+    return mha_fwd_launch({q, q_batch_stride, ldq}, {k, k_batch_stride, ldk}, {v, v_batch_stride, ldv}, {out, o_batch_stride, ldo}, attn_mask,
                           key_padding_mask, B, Lq, Lk, H, D, softmax_scale, (hipStream_t)stream);
 }

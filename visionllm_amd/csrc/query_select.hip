@@ -20,11 +20,11 @@
 #include <math.h>
 #include "common.hpp"
 #include "orchestrate.hpp"
+#include "row_groups.hpp"
 
 namespace vllm {
 namespace {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 constexpr int QS_MAX_LEVELS = 16;
 
 // ---- proposals (:2244-2269) ----------------------------------------------------------------------------------------------------------
@@ -83,36 +83,24 @@ __device__ __forceinline__ QsProposal qs_proposal(long s, int b, const int64_t *
 }
 
 // ---- enc_output_norm with the zero-fill as a row override (:2273-2275) -------------------------------------------------------------------
-// The rows of add_layernorm_kernel (deform_encoder_layer.hip): G lanes share a row, lane j owns its 16-byte chunk j.  A padded row or one
-// with an invalid proposal takes its chunk from `lin_b`, the bias of the linear in front: what that linear gives for a zero row.  In place.
-constexpr int QN_THREADS = 256;
+// Row groups (row_groups.hpp).  A padded row or one with an invalid proposal takes its chunk from `lin_b`, the bias of the linear in
+// front: what that linear gives for a zero row.  In place.
 template <int G>
-__global__ __launch_bounds__(QN_THREADS) void qs_norm_kernel(uint16_t *x, const uint16_t *__restrict__ lin_b, const uint16_t *__restrict__ w,
+__global__ __launch_bounds__(ROWG_THREADS) void qs_norm_kernel(uint16_t *x, const uint16_t *__restrict__ lin_b, const uint16_t *__restrict__ w,
                                                              const uint16_t *__restrict__ b, const uint8_t *__restrict__ pmask,
                                                              const int64_t *__restrict__ shapes, const int64_t *__restrict__ lsi,
                                                              const int *__restrict__ extents, int L, int S, long rows, int C, float eps)
 {
-    constexpr int R = 64 / G;
-    const int lane = threadIdx.x & 63, j = lane % G, sub = lane / G;
-    const long nwaves = (long)gridDim.x * (QN_THREADS / 64), wave0 = (long)blockIdx.x * (QN_THREADS / 64) + (threadIdx.x >> 6);
-    const long ngroups = (rows + R - 1) / R;
-    const bool act = j < (C >> 3);
-    const int c0 = j * 8;
+    const RowLanes<G> ln(rows, C);
+    const bool act = ln.act;
+    const int c0 = ln.c0;
     float gw[8], gb[8];
+    load_affine<G>(w, b, ln, gw, gb);
     uint4_t zero_row = {0u, 0u, 0u, 0u};
-    {
-        uint4_t wv = {0u, 0u, 0u, 0u}, bv = {0u, 0u, 0u, 0u};
-        if (act) {
-            wv = *reinterpret_cast<const uint4_t *>(w + c0);
-            bv = *reinterpret_cast<const uint4_t *>(b + c0);
-            zero_row = *reinterpret_cast<const uint4_t *>(lin_b + c0);
-        }
-        unpack8(wv, gw);
-        unpack8(bv, gb);
-    }
+    if (act) zero_row = *reinterpret_cast<const uint4_t *>(lin_b + c0);
     const float invC = 1.0f / (float)C;
-    for (long g = wave0; g < ngroups; g += nwaves) {
-        const long row = g * R + sub;
+    for (long g = ln.wave0; g < ln.ngroups; g += ln.nwaves) {
+        const long row = ln.row(g);
         uint4_t xv = {0u, 0u, 0u, 0u};
         if (act && row < rows) {
             const long bi = row / S;
@@ -121,24 +109,8 @@ __global__ __launch_bounds__(QN_THREADS) void qs_norm_kernel(uint16_t *x, const 
         }
         float v[8];
         unpack8(xv, v);
-        float s = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s += v[e];
-#pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        const float mean = s * invC;
-        float m2 = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { v[e] = act ? v[e] - mean : 0.f; m2 += v[e] * v[e]; }
-#pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) m2 += __shfl_xor(m2, o);
-        const float rstd = 1.0f / sqrtf(m2 * invC + eps);
-        if (act && row < rows) {
-            float o8[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o8[e] = v[e] * rstd * gw[e] + gb[e];
-            *reinterpret_cast<uint4_t *>(x + row * C + c0) = pack8(o8);
-        }
+        const float rstd = layernorm_center<G>(v, act, invC, eps);
+        if (act && row < rows) *reinterpret_cast<uint4_t *>(x + row * C + c0) = layernorm_chunk(v, rstd, gw, gb);
     }
 }
 
@@ -450,50 +422,29 @@ __global__ __launch_bounds__(256) void qs_gather_kernel(const uint16_t *__restri
 }
 
 // coords_logits[r, c] = h[r, :] . W[c, :] + bias[c] + log(p / (1 - p)), p = the proposal of the row's index (+inf for a padded row or an
-// invalid proposal, the reference's two masked_fill); reference_points = sigmoid of it, so +inf gives 1.0.  fp32; the rows and the fixed
-// xor tree of box_refine_kernel (deform_decoder.hip).  valid [rows] (optional): the proposal's validity flag.
-constexpr int QT_THREADS = 256;
+// invalid proposal, the reference's two masked_fill); reference_points = sigmoid of it, so +inf gives 1.0.  fp32; row groups and their
+// four fused dot products (row_groups.hpp), as box_refine_kernel (deform_decoder.hip).  valid [rows] (optional): the proposal's validity flag.
 template <int G>
-__global__ __launch_bounds__(QT_THREADS) void qs_tail_kernel(const uint16_t *__restrict__ h, int ldh, const uint16_t *__restrict__ W,
+__global__ __launch_bounds__(ROWG_THREADS) void qs_tail_kernel(const uint16_t *__restrict__ h, int ldh, const uint16_t *__restrict__ W,
                                                              const uint16_t *__restrict__ bias, const int64_t *__restrict__ topk,
                                                              const uint8_t *__restrict__ pmask, const int64_t *__restrict__ shapes,
                                                              const int64_t *__restrict__ lsi, const int *__restrict__ extents, int L, int S, int k,
                                                              long rows, int C, float *__restrict__ coords, float *__restrict__ refp,
                                                              uint8_t *__restrict__ valid)
 {
-    constexpr int RW = 64 / G;
-    const int lane = threadIdx.x & 63, j = lane % G, sub = lane / G;
-    const long nwaves = (long)gridDim.x * (QT_THREADS / 64), wave0 = (long)blockIdx.x * (QT_THREADS / 64) + (threadIdx.x >> 6);
-    const long ngroups = (rows + RW - 1) / RW;
-    const bool act = j < (C >> 3), fin = j < 4;
-    const int c0 = j * 8;
+    const RowLanes<G> ln(rows, C);
+    const int j = ln.j;
+    const bool fin = j < 4;
     float w[4][8];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        uint4_t wv = {0u, 0u, 0u, 0u};
-        if (act) wv = *reinterpret_cast<const uint4_t *>(W + (long)c * C + c0);
-        unpack8(wv, w[c]);
-    }
-    const float bk = fin ? bf16_to_f32(bias[j]) : 0.f;
-    for (long g = wave0; g < ngroups; g += nwaves) {
-        const long row = g * RW + sub;
+    const float bk = load_dot4<G>(W, bias, C, ln, w);
+    for (long g = ln.wave0; g < ln.ngroups; g += ln.nwaves) {
+        const long row = ln.row(g);
         uint4_t xv = {0u, 0u, 0u, 0u};
-        if (act && row < rows) xv = *reinterpret_cast<const uint4_t *>(h + row * ldh + c0);
-        float v[8], s[4];
-        unpack8(xv, v);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            s[c] = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) s[c] = fmaf(v[e], w[c][e], s[c]);
-        }
-#pragma unroll
-        for (int o = G / 2; o > 0; o >>= 1) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) s[c] += __shfl_xor(s[c], o);
-        }
+        if (ln.act && row < rows) xv = *reinterpret_cast<const uint4_t *>(h + row * ldh + ln.c0);
+        float s[4];
+        dot4_rows<G>(xv, w, s);
         if (fin && row < rows) {
-            const float dot = j == 0 ? s[0] : j == 1 ? s[1] : j == 2 ? s[2] : s[3];
+            const float dot = dot4_pick(s, j);
             const long bi = row / k;
             long idx = topk[row];
             idx = idx < 0 ? 0 : idx >= S ? S - 1 : idx;
@@ -519,12 +470,7 @@ int extents_launch(const uint8_t *pmask, const int64_t *shapes, const int64_t *l
 int norm_launch(uint16_t *x, const uint16_t *lin_b, const uint16_t *w, const uint16_t *b, const uint8_t *pmask, const int64_t *shapes,
                 const int64_t *lsi, const int *extents, int L, int S, long rows, int C, float eps, hipStream_t st)
 {
-    const int G = C <= 256 ? 32 : 64;
-    const long ngroups = (rows + 64 / G - 1) / (64 / G), want = (ngroups + 3) / 4, cap = (long)device_cus() * 8;
-    const dim3 grid((unsigned)(want < cap ? want : cap));
-    if (G == 32) VLLM_LAUNCH((qs_norm_kernel<32>), grid, dim3(QN_THREADS), 0, st, x, lin_b, w, b, pmask, shapes, lsi, extents, L, S, rows, C, eps);
-    else VLLM_LAUNCH((qs_norm_kernel<64>), grid, dim3(QN_THREADS), 0, st, x, lin_b, w, b, pmask, shapes, lsi, extents, L, S, rows, C, eps);
-    VLLM_CHECK_LAUNCH("qs_norm_kernel");
+    VLLM_LAUNCH_ROW_GROUPS(qs_norm_kernel, rows, C, st, x, lin_b, w, b, pmask, shapes, lsi, extents, L, S, rows, C, eps);
     return VLLM_OK;
 }
 
@@ -547,16 +493,7 @@ int tail_launch(const uint16_t *h, int ldh, const uint16_t *W, const uint16_t *b
                 const int64_t *shapes, const int64_t *lsi, const int *extents, int L, int S, int k, long rows, int C, float *coords, float *refp,
                 uint8_t *valid, hipStream_t st)
 {
-    const int G = C <= 256 ? 32 : 64;
-    const long ngroups = (rows + 64 / G - 1) / (64 / G), want = (ngroups + 3) / 4, cap = (long)device_cus() * 8;
-    const dim3 grid((unsigned)(want < cap ? want : cap));
-    if (G == 32)
-        VLLM_LAUNCH((qs_tail_kernel<32>), grid, dim3(QT_THREADS), 0, st, h, ldh, W, bias, topk, pmask, shapes, lsi, extents, L, S, k, rows, C, coords,
-                    refp, valid);
-    else
-        VLLM_LAUNCH((qs_tail_kernel<64>), grid, dim3(QT_THREADS), 0, st, h, ldh, W, bias, topk, pmask, shapes, lsi, extents, L, S, k, rows, C, coords,
-                    refp, valid);
-    VLLM_CHECK_LAUNCH("qs_tail_kernel");
+    VLLM_LAUNCH_ROW_GROUPS(qs_tail_kernel, rows, C, st, h, ldh, W, bias, topk, pmask, shapes, lsi, extents, L, S, k, rows, C, coords, refp, valid);
     return VLLM_OK;
 }
 

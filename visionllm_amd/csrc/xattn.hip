@@ -29,12 +29,12 @@
 #include <math.h>
 #include "common.hpp"
 #include "kernels.hpp"
+#include "mha_core.hpp"
 
 namespace vllm {
 namespace {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-constexpr int XA_THREADS = 256, XA_QBLK = 64, XA_KV = 64;
+constexpr int XA_THREADS = ATILE_THREADS, XA_QBLK = ATILE_QBLK, XA_KV = ATILE_KV;
 // The plan: no split at up to XA_NOSPLIT_TILES key tiles (512 keys: the text side and small maps) or where the query blocks alone fill the
 // target of two workgroups on each of 256 CUs; otherwise as many splits as reach the target, of at least XA_MIN_TILES key tiles each (a
 // split of fewer than 256 keys does not pay for its partials and their combine).
@@ -52,7 +52,7 @@ struct XattnArgs {
     float c2;                  // softmax_scale * log2(e)
 };
 
-template <int D> constexpr int xattn_lds_bytes() { return (XA_KV * (D + 8) + D * (XA_KV + 8)) * 2 + XA_KV; }
+template <int D> constexpr int xattn_lds_bytes() { return (XA_KV * atile_kld<D>() + D * ATILE_VLD) * 2 + XA_KV; }
 
 // two workgroups per CU = 2 waves per SIMD, a budget of 256 VGPRs
 template <int D, bool SPLIT>
@@ -60,9 +60,8 @@ __global__ __launch_bounds__(XA_THREADS, 2) void xattn_fwd_kernel(const XattnArg
 {
     constexpr int KS = D / 32;            // k-steps of K Q^T
     constexpr int DB = D / 16;            // 16-wide blocks of the output's channels
-    constexpr int KLD = D + 8;            // K tile: [key][d], row stride in elements
-    constexpr int VLD = XA_KV + 8;        // V tile: [d][key]
-    constexpr int CPR = D / 8;            // 16-byte chunks per K / V row
+    constexpr int KLD = atile_kld<D>(), VLD = ATILE_VLD;   // row strides of the K tile [key][d] and of the V tile [d][key], in elements
+    constexpr int CPR = D / 8;           // 16-byte chunks per K / V row
     constexpr int RPP = XA_THREADS / CPR; // K rows one staging pass covers
     constexpr int NI = XA_KV / RPP;       // K staging passes per tile
     constexpr int NV = CPR / 8;           // V staging passes per tile: 32 key pairs x 8 chunks per pass
@@ -71,10 +70,8 @@ __global__ __launch_bounds__(XA_THREADS, 2) void xattn_fwd_kernel(const XattnArg
     uint8_t *dead = reinterpret_cast<uint8_t *>(vt + D * VLD);
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, g = lane >> 4;
-    // ---- block -> (image, head, query block, split): every block of an (image, head) on one XCD ----
-    const int xcd = blockIdx.x & 7, sidx = blockIdx.x >> 3, per = a.nqt * a.splits;
-    const int bh = (sidx / per) * 8 + xcd, rem = sidx % per;
-    if (bh >= a.B * a.H) return;   // (block-uniform, in front of every barrier)
+    int bh, rem;   // block -> (image, head, query block, split)
+    if (!atile_block(a.nqt * a.splits, a.B * a.H, bh, rem)) return;
     const int qt = rem / a.splits, split = rem - qt * a.splits;
     const int b = bh / a.H, head = bh % a.H;
     const int kbeg = split * a.kps, kend = a.Lk - kbeg < a.kps ? a.Lk : kbeg + a.kps;   // this split's keys
@@ -83,13 +80,10 @@ __global__ __launch_bounds__(XA_THREADS, 2) void xattn_fwd_kernel(const XattnArg
     const uint16_t *vb_ = a.v + (long)b * a.v_bs + (long)head * D;
     const uint8_t *kpm = a.kpm ? a.kpm + (long)b * a.Lk : nullptr;
 
-    // ---- Q fragments (B operand): lane (query l15, g) holds Q[query][32 ks + 8 g .. + 7]; rows behind Lq read row Lq - 1 ----
     const int q_row = qt * XA_QBLK + wave * 16 + l15;
-    const int q_ld = q_row < a.Lq ? q_row : a.Lq - 1;
     const bool live_wave = qt * XA_QBLK + wave * 16 < a.Lq;   // wave-uniform
     bf16x8_t qf[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) qf[s] = *reinterpret_cast<const bf16x8_t *>(qb + (long)q_ld * a.ldq + 32 * s + 8 * g);
+    atile_load_q<KS>(qb, q_row, a.Lq, a.ldq, g, qf);
 
     float4_t o[DB];
 #pragma unroll
@@ -153,74 +147,16 @@ __global__ __launch_bounds__(XA_THREADS, 2) void xattn_fwd_kernel(const XattnArg
 #pragma unroll
             for (int s = 0; s < 2; ++s) mw[kb][s] = *reinterpret_cast<const uint32_t *>(&dead[kb * 32 + 8 * g + 4 * s]);
 
-        // ---- S^T = K Q^T, key rows permuted (mha.hip): st[kb][s][r] = score of key 32 kb + 8 g + 4 s + r ----
         float4_t st[2][2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                const int row = kb * 32 + 8 * (l15 >> 2) + 4 * s + (l15 & 3);
-                float4_t acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int c = 0; c < KS; ++c) {
-                    const bf16x8_t kf = *reinterpret_cast<const bf16x8_t *>(&ks[row * KLD + 32 * c + 8 * g]);
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[c], acc, 0, 0, 0);
-                }
-                st[kb][s] = acc;
-            }
-
-        // ---- online softmax, exp2 domain ----
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float x = ((mw[kb][s] >> (8 * r)) & 0xffu) ? -INFINITY : st[kb][s][r] * a.c2;
-                    st[kb][s][r] = x;
-                    mx = fmaxf(mx, x);
-                }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m_run, mx);
-        // every key so far masked: m_new is -inf; subtract 0 instead, so that p = exp2(-inf) = 0 and nothing forms (-inf) - (-inf)
-        const float m_use = m_new == -INFINITY ? 0.f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);   // m_run = -inf: 0, and l_run and o are still 0
-        m_run = m_new;
-        l_run *= alpha;
-#pragma unroll
-        for (int d = 0; d < DB; ++d) o[d] *= alpha;
-        // P rounded to bf16 (what P V multiplies); the row sum is taken from the ROUNDED values, so O / l normalises what was accumulated
         bf16x8_t pf[2];
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb) {
-            uint4_t pw;
-#pragma unroll
-            for (int s = 0; s < 2; ++s)
-#pragma unroll
-                for (int r = 0; r < 4; r += 2) {
-                    const float p0 = __builtin_amdgcn_exp2f(st[kb][s][r] - m_use), p1 = __builtin_amdgcn_exp2f(st[kb][s][r + 1] - m_use);
-                    const uint32_t w = pack_bf16x2(p0, p1);
-                    pw[2 * s + (r >> 1)] = w;
-                    l_run += bf16lo_to_f32(w) + bf16hi_to_f32(w);
-                }
-            pf[kb] = __builtin_bit_cast(bf16x8_t, pw);
-        }
-        // ---- O^T += V^T P^T: A = V^T, lane (channel 16 d + l15, g) reads keys 32 kb + 8 g .. + 7 of its channel ----
-#pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-            for (int d = 0; d < DB; ++d) {
-                const bf16x8_t vf = *reinterpret_cast<const bf16x8_t *>(&vt[(d * 16 + l15) * VLD + kb * 32 + 8 * g]);
-                o[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[kb], o[d], 0, 0, 0);
-            }
+        atile_scores<D>(ks, qf, l15, g, st);
+        atile_softmax<DB>(st, mw, a.c2, m_run, l_run, o, pf);
+        atile_accumulate<D>(vt, pf, l15, g, o);
     }
 
     // ---- finalize: lane (query l15, g) holds channels 16 d + 4 g + r ----
     if (!live_wave || q_row >= a.Lq) return;
-    float l_tot = l_run + __shfl_xor(l_run, 16);
-    l_tot += __shfl_xor(l_tot, 32);
+    const float l_tot = atile_row_sum(l_run);
     if constexpr (SPLIT) {
         const long slot = ((long)bh * a.Lq + q_row) * a.splits + split;
         float *po = a.po + slot * D + 4 * g;
@@ -228,16 +164,7 @@ __global__ __launch_bounds__(XA_THREADS, 2) void xattn_fwd_kernel(const XattnArg
         for (int d = 0; d < DB; ++d) *reinterpret_cast<float4_t *>(po + d * 16) = o[d];
         if (g == 0) a.pml[slot] = (float2_t){m_run, l_tot};
     } else {
-        const bool none = m_run == -INFINITY;   // every key of the row masked (the groups of a query agree: m_run is the reduced maximum)
-        const float inv = 1.0f / l_tot;
-        uint16_t *op = a.out + (long)b * a.o_bs + (long)q_row * a.ldo + head * D + 4 * g;
-#pragma unroll
-        for (int d = 0; d < DB; ++d) {
-            uint2_t w;
-            w.x = none ? 0x7fc07fc0u : pack_bf16x2(o[d][0] * inv, o[d][1] * inv);
-            w.y = none ? 0x7fc07fc0u : pack_bf16x2(o[d][2] * inv, o[d][3] * inv);
-            *reinterpret_cast<uint2_t *>(op + d * 16) = w;
-        }
+        atile_store_row<DB>(a.out + (long)b * a.o_bs + (long)q_row * a.ldo + head * D + 4 * g, o, m_run, l_tot);
     }
 }
 
@@ -275,6 +202,8 @@ __global__ __launch_bounds__(256) void xattn_combine_kernel(const XattnArgs a, i
     }
     *reinterpret_cast<uint4_t *>(a.out + (long)b * a.o_bs + (long)i * a.ldo + head * D + ch) = w;
 }
+
+bool operand_aligned(const AttnOperand &x) { return aligned16(x.p) && x.ld % 8 == 0 && x.bs % 8 == 0; }
 
 bool sizes_ok(int B, int Lq, int Lk, int H, int D)
 {
@@ -316,18 +245,17 @@ long xattn_ws_bytes(int B, int Lq, int Lk, int H, int D)
 }
 
 // host-only: VLLM_OK where vllm_xattn_fwd_bf16 would launch (or has nothing to do), VLLM_EINVAL with the reason otherwise
-int xattn_fwd_check(const uint16_t *q, long q_bs, int ldq, const uint16_t *k, long k_bs, int ldk, const uint16_t *v, long v_bs, int ldv,
-                    const uint16_t *out, long o_bs, int ldo, int B, int Lq, int Lk, int H, int D, const void *ws, long ws_bytes)
+int xattn_fwd_check(const AttnOperand &q, const AttnOperand &k, const AttnOperand &v, const AttnOperand &out, int B, int Lq, int Lk, int H, int D,
+                    const void *ws, long ws_bytes)
 {
     VLLM_REQUIRE(D == 128 || D == 256, "xattn_fwd: head dim %d (128 or 256)", D);
     VLLM_REQUIRE(sizes_ok(B, Lq, Lk, H, D), "xattn_fwd: B=%d Lq=%d Lk=%d H=%d (B, Lq, Lk >= 0; H >= 1)", B, Lq, Lk, H);
     if ((long)B * Lq == 0) return VLLM_OK;
     VLLM_REQUIRE(Lk >= 1, "xattn_fwd: Lk=%d (at least one key)", Lk);
-    VLLM_REQUIRE(q && k && v && out, "xattn_fwd: null pointer (q / k / v / out)");
-    VLLM_REQUIRE(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out) && ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 &&
-                     q_bs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0 && o_bs % 8 == 0,
+    VLLM_REQUIRE(q.p && k.p && v.p && out.p, "xattn_fwd: null pointer (q / k / v / out)");
+    VLLM_REQUIRE(operand_aligned(q) && operand_aligned(k) && operand_aligned(v) && operand_aligned(out),
                  "xattn_fwd: misaligned operand (16-byte aligned pointers; row and batch strides multiples of 8 elements)");
-    VLLM_REQUIRE(ldq >= H * D && ldk >= H * D && ldv >= H * D && ldo >= H * D, "xattn_fwd: row stride below H D = %d", H * D);
+    VLLM_REQUIRE(q.ld >= H * D && k.ld >= H * D && v.ld >= H * D && out.ld >= H * D, "xattn_fwd: row stride below H D = %d", H * D);
     const long need = xattn_ws_bytes(B, Lq, Lk, H, D);
     if (need > 0) {
         VLLM_REQUIRE(ws, "xattn_fwd: null workspace (the plan splits the keys: %ld bytes)", need);
@@ -337,26 +265,19 @@ int xattn_fwd_check(const uint16_t *q, long q_bs, int ldq, const uint16_t *k, lo
     return VLLM_OK;
 }
 
-int xattn_fwd_launch(const uint16_t *q, long q_bs, int ldq, const uint16_t *k, long k_bs, int ldk, const uint16_t *v, long v_bs, int ldv,
-                     uint16_t *out, long o_bs, int ldo, const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D,
-                     float softmax_scale, void *ws, long ws_bytes, hipStream_t st)
+int xattn_fwd_launch(const AttnOperand &q, const AttnOperand &k, const AttnOperand &v, const AttnOperand &out, const uint8_t *key_padding_mask,
+                     int B, int Lq, int Lk, int H, int D, float softmax_scale, void *ws, long ws_bytes, hipStream_t st)
 {
-    const int rc = xattn_fwd_check(q, q_bs, ldq, k, k_bs, ldk, v, v_bs, ldv, out, o_bs, ldo, B, Lq, Lk, H, D, ws, ws_bytes);
+    const int rc = xattn_fwd_check(q, k, v, out, B, Lq, Lk, H, D, ws, ws_bytes);
     if (rc != VLLM_OK) return rc;
     if ((long)B * Lq == 0) return VLLM_OK;
     XattnArgs a;
-    a.q = q; a.k = k; a.v = v; a.out = out;
-    a.q_bs = q_bs; a.k_bs = k_bs; a.v_bs = v_bs; a.o_bs = o_bs;
-    a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo;
-    a.kpm = key_padding_mask;
-    a.B = B; a.Lq = Lq; a.Lk = Lk; a.H = H;
-    a.nqt = (Lq + XA_QBLK - 1) / XA_QBLK;
+    atile_fill_args(a, q, k, v, out, key_padding_mask, B, Lq, Lk, H, softmax_scale);
     plan(B, Lq, Lk, H, &a.splits, &a.kps);
-    a.c2 = softmax_scale * 1.4426950408889634f;
     const long rows = (long)B * H * Lq;
     a.po = a.splits > 1 ? static_cast<float *>(ws) : nullptr;
     a.pml = a.splits > 1 ? reinterpret_cast<float2_t *>(static_cast<float *>(ws) + rows * a.splits * D) : nullptr;
-    const long blocks = (long)(((long)B * H + 7) / 8) * 8 * a.nqt * a.splits, items = rows * (D / 8);
+    const long blocks = atile_blocks(B, H, (long)a.nqt * a.splits), items = rows * (D / 8);
     VLLM_REQUIRE(blocks < (1L << 31) && (items + 255) / 256 < (1L << 31), "xattn_fwd: too many workgroups (B H Lq / 64 >= 2^31)");
     const dim3 grid((unsigned)blocks);
     if (a.splits == 1) return D == 128 ? launch<128, false>(a, grid, st) : launch<256, false>(a, grid, st);
@@ -394,6 +315,6 @@ extern "C" int vllm_xattn_fwd_bf16(const uint16_t *q, long q_batch_stride, int l
                                    const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D, float softmax_scale,
                                    void *workspace, long workspace_bytes, vllm_stream_t stream)
 {
-    return xattn_fwd_launch(q, q_batch_stride, ldq, k, k_batch_stride, ldk, v, v_batch_stride, ldv, out, o_batch_stride, ldo,
+    return xattn_fwd_launch({q, q_batch_stride, ldq}, {k, k_batch_stride, ldk}, {v, v_batch_stride, ldv}, {out, o_batch_stride, ldo},
                             key_padding_mask, B, Lq, Lk, H, D, softmax_scale, workspace, workspace_bytes, (hipStream_t)stream);
 }
