@@ -642,6 +642,88 @@ long vllm_xattn_workspace_bytes(int B, int Lq, int Lk, int H, int D);
 int vllm_xattn_plan(int B, int Lq, int Lk, int H, int D, int *splits, int *keys_per_split);
 
 /* ------------------------------------------------------------------------------------------------
+ * f2g. The TEXT ENHANCER of Grounding-DINO and the whole ENCODER around the three blocks of its layer, bf16 modules (inference).
+ *
+ * Replaces the bodies of
+ *   GroundingDinoTextEnhancerLayer.forward   visionllmv2/model/grounding_dino/modeling_ov_grounding_dino_mask_dn.py:787-857
+ *   get_sine_pos_embed, GroundingDinoEncoderLayer.get_text_position_embeddings / .forward                          :1185-1290
+ *   GroundingDinoEncoder.get_reference_points / .forward                                                           :1560-1722
+ * with dropout the identity, without output_attentions / output_hidden_states.  The descriptors (struct VllmTextEnhancerDesc, struct
+ * VllmGdinoEncoderDesc) are tagged structs in vllm_hip_gdino_encoder.h, included here.
+ *
+ * The enhancer's launches, in order: [vllm_add_bf16: q = text + pos;] one GEMM with N = 2C on q -> [q | k] (in_proj rows 0 .. 2C); one
+ * GEMM with N = C on text -> v (rows 2C .. 3C); vllm_mha_fwd_masks_bf16 on the column slices; out_proj with `text` added in its epilogue;
+ * LayerNorm (layer_norm_before) in place; fc1 + ReLU / GELU; fc2 + residual; LayerNorm (layer_norm_after) -> out.  Every tensor between
+ * two launches is bf16, as in the bf16 module; scores, softmax, sums and statistics are fp32 with one rounding per stored tensor.
+ *
+ * THE MASK OF THE ENHANCER.  attn_mask is [n_masks, Lt, Lt] uint8, non-zero = may NOT attend, and (image b, head h) reads slab
+ * (b H + h) % n_masks.  n_masks = 1 is one shared mask; n_masks = B H is the 3-d mask of nn.MultiheadAttention; n_masks = B is what the
+ * reference's statement `attention_masks.repeat(self.num_heads, 1, 1)` (:839) comes to under nn.MultiheadAttention's indexing of a 3-d
+ * mask by b H + h: image b, head h attends under the mask of image (b H + h) % B -- not of image b, unless B = 1 or the masks are equal.
+ * That is the reference's behaviour and the call reproduces it exactly, without materialising the repeat.
+ *
+ * The encoder, once per call: vllm_encoder_refpoints_f32 (get_reference_points) and, unless the caller passes text_pos_embed,
+ * vllm_text_pos_embed_bf16 (the same tensor in every layer).  Then per layer: the launches of vllm_fusion_layer_forward, those of
+ * vllm_text_enhancer_forward on the fused text, those of vllm_deform_enc_layer_forward on the fused vision features (query = src +
+ * vision_pos).  Vision and text ping-pong in the workspace; the last layer writes the caller's outputs.
+ * ------------------------------------------------------------------------------------------------ */
+#include "vllm_hip_gdino_encoder.h"
+unsigned long vllm_text_enhancer_desc_sizeof(void);
+unsigned long vllm_gdino_encoder_desc_sizeof(void);
+/* Bytes of device scratch the two entries need; host-only; 0 for no rows (B Lt == 0; the encoder: B S == 0 or B Lt == 0), negative for a
+ * refused descriptor or sizes. */
+long vllm_text_enhancer_workspace_bytes(const struct VllmTextEnhancerDesc *desc, int B, int Lt);
+long vllm_gdino_encoder_workspace_bytes(const struct VllmGdinoEncoderDesc *desc, int B, int S, int Lt);
+long vllm_text_enhancer_calls(void);    /* calls of vllm_text_enhancer_forward in this process that reached their launches (tests) */
+long vllm_gdino_encoder_calls(void);    /* the same for vllm_gdino_encoder_forward, which touches no other entry's counter */
+/* text, out [B, Lt, C] bf16; pos [B, Lt, C] bf16 or NULL (queries and keys are `text` itself); attn_mask [n_masks, Lt, Lt] uint8 or NULL,
+ * n_masks >= 1.  A query row whose keys are all masked is NaN in that head's context, hence in the whole output row, as in the module.
+ * One stream, no allocation, no synchronisation, no runtime option.  A refused call (descriptor; sizes; NULL or misaligned operand; `out`
+ * overlapping an input; NULL, misaligned or short workspace: VLLM_EINVAL, reason in vllm_last_error()) has enqueued nothing; B Lt == 0
+ * returns VLLM_OK. */
+/* Alignment: text, pos, out, every weight / bias of the descriptor and workspace 16 bytes; attn_mask: element alignment. */
+int vllm_text_enhancer_forward(const struct VllmTextEnhancerDesc *desc, const uint16_t *text, const uint16_t *pos, const uint8_t *attn_mask,
+                               int n_masks, int B, int Lt, uint16_t *out, void *workspace, long workspace_bytes, vllm_stream_t stream);
+/* vision, vision_pos, out_vision [B, S, C] bf16; vision_padding_mask [B, S] uint8 (non-zero = padded) or NULL; valid_ratios [B, L, 2] fp32;
+ * spatial_shapes [L, 2] / level_start_index [L] device int64 describing S tokens; text, out_text [B, Lt, C] bf16; text_padding_mask [B, Lt]
+ * uint8 (non-zero = padded) or NULL; text_self_attn_mask [n_masks, Lt, Lt] uint8, ALREADY INVERTED (non-zero = may NOT attend: the
+ * caller applies the reference's `~` once per call); text_positions [B, Lt] fp32 or NULL (0 .. Lt - 1 for every image);
+ * text_pos_embed [B, Lt, C] bf16 or NULL (then it is computed from text_positions).  One stream, no allocation, no synchronisation, no
+ * runtime option.  A refused call (NULL or misaligned operand; a layer descriptor its own entry refuses; layers of differing d_model or
+ * n_levels; an output overlapping an input or the other output; NULL, misaligned or short workspace: VLLM_EINVAL, reason in
+ * vllm_last_error()) has enqueued nothing; B S == 0 or B Lt == 0 returns VLLM_OK. */
+/* Alignment: vision, vision_pos, text, text_pos_embed, both outputs, dim_t, every weight / bias and workspace 16 bytes; valid_ratios,
+ * spatial_shapes, level_start_index 8 bytes; text_positions 4 bytes; the masks: element alignment. */
+int vllm_gdino_encoder_forward(const struct VllmGdinoEncoderDesc *desc, const uint16_t *vision, const uint16_t *vision_pos,
+                               const uint8_t *vision_padding_mask, const float *valid_ratios, const int64_t *spatial_shapes,
+                               const int64_t *level_start_index, const uint16_t *text, const uint8_t *text_padding_mask,
+                               const uint8_t *text_self_attn_mask, int n_masks, const float *text_positions, const uint16_t *text_pos_embed,
+                               int B, int S, int Lt, uint16_t *out_vision, uint16_t *out_text, void *workspace, long workspace_bytes,
+                               vllm_stream_t stream);
+/* The three new kernels, exposed for the parity tests.  No atomics: the same bits on every run.
+ * vllm_mha_fwd_masks_bf16: vllm_mha_fwd_bf16 (section f2c: layouts, alignment, NaN rows) with attn_mask [n_masks, Lq, Lk] and slab
+ *   (b H + h) % n_masks for workgroup (b, h); n_masks = 1 is vllm_mha_fwd_bf16 itself, bit for bit (one launch function).
+ * vllm_text_pos_embed_bf16: out [B Lt, C] bf16 with row stride ld_out (elements, a multiple of 8, at least C); element i of row (b, t) is
+ *   sin (i even) or cos (i odd) of (p * 2 pi) / dim_t[i], p = positions[b, t], or t where positions is NULL -- fp32, a true division, the
+ *   accurate sinf / cosf, one rounding: get_sine_pos_embed(p[..., None], C, exchange_xy=False) (:1185-1214).  C a multiple of 64 in
+ *   64 .. 512.  Nothing is written outside the C columns of a row.
+ * vllm_encoder_refpoints_f32: out [B, S, L, 2] fp32, out[b, s, l', k] = ((c + 0.5) / (valid_ratios[b, l, k] * extent_k(l))) *
+ *   valid_ratios[b, l', k], token s lying in level l at column (k = 0, extent = width) / row (k = 1, extent = height) c: every product
+ *   and the division one fp32 operation in the reference's order (:1592-1605), so the bits are those of the module's statement run in
+ *   fp32 on the device.  1 <= L <= 16; level_start_index ascending from 0.
+ * A refused call (VLLM_EINVAL) has enqueued nothing; no rows returns VLLM_OK. */
+/* Alignment (vllm_mha_fwd_masks_bf16): q, k, v, out 16 bytes, the row and batch strides multiples of 8 elements; the masks: element alignment. */
+int vllm_mha_fwd_masks_bf16(const uint16_t *q, long q_batch_stride, int ldq, const uint16_t *k, long k_batch_stride, int ldk,
+                            const uint16_t *v, long v_batch_stride, int ldv, uint16_t *out, long o_batch_stride, int ldo,
+                            const uint8_t *attn_mask, int n_masks, const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D,
+                            float softmax_scale, vllm_stream_t stream);
+/* Alignment (vllm_text_pos_embed_bf16): dim_t, out 16 bytes; positions 4 bytes. */
+int vllm_text_pos_embed_bf16(const float *positions, const float *dim_t, int B, int Lt, int C, uint16_t *out, int ld_out, vllm_stream_t stream);
+/* Alignment (vllm_encoder_refpoints_f32): out 16 bytes; valid_ratios, spatial_shapes, level_start_index 8 bytes. */
+int vllm_encoder_refpoints_f32(const int64_t *spatial_shapes, const int64_t *level_start_index, const float *valid_ratios, int B, int S, int L,
+                               float *out, vllm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * f3b. The whole DCNv3 layer, bf16 modules (inference).
  *
  * Replaces the body of DCNv3.forward, visionllmv2/model/ops_dcnv3/modules/dcnv3.py:313-351, with the CenterFeatureScaleModule

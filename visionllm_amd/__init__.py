@@ -18,6 +18,10 @@ Host-side mirror of the reference's operator/module interfaces for that path onl
 * ``fusion_layer`` -- ``GroundingDinoFusionLayer`` (with ``GroundingDinoBiMultiHeadAttention`` and ``GroundingDinoDropPath``): the
   bi-directional image <-> text attention in front of every Grounding-DINO encoder layer, with the one-call native forward; the three
   names are also attributes of this package.
+* ``gdino_encoder`` -- ``GroundingDinoTextEnhancerLayer``, ``GroundingDinoEncoderLayer`` and ``GroundingDinoEncoder`` (with
+  ``get_sine_pos_embed`` and ``GroundingDinoEncoderOutput``): the text enhancer with its one-call native forward, the layer that chains
+  fusion layer, enhancer and deformable layer, and the whole encoder loop as one native call; the five names are also attributes of
+  this package.
 
 All compute goes through ``libvllm_hip.so`` (hand-written HIP, C ABI in ``include/vllm_hip.h``).  There is NO
 CPU fallback: calling an op without the built extension, or with CPU tensors, raises.
@@ -30,7 +34,9 @@ _ENCODER_EXPORTS = ("DeformableTransformerEncoderLayer", "GroundingDinoDeformabl
 _DECODER_EXPORTS = ("DeformableTransformerDecoderLayer", "GroundingDinoDecoderLayer", "GroundingDinoDecoder", "GroundingDinoMLPPredictionHead")
 _SELECTION_EXPORTS = ("GroundingDinoQuerySelection",)
 _FUSION_EXPORTS = ("GroundingDinoFusionLayer", "GroundingDinoBiMultiHeadAttention", "GroundingDinoDropPath")
-__all__ = ["build", "lib", "lib_path", *_ENCODER_EXPORTS, *_DECODER_EXPORTS, *_SELECTION_EXPORTS, *_FUSION_EXPORTS]
+_GDINO_ENCODER_EXPORTS = ("GroundingDinoTextEnhancerLayer", "GroundingDinoEncoderLayer", "GroundingDinoEncoder", "GroundingDinoEncoderOutput",
+                          "get_sine_pos_embed")
+__all__ = ["build", "lib", "lib_path", *_ENCODER_EXPORTS, *_DECODER_EXPORTS, *_SELECTION_EXPORTS, *_FUSION_EXPORTS, *_GDINO_ENCODER_EXPORTS]
 
 
 def __getattr__(name):
@@ -47,4 +53,7 @@ def __getattr__(name):
     if name in _FUSION_EXPORTS:
         from . import fusion_layer
         return getattr(fusion_layer, name)
+    if name in _GDINO_ENCODER_EXPORTS:
+        from . import gdino_encoder
+        return getattr(gdino_encoder, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,5 +1,6 @@
 """ctypes binding of libvllm_hip.so.  The header ``include/vllm_hip.h`` is the single source of truth: the prototypes AND the
-descriptor structs (``_lib.VllmVitDesc``, ...) are parsed from it when this module is imported, which does not load the library.
+descriptor structs (``_lib.VllmVitDesc``, ...) are parsed from it (and from ``include/vllm_hip_gdino_encoder.h``, which it includes
+for the two descriptors of its section f2g) when this module is imported, which does not load the library.
 Loading it (``lib()``) fails when a declared symbol is not exported, and checks every struct's size against the library's own
 ``vllm_*_sizeof()`` once."""
 import ctypes
@@ -10,6 +11,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 HEADER = os.path.join(_ROOT, "include", "vllm_hip.h")
+GDINO_ENCODER_HEADER = os.path.join(_ROOT, "include", "vllm_hip_gdino_encoder.h")   # section f2g's descriptors; vllm_hip.h includes it
 
 _lib = None
 
@@ -74,6 +76,9 @@ def _struct_class(path, name, body, structs):
     fields = []
     for decl in filter(None, (d.strip() for d in body.split(";"))):
         head = re.match(r"(?:const\s+)?(\w+)\b(.*)", decl, flags=re.S)
+        tagged = head and head.group(1) == "struct" and re.match(r"\s*(\w+)\b(.*)", head.group(2), flags=re.S)
+        if tagged and issubclass(structs.get(tagged.group(1), int), ctypes.Structure):   # `struct Tag *p`, Tag a struct read before
+            head = tagged
         base = head and (structs.get(head.group(1)) or _MEMBER_CTYPES.get(head.group(1)))
         members = [re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[\s*(\d+)\s*\])?\s*", d) for d in head.group(2).split(",")] if base else [None]
         if not all(members):
@@ -94,12 +99,16 @@ def parse_structs(path: str = HEADER):
     return structs
 
 
-def parse_tagged_structs(path: str = HEADER):
+def parse_tagged_structs(path: str = HEADER, known=None):
     """-> {tag: ctypes.Structure subclass} for every ``struct Tag { ... };`` of the header that has no typedef name (C callers write
-    ``struct Tag``), under the member rules of parse_structs; a member may name a typedef'd struct."""
-    known = parse_structs(path)
-    return {m.group(1): _struct_class(path, m.group(1), m.group(2), known)
-            for m in re.finditer(r"^struct\s+(\w+)\s*\{(.*?)\}\s*;", _strip_comments(path), flags=re.S | re.M)}
+    ``struct Tag``), under the member rules of parse_structs; a member may name a typedef'd struct, or as ``struct Tag`` a tagged one
+    read before it.  ``known``: the structs declared in front of ``path`` (a file that the header includes); default: the typedef'd
+    structs of ``path`` itself."""
+    known = dict(parse_structs(path) if known is None else known)
+    out = {}
+    for m in re.finditer(r"^struct\s+(\w+)\s*\{(.*?)\}\s*;", _strip_comments(path), flags=re.S | re.M):
+        out[m.group(1)] = known[m.group(1)] = _struct_class(path, m.group(1), m.group(2), known)
+    return out
 
 
 def header_abi_version(path: str = HEADER) -> int:
@@ -177,6 +186,8 @@ STRUCTS = parse_structs()
 globals().update(STRUCTS)
 TAGGED_STRUCTS = parse_tagged_structs()          # struct VllmFusionLayerDesc
 globals().update(TAGGED_STRUCTS)
+GDINO_ENCODER_STRUCTS = parse_tagged_structs(GDINO_ENCODER_HEADER, {**STRUCTS, **TAGGED_STRUCTS})   # struct VllmTextEnhancerDesc, struct VllmGdinoEncoderDesc
+globals().update(GDINO_ENCODER_STRUCTS)
 
 
 def pointer_fields(struct):
@@ -192,10 +203,10 @@ def _check_struct_layouts(L, protos):
     """Every struct against the library's own sizeof: ``VllmFooBar`` against ``vllm_foo_bar_sizeof()``.  One without such an export
     has to lie by value inside one that has it."""
     checked = []
-    for name, cls in {**STRUCTS, **TAGGED_STRUCTS}.items():
+    for name, cls in {**STRUCTS, **TAGGED_STRUCTS, **GDINO_ENCODER_STRUCTS}.items():
         fn = "vllm_" + re.sub(r"(?<!^)(?=[A-Z])", "_", name[len("Vllm"):]).lower() + "_sizeof"
         if fn not in protos:
-            if name in TAGGED_STRUCTS:
+            if name not in STRUCTS:
                 raise RuntimeError(f"include/vllm_hip.h: no {fn}() for struct {name}")
             continue
         if ctypes.sizeof(cls) != getattr(L, fn)():

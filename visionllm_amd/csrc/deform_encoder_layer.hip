@@ -17,6 +17,7 @@
 #include "msda_layer.hpp"
 #include "deform_blocks.hpp"
 #include "row_groups.hpp"
+#include "gdino_encoder.hpp"
 
 namespace vllm {
 namespace {
@@ -166,7 +167,9 @@ FfnBlock enc_ffn(const VllmDeformEncLayerDesc *d)
     return {d->fc1_w, d->fc1_b, d->fc2_w, d->fc2_b, d->norm2_w, d->norm2_b, d->act, d->d_ffn, d->norm2_eps};
 }
 
-int enc_check_desc(const VllmDeformEncLayerDesc *d)
+}  // namespace
+
+int enc_layer_check_desc(const VllmDeformEncLayerDesc *d)
 {
     VLLM_REQUIRE(d, "deform_enc_layer: null descriptor");
     TRY(msda_layer_check_desc(&d->attn));
@@ -180,9 +183,53 @@ int enc_check_desc(const VllmDeformEncLayerDesc *d)
     return VLLM_OK;
 }
 
-long g_calls = 0;
+long enc_layer_ws_bytes(const VllmDeformEncLayerDesc *d, int B, int S) { return enc_ws(d, B, S).total; }
 
-}  // namespace
+int enc_layer_check_call(const VllmDeformEncLayerDesc *d, const uint16_t *src, const uint16_t *pos, const uint16_t *query_in,
+                         const float *reference_points, const int64_t *spatial_shapes, const int64_t *level_start_index, int B, int S,
+                         const uint16_t *out, const uint16_t *query_out, const void *workspace, long workspace_bytes)
+{
+    VLLM_REQUIRE(src && reference_points && spatial_shapes && level_start_index && out, "deform_enc_layer: null pointer (src / reference_points / spatial_shapes / level_start_index / out)");
+    VLLM_REQUIRE(!query_out || pos, "deform_enc_layer: null pointer (query_out needs pos)");
+    const VllmMsdaLayerDesc &at = d->attn;
+    VLLM_REQUIRE(aligned16(src) && aligned16(pos) && aligned16(query_in) && aligned16(out) && aligned16(query_out) &&
+                     (reinterpret_cast<uintptr_t>(reference_points) & 7u) == 0,
+                 "deform_enc_layer: misaligned src / pos / query_in / out / query_out (16 bytes) or reference_points (8 bytes)");
+    for (const uint16_t *p : {d->norm1_w, d->norm1_b, d->fc1_w, d->fc1_b, d->fc2_w, d->fc2_b, d->norm2_w, d->norm2_b})
+        VLLM_REQUIRE(aligned16(p), "deform_enc_layer: misaligned weight or bias (16 bytes)");
+    for (const uint16_t *p : msda_weights(at)) VLLM_REQUIRE(aligned16(p), "deform_enc_layer: misaligned weight or bias (16 bytes)");
+    const EncWs w = enc_ws(d, B, S);
+    VLLM_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= w.total,
+                 "deform_enc_layer: workspace too small (%ld < %ld bytes) or misaligned", workspace_bytes, w.total);
+    return VLLM_OK;
+}
+
+int enc_layer_run(const VllmDeformEncLayerDesc *d, const uint16_t *src, const uint16_t *pos, const uint16_t *query_in, const float *reference_points,
+                  const uint8_t *padding_mask, const int64_t *spatial_shapes, const int64_t *level_start_index, int B, int S, uint16_t *out,
+                  uint16_t *query_out, void *workspace, hipStream_t st)
+{
+    const VllmMsdaLayerDesc &at = d->attn;
+    const EncWs w = enc_ws(d, B, S);
+    char *ws = (char *)workspace;
+    const long R = (long)B * S;
+    const int C = at.d_model;
+    uint16_t *t0 = (uint16_t *)(ws + w.t0), *x1 = (uint16_t *)(ws + w.x1), *h = (uint16_t *)(ws + w.h);
+    // 1. the query (modeling_unipose.py:3174 with_pos_embed; ...mask_dn.py:771-772)
+    const uint16_t *query = query_in ? query_in : src;
+    if (!query_in && pos) { TRY(add_launch(src, pos, t0, R * C, st)); query = t0; }
+    // 2. x1 = src + self_attn(query, reference_points, src) (:3174-3176; :1151-1164): the residual goes into output_proj's epilogue
+    TRY(msda_layer_run(&at, query, reference_points, src, padding_mask, spatial_shapes, level_start_index, B, S, S, x1,
+                       msda_layer_bufs(&at, ws + w.attn, B, S, S), nullptr, st, src));
+    // 3. norm1 (:3177; :1165), in place
+    TRY(add_layernorm_launch(x1, C, nullptr, 0, d->norm1_w, d->norm1_b, x1, C, nullptr, 0, nullptr, 0, R, C, d->norm1_eps, st));
+    // 4. - 6. t0 = x1 + linear2(act(linear1(x1))) (:3167-3168; :1167-1174), a slab of rows at a time (t0 held the query: the attention has read
+    // it); norm2 (:3169; :1175) -> out, and the next layer's query out + pos
+    return ffn_block_run(st, enc_ffn(d), x1, R, C, h, w.slab, t0, out, pos, query_out);
+}
+
+namespace {
+long g_calls = 0;
+}
 
 }  // namespace vllm
 
@@ -214,10 +261,10 @@ extern "C" long vllm_deform_enc_layer_calls(void) { return g_calls; }
 
 extern "C" long vllm_deform_enc_layer_workspace_bytes(const VllmDeformEncLayerDesc *d, int B, int S)
 {
-    if (enc_check_desc(d) != VLLM_OK) return -1;
+    if (enc_layer_check_desc(d) != VLLM_OK) return -1;
     if (B < 0 || S < 0 || (long)B * S >= (1L << 31)) { set_error("deform_enc_layer: B=%d S=%d (0 <= B S < 2^31)", B, S); return -1; }
     if ((long)B * S == 0) return 0;
-    return enc_ws(d, B, S).total;
+    return enc_layer_ws_bytes(d, B, S);
 }
 
 extern "C" int vllm_deform_enc_layer_forward(const VllmDeformEncLayerDesc *d, const uint16_t *src, const uint16_t *pos, const uint16_t *query_in,
@@ -225,36 +272,12 @@ extern "C" int vllm_deform_enc_layer_forward(const VllmDeformEncLayerDesc *d, co
                                              const int64_t *level_start_index, int B, int S, uint16_t *out, uint16_t *query_out, void *workspace,
                                              long workspace_bytes, vllm_stream_t stream)
 {
-    TRY(enc_check_desc(d));
+    TRY(enc_layer_check_desc(d));
     VLLM_REQUIRE(B >= 0 && S >= 0 && (long)B * S < (1L << 31), "deform_enc_layer: B=%d S=%d (0 <= B S < 2^31)", B, S);
     if ((long)B * S == 0) return VLLM_OK;
-    VLLM_REQUIRE(src && reference_points && spatial_shapes && level_start_index && out, "deform_enc_layer: null pointer (src / reference_points / spatial_shapes / level_start_index / out)");
-    VLLM_REQUIRE(!query_out || pos, "deform_enc_layer: null pointer (query_out needs pos)");
-    const VllmMsdaLayerDesc &at = d->attn;
-    VLLM_REQUIRE(aligned16(src) && aligned16(pos) && aligned16(query_in) && aligned16(out) && aligned16(query_out) &&
-                     (reinterpret_cast<uintptr_t>(reference_points) & 7u) == 0,
-                 "deform_enc_layer: misaligned src / pos / query_in / out / query_out (16 bytes) or reference_points (8 bytes)");
-    for (const uint16_t *p : {d->norm1_w, d->norm1_b, d->fc1_w, d->fc1_b, d->fc2_w, d->fc2_b, d->norm2_w, d->norm2_b})
-        VLLM_REQUIRE(aligned16(p), "deform_enc_layer: misaligned weight or bias (16 bytes)");
-    for (const uint16_t *p : msda_weights(at)) VLLM_REQUIRE(aligned16(p), "deform_enc_layer: misaligned weight or bias (16 bytes)");
-    const EncWs w = enc_ws(d, B, S);
-    VLLM_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= w.total,
-                 "deform_enc_layer: workspace too small (%ld < %ld bytes) or misaligned", workspace_bytes, w.total);
+    TRY(enc_layer_check_call(d, src, pos, query_in, reference_points, spatial_shapes, level_start_index, B, S, out, query_out, workspace,
+                             workspace_bytes));
     ++g_calls;
-    hipStream_t st = (hipStream_t)stream;
-    char *ws = (char *)workspace;
-    const long R = (long)B * S;
-    const int C = at.d_model;
-    uint16_t *t0 = (uint16_t *)(ws + w.t0), *x1 = (uint16_t *)(ws + w.x1), *h = (uint16_t *)(ws + w.h);
-    // 1. the query (modeling_unipose.py:3174 with_pos_embed; ...mask_dn.py:771-772)
-    const uint16_t *query = query_in ? query_in : src;
-    if (!query_in && pos) { TRY(add_launch(src, pos, t0, R * C, st)); query = t0; }
-    // 2. x1 = src + self_attn(query, reference_points, src) (:3174-3176; :1151-1164): the residual goes into output_proj's epilogue
-    TRY(msda_layer_run(&at, query, reference_points, src, padding_mask, spatial_shapes, level_start_index, B, S, S, x1,
-                       msda_layer_bufs(&at, ws + w.attn, B, S, S), nullptr, st, src));
-    // 3. norm1 (:3177; :1165), in place
-    TRY(add_layernorm_launch(x1, C, nullptr, 0, d->norm1_w, d->norm1_b, x1, C, nullptr, 0, nullptr, 0, R, C, d->norm1_eps, st));
-    // 4. - 6. t0 = x1 + linear2(act(linear1(x1))) (:3167-3168; :1167-1174), a slab of rows at a time (t0 held the query: the attention has read
-    // it); norm2 (:3169; :1175) -> out, and the next layer's query out + pos
-    return ffn_block_run(st, enc_ffn(d), x1, R, C, h, w.slab, t0, out, pos, query_out);
+    return enc_layer_run(d, src, pos, query_in, reference_points, padding_mask, spatial_shapes, level_start_index, B, S, out, query_out, workspace,
+                         (hipStream_t)stream);
 }

@@ -248,7 +248,8 @@ int attn_bwd_launch(const uint16_t *qkv, const uint16_t *out, const float *lse, 
 struct AttnOperand;
 int mha_fwd_check(const AttnOperand &q, const AttnOperand &k, const AttnOperand &v, const AttnOperand &out, int B, int Lq, int Lk, int H, int D);
 int mha_fwd_launch(const AttnOperand &q, const AttnOperand &k, const AttnOperand &v, const AttnOperand &out, const uint8_t *attn_mask,
-                   const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D, float softmax_scale, hipStream_t st);
+                   const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D, float softmax_scale, hipStream_t st, int n_masks = 1);
+// (n_masks: attn_mask is [n_masks, Lq, Lk] and (image b, head h) reads slab (b H + h) % n_masks -- vllm_mha_fwd_masks_bf16)
 
 // xattn.hip: masked cross attention for head dims 128 / 256 with an optional key split; the arguments of vllm_xattn_fwd_bf16.
 // xattn_fwd_check is the launch's own gate, host-only; xattn_ws_bytes the bytes the plan's partials take (0: one split).

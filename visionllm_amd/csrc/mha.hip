@@ -34,8 +34,9 @@ struct MhaArgs {
     uint16_t *out;
     long q_bs, k_bs, v_bs, o_bs;
     int ldq, ldk, ldv, ldo;
-    const uint8_t *am, *kpm;   // [Lq, Lk] / [B, Lk], non-zero = masked; null = none
-    int am_words;              // 1: the [Lq, Lk] mask can be read as 4-byte words (4-byte aligned, Lk % 4 == 0)
+    const uint8_t *am, *kpm;   // [n_masks, Lq, Lk] / [B, Lk], non-zero = masked; null = none
+    int am_words;              // 1: the mask can be read as 4-byte words (4-byte aligned, Lk % 4 == 0: every row of every slab starts on a word)
+    int n_masks;               // slabs of `am`; workgroup (b, head) reads slab (b H + head) % n_masks
     int B, Lq, Lk, H, nqt;
     float c2;                  // softmax_scale * log2(e)
 };
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(MHA_THREADS, 4) void mha_fwd_kernel(const MhaArgs a
     const bool live_wave = qt * MHA_QBLK + wave * 16 < a.Lq;   // wave-uniform
     bf16x8_t qf[KS];
     const int q_ld = atile_load_q<KS>(qb, q_row, a.Lq, a.ldq, g, qf);
-    const uint8_t *am = a.am ? a.am + (long)q_ld * a.Lk : nullptr;
+    const uint8_t *am = a.am ? a.am + atile_mask_slab(bh, a.n_masks, a.Lq, a.Lk) + (long)q_ld * a.Lk : nullptr;
 
     float4_t o[DB];
 #pragma unroll
@@ -171,14 +172,17 @@ int mha_fwd_check(const AttnOperand &q, const AttnOperand &k, const AttnOperand 
 }
 
 int mha_fwd_launch(const AttnOperand &q, const AttnOperand &k, const AttnOperand &v, const AttnOperand &out, const uint8_t *attn_mask,
-                   const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D, float softmax_scale, hipStream_t st)
+                   const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H, int D, float softmax_scale, hipStream_t st, int n_masks)
 {
     const int rc = mha_fwd_check(q, k, v, out, B, Lq, Lk, H, D);
     if (rc != VLLM_OK) return rc;
+    VLLM_REQUIRE(n_masks >= 1 && (long)n_masks * Lq * Lk < (1L << 40), "mha_fwd: n_masks=%d (at least 1)", n_masks);
     if ((long)B * Lq == 0) return VLLM_OK;
     MhaArgs a;
     atile_fill_args(a, q, k, v, out, key_padding_mask, B, Lq, Lk, H, softmax_scale);
     a.am = attn_mask;
+    a.n_masks = n_masks;
+    // (Lk % 4 == 0 makes Lq Lk a multiple of 4 too: a slab's offset keeps the words aligned for every n_masks)
     a.am_words = attn_mask && (reinterpret_cast<uintptr_t>(attn_mask) & 3u) == 0 && Lk % 4 == 0;
     const long blocks = atile_blocks(B, H, a.nqt);
     VLLM_REQUIRE(blocks < (1L << 31), "mha_fwd: too many workgroups (B H Lq / 64 >= 2^31)");
@@ -200,4 +204,13 @@ extern "C" int vllm_mha_fwd_bf16(const uint16_t *q, long q_batch_stride, int ldq
 {
     return mha_fwd_launch({q, q_batch_stride, ldq}, {k, k_batch_stride, ldk}, {v, v_batch_stride, ldv}, {out, o_batch_stride, ldo}, attn_mask,
                           key_padding_mask, B, Lq, Lk, H, D, softmax_scale, (hipStream_t)stream);
+}
+
+extern "C" int vllm_mha_fwd_masks_bf16(const uint16_t *q, long q_batch_stride, int ldq, const uint16_t *k, long k_batch_stride, int ldk,
+                                       const uint16_t *v, long v_batch_stride, int ldv, uint16_t *out, long o_batch_stride, int ldo,
+                                       const uint8_t *attn_mask, int n_masks, const uint8_t *key_padding_mask, int B, int Lq, int Lk, int H,
+                                       int D, float softmax_scale, vllm_stream_t stream)
+{
+    return mha_fwd_launch({q, q_batch_stride, ldq}, {k, k_batch_stride, ldk}, {v, v_batch_stride, ldv}, {out, o_batch_stride, ldo}, attn_mask,
+                          key_padding_mask, B, Lq, Lk, H, D, softmax_scale, (hipStream_t)stream, n_masks);
 }

@@ -47,6 +47,11 @@ __device__ __forceinline__ bool atile_block(int per, int BH, int &bh, int &rem)
     return bh < BH;
 }
 
+// Which [Lq, Lk] slab of an attention mask [n_masks, Lq, Lk] the workgroup of (image, head) pair bh = b H + h reads: slab bh % n_masks.
+// n_masks = 1 is one shared mask, B H one per (image, head) -- the 3-d mask of nn.MultiheadAttention -- and B what indexing
+// `mask.repeat(H, 1, 1)` by b H + h comes to (GroundingDinoTextEnhancerLayer.forward, ...mask_dn.py:837-839), without the copy.
+__device__ __forceinline__ long atile_mask_slab(int bh, int n_masks, int Lq, int Lk) { return (long)(bh % n_masks) * Lq * Lk; }
+
 // Q fragments (B operand): lane (query l15, g) holds Q[query][32 ks + 8 g .. + 7]; rows behind Lq read row Lq - 1.  Returns the row read.
 template <int KS>
 __device__ __forceinline__ int atile_load_q(const uint16_t *qb, int q_row, int Lq, int ldq, int g, bf16x8_t (&qf)[KS])
