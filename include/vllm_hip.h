@@ -724,6 +724,86 @@ int vllm_encoder_refpoints_f32(const int64_t *spatial_shapes, const int64_t *lev
                                float *out, vllm_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * f2h. The INPUTS of the Grounding-DINO encoder from the backbone's feature maps and the pixel mask, bf16 modules (inference).
+ *
+ * Replaces, of OVGroundingDinoModel in visionllmv2/model/grounding_dino/modeling_ov_grounding_dino_mask_dn.py,
+ *   input_proj_vision (1 x 1 Conv2d + GroupNorm(32) per map, 3 x 3 / stride 2 Conv2d + GroupNorm per extra level)   :2080-2111
+ *   the mask down-sampling of the backbone and of the extra levels                                                  :502, :2406
+ *   GroundingDinoSinePositionEmbedding.forward (normalize=True, scale 2 pi) and `+ level_embed[level]`               :529-564, :2164, :2429
+ *   get_valid_ratio                                                                                                 :2200-2209
+ *   the flatten / transpose / cat statements of forward                                                             :2388-2439
+ * The descriptor (struct VllmGdinoInputsDesc) is a tagged struct in vllm_hip_gdino_inputs.h, included here.
+ *
+ * Level l has H_l x W_l cells: a backbone map's own size for l < n_maps, else ((H_{l-1} - 1) / 2 + 1) x ((W_{l-1} - 1) / 2 + 1).  S is
+ * the sum of H_l W_l, level l's rows start at row sum_{l' < l} H_l' W_l' of every image.
+ * The launches per level: [vllm_nchw_to_rows_bf16 for a contiguous NCHW map; a channels-last map is the GEMM's operand in place] or
+ * [vllm_im2col3x3s2_bf16]; one vllm_gemm_bf16 (VLLM_EPI_BIAS; the conv output is bf16 in the workspace, the bf16 module's own rounding);
+ * the three kernels of vllm_groupnorm_rows_bf16, which write the level's rows of out_source.  Then vllm_pixel_mask_levels_u8 and
+ * vllm_sine_pos_embed_rows_bf16 for all levels at once.  No atomics on any output: the same inputs give the same bits on every run.
+ *
+ * ONE DEPARTURE.  The reference rounds the position embedding to bf16 (`.to(feature_map.dtype)`, :524) and then adds level_embed with a
+ * second rounding (:2429); vllm_sine_pos_embed_rows_bf16 adds level_embed in fp32 and rounds once.
+ * ------------------------------------------------------------------------------------------------ */
+#include "vllm_hip_gdino_inputs.h"
+unsigned long vllm_gdino_inputs_desc_sizeof(void);
+long vllm_gdino_inputs_calls(void);   /* calls of vllm_gdino_inputs_forward in this process that reached their launches (tests) */
+/* Bytes of device scratch vllm_gdino_inputs_forward needs; host-only; map_h, map_w, map_format HOST arrays [n_maps] as for the call;
+ * 0 for B == 0, negative for a refused descriptor or sizes. */
+long vllm_gdino_inputs_workspace_bytes(const struct VllmGdinoInputsDesc *desc, int B, const int *map_h, const int *map_w, const int *map_format);
+/* maps: HOST array [n_maps] of device pointers, map l bf16 [B, c_in[l], map_h[l], map_w[l]] contiguous (map_format[l] == 0) or
+ * channels-last [B, map_h[l], map_w[l], c_in[l]] (map_format[l] == 1); map_h, map_w, map_format HOST arrays.  pixel_mask [B, H, W] of
+ * mask_elem_bytes 1 (bool / uint8) or 8 (int64), non-zero = a real pixel.  out_source, out_pos [B, S, C] bf16; out_mask [B, S] uint8
+ * (1 = a real cell); out_valid_ratios [B, n_levels, 2] fp32 (width ratio, height ratio).  One stream, no allocation, no
+ * synchronisation, no runtime option.  A refused call (descriptor; sizes outside the contract: a map extent or H, W below 1, B S or
+ * a GEMM operand reaching 2^31; an unknown format or mask element size; NULL or misaligned operand; outputs overlapping each other; NULL,
+ * misaligned or short workspace, or one overlapping an operand: VLLM_EINVAL, reason in vllm_last_error()) has enqueued nothing; B == 0
+ * returns VLLM_OK. */
+/* Alignment: every map, out_source, out_pos, every weight / bias / parameter of the descriptor, level_embed, dim_t and workspace 16
+ * bytes; out_valid_ratios 8 bytes; pixel_mask its element size; out_mask: element alignment. */
+int vllm_gdino_inputs_forward(const struct VllmGdinoInputsDesc *desc, const uint16_t *const *maps, const int *map_h, const int *map_w,
+                              const int *map_format, const void *pixel_mask, int mask_elem_bytes, int B, int H, int W, uint16_t *out_source,
+                              uint16_t *out_pos, uint8_t *out_mask, float *out_valid_ratios, void *workspace, long workspace_bytes,
+                              vllm_stream_t stream);
+/* The five new kernels, exposed for the parity tests.  A refused call (VLLM_EINVAL) has enqueued nothing; no rows returns VLLM_OK.
+ * vllm_groupnorm_rows_bf16: nn.GroupNorm(32, C) (:2090) over B channels-last images x [B HW, C] bf16 (row stride ldx, image b at row b HW),
+ *   C a multiple of 64 in 64 .. 512 (2 .. 16 channels per group).  Statistics per (image, group) over HW C / 32 elements in fp32: every
+ *   slab of 32 rows gives {count, mean, M2}, M2 taken about the slab's own mean; the slabs are combined in a fixed order with Chan's
+ *   formula (never E[x^2] - E[x]^2); the variance is biased.  A second pass writes (x - mean) rstd gamma + beta with one rounding to
+ *   out + b out_batch_stride + row ldo (elements): a level's rows inside a [B, S, C] tensor, so the level `cat` (:2433) never happens.
+ *   HW == 1 and a constant map give beta exactly (eps > 0).  Nothing is written outside the C columns of a row.  workspace:
+ *   vllm_groupnorm_rows_workspace_bytes(B, HW, C) bytes (negative for refused sizes).
+ * vllm_nchw_to_rows_bf16: out[(b HW + p) ld_out + c] = in[(b Cin + c) HW + p]: the `flatten(2).transpose(1, 2)` of :2426 in front of the
+ *   conv instead of behind it, through 64 x 64 LDS tiles.  Cin a multiple of 64; `in` 16-byte aligned (any HW).
+ * vllm_im2col3x3s2_bf16: out [B Ho Wo, 9 Cin], Ho = (Hi - 1) / 2 + 1, Wo = (Wi - 1) / 2 + 1, row (b, oy, ox) = the 3 x 3 patch at
+ *   (2 oy - 1 + ky, 2 ox - 1 + kx) in (ky, kx, c) order from channels-last rows src + b src_batch_stride + (y Wi + x) ld_src; taps in the
+ *   padding are zeros (:2097).  Cin a multiple of 8.
+ * vllm_pixel_mask_levels_u8: for every level (level_h, level_w HOST arrays [L], 1 <= L <= 8) the nearest-neighbour down-sampled mask
+ *   of F.interpolate (:502, :2406) -- source index min(floor(dst * (float(in) / out)), in - 1), the scale and the product in fp32 -- as
+ *   out_mask [B, S] uint8; the inclusive prefix counts of valid cells along y and along x (the cumsums of :549-550) as int32 [B, S] each;
+ *   out_valid_ratios [B, L, 2] fp32 with the bits of get_valid_ratio (:2200-2209) on the device: count * (1 / extent) in fp32, which is
+ *   what torch's division of a device tensor by a host scalar computes.
+ * vllm_sine_pos_embed_rows_bf16: out [B, S, C] bf16 from the prefix counts: channel i < C / 2 of cell (y, x) is sin (i even) / cos (i odd)
+ *   of ((ycnt / (ycnt_last_row + 1e-6)) * 2 pi) / dim_t[i], channel C / 2 + i the same of xcnt and the row's last column, in fp32 in the
+ *   statement's order (:553-562) with true divisions and the accurate sinf / cosf, + level_embed[l, channel], one rounding (the departure
+ *   above).  dim_t [C / 2] fp32.  A fully masked image gives 0 / (0 + 1e-6) = 0. */
+/* Alignment (vllm_groupnorm_rows_bf16): x, gamma, beta, out, workspace 16 bytes; ldx, ldo, out_batch_stride multiples of 8 elements. */
+int vllm_groupnorm_rows_bf16(const uint16_t *x, int ldx, const uint16_t *gamma, const uint16_t *beta, float eps, int B, int HW, int C,
+                             uint16_t *out, long out_batch_stride, int ldo, void *workspace, long workspace_bytes, vllm_stream_t stream);
+long vllm_groupnorm_rows_workspace_bytes(int B, int HW, int C);
+/* Alignment (vllm_nchw_to_rows_bf16): in, out 16 bytes; ld_out a multiple of 8 elements. */
+int vllm_nchw_to_rows_bf16(const uint16_t *in, int B, int Cin, int HW, uint16_t *out, int ld_out, vllm_stream_t stream);
+/* Alignment (vllm_im2col3x3s2_bf16): src, out 16 bytes; ld_src, src_batch_stride multiples of 8 elements. */
+int vllm_im2col3x3s2_bf16(const uint16_t *src, long src_batch_stride, int ld_src, int B, int Hi, int Wi, int Cin, uint16_t *out,
+                          vllm_stream_t stream);
+/* Alignment (vllm_pixel_mask_levels_u8): pixel_mask its element size; out_ycnt, out_xcnt 4 bytes; out_valid_ratios 8 bytes; out_mask:
+ * element alignment. */
+int vllm_pixel_mask_levels_u8(const void *pixel_mask, int mask_elem_bytes, int B, int H, int W, const int *level_h, const int *level_w, int L,
+                              uint8_t *out_mask, int32_t *out_ycnt, int32_t *out_xcnt, float *out_valid_ratios, vllm_stream_t stream);
+/* Alignment (vllm_sine_pos_embed_rows_bf16): level_embed, dim_t, out 16 bytes; ycnt, xcnt 4 bytes. */
+int vllm_sine_pos_embed_rows_bf16(const int32_t *ycnt, const int32_t *xcnt, const int *level_h, const int *level_w, int L, int B, int C,
+                                  const uint16_t *level_embed, const float *dim_t, uint16_t *out, vllm_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * f3b. The whole DCNv3 layer, bf16 modules (inference).
  *
  * Replaces the body of DCNv3.forward, visionllmv2/model/ops_dcnv3/modules/dcnv3.py:313-351, with the CenterFeatureScaleModule

@@ -22,6 +22,10 @@ Host-side mirror of the reference's operator/module interfaces for that path onl
   ``get_sine_pos_embed`` and ``GroundingDinoEncoderOutput``): the text enhancer with its one-call native forward, the layer that chains
   fusion layer, enhancer and deformable layer, and the whole encoder loop as one native call; the five names are also attributes of
   this package.
+* ``gdino_inputs`` -- ``GroundingDinoEncoderInputs`` (with ``GroundingDinoSinePositionEmbedding`` and
+  ``GroundingDinoEncoderInputsOutput``): the step between the backbone's feature maps and that encoder -- input projections with
+  GroupNorm, the mask pyramid, the sine position embedding + level embedding, valid ratios -- with the one-call native forward; the
+  three names are also attributes of this package.
 
 All compute goes through ``libvllm_hip.so`` (hand-written HIP, C ABI in ``include/vllm_hip.h``).  There is NO
 CPU fallback: calling an op without the built extension, or with CPU tensors, raises.
@@ -36,7 +40,9 @@ _SELECTION_EXPORTS = ("GroundingDinoQuerySelection",)
 _FUSION_EXPORTS = ("GroundingDinoFusionLayer", "GroundingDinoBiMultiHeadAttention", "GroundingDinoDropPath")
 _GDINO_ENCODER_EXPORTS = ("GroundingDinoTextEnhancerLayer", "GroundingDinoEncoderLayer", "GroundingDinoEncoder", "GroundingDinoEncoderOutput",
                           "get_sine_pos_embed")
-__all__ = ["build", "lib", "lib_path", *_ENCODER_EXPORTS, *_DECODER_EXPORTS, *_SELECTION_EXPORTS, *_FUSION_EXPORTS, *_GDINO_ENCODER_EXPORTS]
+_GDINO_INPUTS_EXPORTS = ("GroundingDinoEncoderInputs", "GroundingDinoSinePositionEmbedding", "GroundingDinoEncoderInputsOutput")
+__all__ = ["build", "lib", "lib_path", *_ENCODER_EXPORTS, *_DECODER_EXPORTS, *_SELECTION_EXPORTS, *_FUSION_EXPORTS, *_GDINO_ENCODER_EXPORTS,
+           *_GDINO_INPUTS_EXPORTS]
 
 
 def __getattr__(name):
@@ -56,4 +62,7 @@ def __getattr__(name):
     if name in _GDINO_ENCODER_EXPORTS:
         from . import gdino_encoder
         return getattr(gdino_encoder, name)
+    if name in _GDINO_INPUTS_EXPORTS:
+        from . import gdino_inputs
+        return getattr(gdino_inputs, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

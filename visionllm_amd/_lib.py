@@ -1,6 +1,7 @@
 """ctypes binding of libvllm_hip.so.  The header ``include/vllm_hip.h`` is the single source of truth: the prototypes AND the
-descriptor structs (``_lib.VllmVitDesc``, ...) are parsed from it (and from ``include/vllm_hip_gdino_encoder.h``, which it includes
-for the two descriptors of its section f2g) when this module is imported, which does not load the library.
+descriptor structs (``_lib.VllmVitDesc``, ...) are parsed from it (and from ``include/vllm_hip_gdino_encoder.h`` and
+``include/vllm_hip_gdino_inputs.h``, which it includes for the descriptors of its sections f2g and f2h) when this module is imported,
+which does not load the library.
 Loading it (``lib()``) fails when a declared symbol is not exported, and checks every struct's size against the library's own
 ``vllm_*_sizeof()`` once."""
 import ctypes
@@ -12,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 HEADER = os.path.join(_ROOT, "include", "vllm_hip.h")
 GDINO_ENCODER_HEADER = os.path.join(_ROOT, "include", "vllm_hip_gdino_encoder.h")   # section f2g's descriptors; vllm_hip.h includes it
+GDINO_INPUTS_HEADER = os.path.join(_ROOT, "include", "vllm_hip_gdino_inputs.h")     # section f2h's descriptor; vllm_hip.h includes it
 
 _lib = None
 
@@ -188,6 +190,8 @@ TAGGED_STRUCTS = parse_tagged_structs()          # struct VllmFusionLayerDesc
 globals().update(TAGGED_STRUCTS)
 GDINO_ENCODER_STRUCTS = parse_tagged_structs(GDINO_ENCODER_HEADER, {**STRUCTS, **TAGGED_STRUCTS})   # struct VllmTextEnhancerDesc, struct VllmGdinoEncoderDesc
 globals().update(GDINO_ENCODER_STRUCTS)
+GDINO_INPUTS_STRUCTS = parse_tagged_structs(GDINO_INPUTS_HEADER, {**STRUCTS, **TAGGED_STRUCTS, **GDINO_ENCODER_STRUCTS})   # struct VllmGdinoInputsDesc
+globals().update(GDINO_INPUTS_STRUCTS)
 
 
 def pointer_fields(struct):
@@ -203,7 +207,7 @@ def _check_struct_layouts(L, protos):
     """Every struct against the library's own sizeof: ``VllmFooBar`` against ``vllm_foo_bar_sizeof()``.  One without such an export
     has to lie by value inside one that has it."""
     checked = []
-    for name, cls in {**STRUCTS, **TAGGED_STRUCTS, **GDINO_ENCODER_STRUCTS}.items():
+    for name, cls in {**STRUCTS, **TAGGED_STRUCTS, **GDINO_ENCODER_STRUCTS, **GDINO_INPUTS_STRUCTS}.items():
         fn = "vllm_" + re.sub(r"(?<!^)(?=[A-Z])", "_", name[len("Vllm"):]).lower() + "_sizeof"
         if fn not in protos:
             if name not in STRUCTS:

@@ -1,5 +1,5 @@
 // Host-side scaffolding shared by the orchestrators (vit.cpp, layer_train.cpp, bridge_train.cpp, region_train.cpp, embed_train.hip,
-// msda_layer.hip, msda_layer_train.cpp, dcnv3_layer.hip, deform_encoder_layer.hip, deform_decoder_layer.hip, deform_decoder.hip, query_select.hip, fusion_layer.cpp, gdino_encoder.hip): the
+// msda_layer.hip, msda_layer_train.cpp, dcnv3_layer.hip, deform_encoder_layer.hip, deform_decoder_layer.hip, deform_decoder.hip, query_select.hip, fusion_layer.cpp, gdino_encoder.hip, gdino_inputs.hip): the
 // pieces every entry point that strings kernels together on the caller's stream used to copy from the one before.  Host code only.
 #pragma once
 #include <initializer_list>
