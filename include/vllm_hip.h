@@ -322,6 +322,11 @@ int vllm_dcnv3_backward_f16(const uint16_t *input, const uint16_t *offset, const
                             int W, int G, int C, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, float offset_scale,
                             uint16_t *grad_input, uint16_t *grad_offset, uint16_t *grad_mask, void *workspace, long workspace_bytes,
                             vllm_stream_t stream);
+/* Kernel launches of this process per DCNv3 route (tests / tuning), counted on the host where the launch is made: 0 gather forward
+ * (every dtype), 1 pipelined forward (dcnv3_tiled 1 / 2), 2 two-blocks-per-CU forward (3 / 4), 3 vectorised backward (4 / 8 / 16 / 32 /
+ * 64 group channels), 4 generic backward, 5 windowed matrix-core backward (dcnv3_bwd_tiled 1, group channels 32; the half-precision
+ * backward runs the fp32 routes and counts there).  -1 for any other route. */
+long vllm_dcnv3_route_launches(int route);
 
 /* ------------------------------------------------------------------------------------------------
  * f2b. The whole deformable ENCODER layer around the attention layer above, bf16 modules (inference).

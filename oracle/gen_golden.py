@@ -482,6 +482,48 @@ def gen_dcnv3():
     case("bwd_c71", 2, 8, 8, 2, 71, 3, 3, 1, 1, 1, 1, 2.0, 33)
 
 
+def gen_dcnv3_geometry():
+    """DCNv3 with kernel, stride and dilation that differ between h and w: the reference's pure-PyTorch twin and its fp64 autograd on
+    the entries of tests/dcnv3_geometry_inputs.py that the twin can express.  It pads W by pad_h and H by pad_w (dcnv3_func.py:129-131),
+    so every entry runs with pad_h == pad_w (the larger of the table's two pads where they differ); unequal pads are anchored by the
+    padding identity of tests/test_dcnv3_geometry_cpu.py instead.  N 1, a 9 x 12 map, 2 groups of 4 and of 5 channels.
+    -> tests/golden/dcnv3_geometry.npz, keys "<entry>.c<channels>.<key of the dcnv3_*.npz files>", arrays only."""
+    glb = {"torch": torch, "F": F}
+    fns = ast_extract(f"{REF}/visionllmv2/model/ops_dcnv3/functions/dcnv3_func.py",
+                      ["_get_reference_points", "_generate_dilation_grids", "dcnv3_core_pytorch"], glb)
+    glb.update(fns)
+    core = fns["dcnv3_core_pytorch"]
+    N, H, W, M = 1, 9, 12, 2
+    rec = {}
+    #                  kh kw sh sw ph pw dh dw  offset_scale
+    entries = {"k2x3": (2, 3, 1, 1, 1, 1, 1, 1, 1.0),
+               "s1x2": (3, 3, 1, 2, 1, 1, 1, 1, 1.7),
+               "s2x1": (3, 3, 2, 1, 1, 1, 1, 1, 1.0),
+               "d2x1": (3, 3, 1, 1, 2, 2, 2, 1, 1.7),
+               "k3x2_s1x2_d2x1": (3, 2, 1, 2, 2, 2, 2, 1, 1.3)}
+    for e, (tag, (kh, kw, sh, sw, ph, pw, dh, dw, scale)) in enumerate(entries.items()):
+        for D in (4, 5):
+            torch.manual_seed(50 + 2 * e + D)
+            Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1
+            Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
+            P = kh * kw
+            inp = torch.randn(N, H, W, M * D)
+            offset = torch.randn(N, Ho, Wo, M * P * 2) * 2.0
+            mask = torch.rand(N, Ho, Wo, M, P) + 1e-5
+            mask = (mask / mask.sum(-1, keepdim=True)).reshape(N, Ho, Wo, M * P)
+            grad_out = torch.randn(N, Ho, Wo, M * D, dtype=torch.float64)
+            a, b, c = (t.double().requires_grad_(True) for t in (inp, offset, mask))
+            out = core(a, b, c, kh, kw, sh, sw, ph, pw, dh, dw, M, D, scale)
+            out.backward(grad_out)
+            k = f"{tag}.c{D}."
+            rec.update({k + "input": inp.numpy(), k + "offset": offset.numpy(), k + "mask": mask.numpy(), k + "grad_out": grad_out.numpy(),
+                        k + "params": np.array([kh, kw, sh, sw, ph, pw, dh, dw, M, D], dtype=np.int64), k + "offset_scale": np.array(scale),
+                        k + "out_f64": out.detach().numpy(), k + "grad_input_f64": a.grad.numpy(), k + "grad_offset_f64": b.grad.numpy(),
+                        k + "grad_mask_f64": c.grad.numpy()})
+            print(f"dcnv3_geometry {tag} c{D}: out {tuple(out.shape)} |out| max {float(out.abs().max()):.3g} |grad_offset| max {float(b.grad.abs().max()):.3g}")
+    np.savez_compressed(os.path.join(OUT, "dcnv3_geometry.npz"), **rec)
+
+
 def gen_dcnv3_half():
     """DCNv3 in half precision (round 5; the reference dispatches AT_DISPATCH_FLOATING_TYPES_AND_HALF with opmath_t = float,
     ops_dcnv3/src/cuda/dcnv3_cuda.cu:69, 147: half operands, fp32 arithmetic, the result rounded to half).  F.grid_sample has no CPU
@@ -705,6 +747,7 @@ if __name__ == "__main__":
     gen_token_loops()
     gen_region_branch()
     gen_dcnv3()
+    gen_dcnv3_geometry()
     gen_dcnv3_half()
     gen_point_sample()
     gen_intern_vit()

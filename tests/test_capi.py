@@ -10,7 +10,7 @@ from visionllm_amd import _lib
 
 def test_header_parses_and_names_are_prefixed():
     protos = _lib.parse_header()
-    assert "vllm_msda_forward_f32" in protos and "vllm_last_error" in protos
+    assert "vllm_msda_forward_f32" in protos and "vllm_last_error" in protos and "vllm_dcnv3_route_launches" in protos
     assert all(n.startswith("vllm_") for n in protos)
 
 

@@ -20,6 +20,9 @@ bool dcnv3_pipe_ok(const Dcnv3Geo &q);                                          
 int dcnv3_pipe_launch(const float *in, const float *off, const float *msk, const Dcnv3Geo &q, float offset_scale, float *out, int prof,
                       hipStream_t st);
 
+static long g_route_launches[DCN_ROUTE_COUNT] = {};   // (vllm_dcnv3_route_launches: tests assert the route they mean to cover ran)
+void dcnv3_count_route(int route) { __atomic_add_fetch(&g_route_launches[route], 1, __ATOMIC_RELAXED); }
+
 namespace {
 
 typedef _Float16 half4_t __attribute__((ext_vector_type(4)));
@@ -127,6 +130,7 @@ int dcnv3_launch(const TIO *in, const TIO *off, const TIO *msk, Dcnv3Geo q, T of
     VLLM_REQUIRE(total < (1L << 40), "dcnv3: too many output elements");
     const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
     const bool k3 = q.kh == 3 && q.kw == 3;
+    dcnv3_count_route(DCN_ROUTE_FWD_GATHER);
     if (vec && k3) VLLM_LAUNCH((dcnv3_fwd_kernel<TIO, T, 4, true>), grid, block, 0, st, in, off, msk, out, total, q, offset_scale);
     else if (vec) VLLM_LAUNCH((dcnv3_fwd_kernel<TIO, T, 4, false>), grid, block, 0, st, in, off, msk, out, total, q, offset_scale);
     else if (k3) VLLM_LAUNCH((dcnv3_fwd_kernel<TIO, T, 1, true>), grid, block, 0, st, in, off, msk, out, total, q, offset_scale);
@@ -150,6 +154,11 @@ int make_geo(Dcnv3Geo &q, int N, int H, int W, int G, int C, int kh, int kw, int
 }  // namespace vllm
 
 using namespace vllm;
+
+extern "C" long vllm_dcnv3_route_launches(int route)
+{
+    return route >= 0 && route < DCN_ROUTE_COUNT ? __atomic_load_n(&g_route_launches[route], __ATOMIC_RELAXED) : -1;
+}
 
 extern "C" int vllm_dcnv3_forward_f32(const float *input, const float *offset, const float *mask, int N, int H, int W,
                                       int G, int C, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,

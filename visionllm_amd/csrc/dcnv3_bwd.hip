@@ -205,12 +205,14 @@ int dcnv3_bwd_launch(const T *in, const T *off, const T *msk, const T *gout, Dcn
     if (vec) {
         const long total = pix * lpg;
         const dim3 grid((unsigned)ceil_div(total, 256)), block(256);
+        dcnv3_count_route(DCN_ROUTE_BWD_VEC);
 #define GO(LL) VLLM_LAUNCH((dcnv3_bwd_vec_kernel<T, LL>), grid, block, 0, st, in, off, msk, gout, gin, goff, gmsk, total, q, offset_scale)
         switch (lpg) { case 1: GO(1); break; case 2: GO(2); break; case 4: GO(4); break; case 8: GO(8); break; default: GO(16); }
 #undef GO
         VLLM_CHECK_LAUNCH("dcnv3_bwd_vec_kernel");
         return VLLM_OK;
     }
+    dcnv3_count_route(DCN_ROUTE_BWD_GENERIC);
     VLLM_LAUNCH((dcnv3_bwd_generic_kernel<T>), dim3((unsigned)ceil_div(pix, 256)), dim3(256), 0, st, in, off, msk, gout, gin, goff, gmsk,
                 pix, q, offset_scale);
     VLLM_CHECK_LAUNCH("dcnv3_bwd_generic_kernel");

@@ -17,6 +17,12 @@ struct Dcnv3Geo {
 // for a location within 1 ulp of an integer that build can pick the neighbouring cell (grad_offset then differs by a whole cell's
 // slope).  No reference build exists here to compare against (CUDA only); the half-precision fixture keeps its
 // locations away from integers for that reason.
+// Host-side launch counters of the DCNv3 routes (vllm_dcnv3_route_launches; defined in dcnv3.hip): each launch site counts itself, so a
+// test can assert that the kernel it names took the call.
+enum { DCN_ROUTE_FWD_GATHER = 0, DCN_ROUTE_FWD_PIPE, DCN_ROUTE_FWD_TILED, DCN_ROUTE_BWD_VEC, DCN_ROUTE_BWD_GENERIC, DCN_ROUTE_BWD_WINDOWED,
+       DCN_ROUTE_COUNT };
+void dcnv3_count_route(int route);
+
 #ifdef __HIPCC__
 template <typename T>
 __device__ __forceinline__ T dcn_mul_rn(T a, T b)

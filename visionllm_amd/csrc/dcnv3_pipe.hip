@@ -551,6 +551,7 @@ int dp_go(const float *in, const float *off, const float *msk, const Dcnv3Geo &q
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&dcnv3_fwd_pipe_kernel<CPG, WIN, PROF>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
+    dcnv3_count_route(DCN_ROUTE_FWD_PIPE);
     VLLM_LAUNCH((dcnv3_fwd_pipe_kernel<CPG, WIN, PROF>), dim3((unsigned)((cus / 8) * 8 * DP_BPC)), dim3(DP_THREADS), lds, st, in, off, msk, out,
                 q, offset_scale);
     VLLM_CHECK_LAUNCH("dcnv3_fwd_pipe_kernel");

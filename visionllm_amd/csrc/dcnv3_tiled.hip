@@ -307,6 +307,7 @@ int dt_go(const float *in, const float *off, const float *msk, const Dcnv3Geo &q
     const long items = (long)q.N * q.G * ((q.Ho + DT_TH - 1) / DT_TH) * ((q.Wo + DT_TW - 1) / DT_TW);
     long blocks = (long)(cus / 8) * 8 * 2;
     if (blocks > ((items + 7) / 8) * 8) blocks = ((items + 7) / 8) * 8;
+    dcnv3_count_route(DCN_ROUTE_FWD_TILED);
     VLLM_LAUNCH((dcnv3_fwd_tiled_kernel<CPG, WIN, PROF>), dim3((unsigned)blocks), dim3(DT_THREADS), lds, st, in, off, msk, out, q,
                 offset_scale);
     VLLM_CHECK_LAUNCH("dcnv3_fwd_tiled_kernel");

@@ -577,6 +577,7 @@ int dcnv3_bwd_mfma_launch(const float *input, const float *offset, const float *
     }
     const int grid = (cus / 8) * 8 * BT_BLOCKS_PER_CU;
     const int L = (q.kh * q.kw + 3) / 4;
+    dcnv3_count_route(DCN_ROUTE_BWD_WINDOWED);
     VLLM_LAUNCH(msda_bwd_mfma_kernel<true>, dim3(grid), dim3(BT_THREADS), BT_LDS, st, input, nullptr, nullptr, offset, mask, grad_out, q.N,
                 q.H * q.W, q.G, L, q.Ho * q.Wo, grad_input, grad_offset, grad_mask, q, offset_scale);
     VLLM_CHECK_LAUNCH("msda_bwd_mfma_kernel<dcnv3>");
